@@ -7,11 +7,17 @@ gradient all-reduce (N>1) and a plain SGD update of all block parameters.  Input
 in HBM when the timed region starts.  `value` = volumes (patches) per second over all ranks.
 
     python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full
+    python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0 (see the driver contract), including
+Prints ONE JSON line on rank 0 (see the driver contract).  A plain run sets up, warms up, times exactly `--steps` steps once and
+prints the headline (`value`, `ms_per_step`, ...).  `--full` adds everything else:
+  "repetitions":  the timed region run `--reps` (default 3) times back to back, the median reported
   "roofline":     dominant kernel, algorithmic flops|bytes per launch / HIP-event duration, vs the MI355X peak
-  "cpu_baseline": the oracle block (ATen CPU convs + C deformable oracle) timed on the host cores, bounded sample.
+  "cpu_baseline": the oracle block (ATen CPU convs + C deformable oracle) timed on the host cores, bounded sample
+  "other_dtype", "tblock", "lka_modules", "lka2d", "fullnet": the companion metrics (`--extras` adds more and implies `--full`).
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (float32), see dump_outputs().
 """
 import argparse
 import json
@@ -40,7 +46,11 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--reps", type=int, default=3, help="repetitions of the timed K-step region; the median is reported")
+    ap.add_argument("--full", action="store_true", help="also run everything besides the headline: repeated timed regions, roofline, CPU baseline, "
+                    "the other dtype and the companion metrics (several minutes)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed to DIR/<name>.npy (float32, < 64 MB in all)")
+    ap.add_argument("--reps", type=int, default=None, help="repetitions of the timed K-step region; the median is reported "
+                    "(default: 1, or 3 with --full)")
     ap.add_argument("--batch", type=int, default=2, help="volumes per GPU (BASELINE.json: b2)")
     ap.add_argument("--dtype", default="f32", choices=["f32", "bf16"])
     ap.add_argument("--no-graph", action="store_true", help="do not capture the step in a hipGraph")
@@ -53,7 +63,12 @@ def parse():
     ap.add_argument("--no-fullnet", action="store_true", help="skip the full-net trainer iteration (SURVEY section 8d metric iii; 5 timed iterations, ~10 s incl. building the net)")
     ap.add_argument("--no-lka2d", action="store_true", help="skip the 2-D block metric (BASELINE.json config 2: bf16, batch 24; ~0.15 s of GPU time)")
     ap.add_argument("--cpu-sample", default="stage", choices=["stage", "tiny"])
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.extras:   # the extras are reported beside everything --full reports
+        args.full = True
+    if args.reps is None:
+        args.reps = 3 if args.full else 1
+    return args
 
 
 # ----------------------------------------------------------------------------------------------------------------
@@ -324,6 +339,49 @@ def step_work(batch, dbytes):
         fl += n * 3 * fwd
         by += n * (43 * E * dbytes + 5 * Off * 4)
     return fl, by
+
+
+DUMP_BUDGET_BYTES = 60_000_000   # --dump-outputs writes at most this much (float32)
+DUMP_FLAT_SAMPLE = 1 << 20       # elements kept of the flat parameter / gradient buffers
+
+
+def _seeded_sample(t, k, seed):
+    """t flattened, or k of its elements at fixed positions (seeded, ascending) when it holds more."""
+    flat = t.detach().reshape(-1)
+    if flat.numel() <= k:
+        return flat
+    idx = torch.randperm(flat.numel(), generator=torch.Generator().manual_seed(seed))[:k].sort().values
+    return flat[idx.to(flat.device)]
+
+
+def dump_outputs(stack, out_dir):
+    """What a caller of the timed step holds after the LAST step: per chain (stage instance, execution order) the output of its last block
+    (`y`, [B, N, C]) and the gradient w.r.t. its input (`grad_x`), and the flat fp32 parameter and gradient buffers after the SGD update.  All as
+    float32.  The flat buffers are always a fixed seeded sample of DUMP_FLAT_SAMPLE elements; the activations are written whole when they fit
+    the budget, else each is a fixed seeded sample of the same fraction of its elements.  Returns {name: shape}."""
+    import numpy as np
+    acts = []
+    for k, chain in enumerate(stack.chains):
+        tag = "chain%d_C%d" % (k, chain[0].C)
+        acts.append(("y_" + tag, chain[-1].y))
+        acts.append(("grad_x_" + tag, chain[0].gx))
+    flat = [("params_sample", stack.flat_params), ("grads_sample", stack.flat_grads)]
+    room = DUMP_BUDGET_BYTES // 4 - sum(min(t.numel(), DUMP_FLAT_SAMPLE) for _, t in flat)
+    total = sum(t.numel() for _, t in acts)
+    arrays = []
+    for i, (name, t) in enumerate(acts):
+        if total <= room:
+            arrays.append((name, t.detach()))
+        else:
+            arrays.append((name + "_sample", _seeded_sample(t, max(1, t.numel() * room // total), 1000 + i)))
+    arrays += [(name, _seeded_sample(t, DUMP_FLAT_SAMPLE, 2000 + i)) for i, (name, t) in enumerate(flat)]
+    os.makedirs(out_dir, exist_ok=True)
+    shapes = {}
+    for name, t in arrays:
+        a = t.float().cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        shapes[name] = list(a.shape)
+    return shapes
 
 
 def tblock_metric(batch, steps, warmup, dev, overlap=False):
@@ -933,9 +991,9 @@ def main(harness=None):
     if world > 1:
         dist.barrier()
     sync()
-    # The timed region — EXACTLY `steps` steps between barrier + synchronize on both sides, MAX over ranks — is run `reps` times back to back (default 3:
-    # the region is 0.2 s on a pool that varies by +-2 % from box to box and by ~0.5 % from loop to loop); `value` is the MEDIAN repetition, all of them are
-    # reported (`repetitions`).
+    # The timed region — EXACTLY `steps` steps between barrier + synchronize on both sides, MAX over ranks — is run `reps` times back to back (default 1;
+    # 3 with --full: the region is 0.2 s on a pool that varies by +-2 % from box to box and by ~0.5 % from loop to loop); `value` is the MEDIAN repetition,
+    # all of them are reported (`repetitions`).
     rep_elapsed = []
     for _ in range(max(1, args.reps)):
         t0 = time.perf_counter()
@@ -957,6 +1015,8 @@ def main(harness=None):
     health = stack.health()   # finite parameters / gradients and the offset statistics of the LAST executed step
     if not health["finite"]:
         raise SystemExit(f"bench invalid: non-finite parameters or gradients after the timed steps: {health}")
+    if args.dump_outputs and rank == 0:   # before anything below runs the stack again
+        log("bench.py: outputs of the last timed step ->", args.dump_outputs, dump_outputs(stack, args.dump_outputs))
 
     if rank == 0:
         out = {
@@ -973,7 +1033,7 @@ def main(harness=None):
                        "allreduce_overlap": bool(step is step_overlapped), "allreduce_split_block": int(split),
                        "offset_std_voxels_stage0": health["offset_std"][0], "offset_std_voxels_by_stage": health["offset_std"]},
         }
-        if not args.no_roofline:
+        if args.full and not args.no_roofline:
             try:
                 out["roofline"] = roofline_report(stack, args.batch, dtype, ms_per_step)
                 fl, by = step_work(args.batch, 4 if dtype == torch.float32 else 2)
@@ -986,7 +1046,7 @@ def main(harness=None):
             except Exception as e:
                 log("roofline timing failed:", repr(e))
                 out["roofline"] = None
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             try:
                 out["cpu_baseline"] = cpu_baseline(args.cpu_sample, args.batch)
             except Exception as e:
@@ -1001,7 +1061,7 @@ def main(harness=None):
             out["config"]["bf16"] = ("bf16 STORAGE of every activation tensor (x, y, saved, intermediate gradients); fp32 parameters, offsets, "
                                      "grad_offset and accumulation; the offset-predict conv and the deformable conv's contractions (forward, Col of grad_offset / grad_input) on the "
                                      "bf16 matrix cores (v_mfma_f32_32x32x16_bf16 / 16x16x32, two-term weight records), the pointwise convs and the stored-sample weight gradient on fp32 MFMA")
-        if world == 1 and not args.no_companion:
+        if args.full and world == 1 and not args.no_companion:
             try:
                 out["other_dtype"] = companion_metric(args.batch, args.steps, args.warmup, dev, torch.bfloat16 if dtype == torch.float32 else torch.float32, lr,
                                                     roofline=not args.no_roofline)
@@ -1009,7 +1069,7 @@ def main(harness=None):
                 log("companion dtype measurement failed:", repr(e))
                 out["other_dtype"] = None
             torch.cuda.empty_cache()
-        if not args.no_tblock and world == 1 and dtype == torch.float32:
+        if args.full and not args.no_tblock and world == 1 and dtype == torch.float32:
             try:
                 # (one stream: with `wgrad_overlap` — the schedule `training.initialize_network` turns on, which `lka_modules` / `fullnet` below run with — the eager wrapper stack
                 #  measured 118.8 - 119.9 volumes/s in some processes and 108.8 - 109.3 in others on round 6's final tree (the replayed graph 119 - 120 either way): the eager
@@ -1018,22 +1078,22 @@ def main(harness=None):
             except Exception as e:
                 log("tblock metric failed:", repr(e))
                 out["tblock"] = None
-        if not args.no_tblock and world == 1 and dtype == torch.float32:
+        if args.full and not args.no_tblock and world == 1 and dtype == torch.float32:
             try:
                 out["lka_modules"] = lka_modules_metric(args.batch, max(3, args.steps // 2), 2, dev)
             except Exception as e:
                 log("lka_modules metric failed:", repr(e))
                 out["lka_modules"] = None
             torch.cuda.empty_cache()
-        if not args.no_lka2d and world == 1 and dtype == torch.float32:   # BASELINE.json config 2 AS WRITTEN (bf16, B = 24) in the DEFAULT line, so that the
-            try:                                                           # driver times it (round-3 verdict); its host companion stays in --extras
+        if args.full and not args.no_lka2d and world == 1 and dtype == torch.float32:   # BASELINE.json config 2 AS WRITTEN (bf16, B = 24) in every --full line
+            try:                                                                         # (round-3 verdict); its host companion stays in --extras
                 out["lka2d"] = lka2d_metric(5, dev, torch.bfloat16, with_cpu=False)
             except Exception as e:
                 log("lka2d metric failed:", repr(e))
                 out["lka2d"] = None
             torch.cuda.empty_cache()
-        if not args.no_fullnet and world == 1 and dtype == torch.float32:   # SURVEY section 8d metric (iii) in the DEFAULT line (round-4 verdict: the driver never
-            try:                                                             # timed the net: --extras is not in its command)
+        if args.full and not args.no_fullnet and world == 1 and dtype == torch.float32:   # SURVEY section 8d metric (iii) in every --full line, not only with
+            try:                                                                           # --extras (round-4 verdict)
                 out["fullnet"] = fullnet_metric(args.batch, 5, dev, bf16=False)
             except Exception as e:
                 log("fullnet metric failed:", repr(e))

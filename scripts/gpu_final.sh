@@ -1,13 +1,13 @@
 #!/bin/bash
-# end-of-round validation: full GPU suite, smoke, default bench (+ rocprof stats of the same command), bf16 bench, extras, per-stage block profiles
+# end-of-round validation: full GPU suite, smoke, --full bench (+ rocprof stats of the same command), bf16 bench, extras, per-stage block profiles
 set -u
 R="${GRAFT_REPO_ROOT:-/root/repo}"; cd $R
 TAG=${1:-final}; OUT=gpurun_out/$TAG; mkdir -p $OUT; export TMPDIR=/tmp
 if [ "${PROFILES_ONLY:-0}" != 1 ]; then
 echo "== pytest -m gpu"; timeout 1500 python -m pytest tests -m gpu -q > $OUT/pytest_gpu.log 2>&1; echo "exit $?"; tail -3 $OUT/pytest_gpu.log
 echo "== smoke"; timeout 600 python -c 'import __graft_entry__ as g; g.smoke()' > $OUT/smoke.log 2>&1; echo "exit $?"; tail -2 $OUT/smoke.log
-echo "== bench (default)"; timeout 900 python bench.py > $OUT/bench_f32.json 2> $OUT/bench_f32.err; echo "exit $?"
-echo "== bench --dtype bf16"; timeout 900 python bench.py --dtype bf16 --no-cpu-baseline > $OUT/bench_bf16.json 2> $OUT/bench_bf16.err; echo "exit $?"
+echo "== bench --full"; timeout 900 python bench.py --full > $OUT/bench_f32.json 2> $OUT/bench_f32.err; echo "exit $?"
+echo "== bench --dtype bf16"; timeout 900 python bench.py --full --dtype bf16 --no-cpu-baseline > $OUT/bench_bf16.json 2> $OUT/bench_bf16.err; echo "exit $?"
 echo "== bench under torch.distributed.run (1 rank, nccl), overlapped all-reduce schedule forced"
 DLKA_BENCH_FORCE_SPLIT=1 timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 1 --steps 10 --warmup 3 --no-cpu-baseline --no-tblock --no-companion --no-lka2d --no-roofline > $OUT/bench_dist1.json 2> $OUT/bench_dist1.err; echo "exit $?"; python -c "
 import json; d=json.load(open('$OUT/bench_dist1.json')); print('dist1', d['value'], d['ms_per_step'], d['config']['allreduce_overlap'], d['config']['allreduce_split_block'])"
@@ -31,7 +31,7 @@ if [ "${SKIP_PROFILES:-0}" = 1 ]; then   # (block-stack kernels unchanged since 
 fi
 cd /tmp
 echo "== rocprof of the bench command (as timed: the weight gradients of a block overlap the next block's data chain on a second stream — concurrent kernels stretch each other)"
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$OUT/prof_bench -o t -- python $R/bench.py --no-cpu-baseline --no-tblock --no-companion --no-lka2d --no-fullnet > $R/$OUT/prof_bench.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$OUT/prof_bench -o t -- python $R/bench.py --full --no-cpu-baseline --no-tblock --no-companion --no-lka2d --no-fullnet > $R/$OUT/prof_bench.log 2>&1
 F=$(find $R/$OUT/prof_bench -name "*kernel_stats.csv" | head -1); [ -n "$F" ] && cp "$F" $R/$OUT/bench_kernel_stats.csv && head -6 $R/$OUT/bench_kernel_stats.csv | cut -c1-150
 echo "== rocprof of the bench command on ONE stream (DLKA_STACK_WGRAD_OVERLAP=0): the per-kernel durations the roofline block's launch trace must agree with"
 # (no library-internal forks either, and none of the companion metrics: the nn.Module / full-net loops run the same kernels beside their own side-stream work, which would stretch the averages)

@@ -24,7 +24,7 @@ for f in sorted(glob.glob("$OUT/*_block_kernel_stats.csv")):
         n=r["Name"].replace("void dlka::","").replace("dlka::","").split("(")[0]
         print("   %-62s x%-2d %8.1f us"%(n[:62], int(r["Calls"])//22, float(r["AverageNs"])/1e3))
 PY
-echo "== bench"; timeout 900 python bench.py --no-cpu-baseline --no-tblock > $OUT/bench_f32.json 2> $OUT/bench_f32.err; echo "exit $?"; head -8 $OUT/bench_f32.err
+echo "== bench"; timeout 900 python bench.py --full --no-cpu-baseline --no-tblock > $OUT/bench_f32.json 2> $OUT/bench_f32.err; echo "exit $?"; head -8 $OUT/bench_f32.err
 python -c "
 import json; d=json.load(open('$OUT/bench_f32.json')); print(d['value'], d['ms_per_step'], d['other_dtype'])"
 find $OUT -name "*kernel_trace.csv" -delete; find $OUT -name "*.db" -delete; du -sh $OUT

@@ -59,3 +59,34 @@ def test_more_ranks_than_gpus_is_refused_before_spawning():
         pytest.skip("needs a box with fewer than 2 GPUs")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode != 0 and "GPU(s) visible" in (r.stderr + r.stdout)
+
+
+@pytest.mark.timeout(1200)
+def test_plain_run_times_exactly_steps_and_dumps_reproducible_outputs(tmp_path):
+    """`--steps K` times exactly K steps once (the extras are behind --full), and `--dump-outputs DIR` writes what the last timed step computed as float32
+    .npy files, under 64 MB in all, the same from run to run with the same arguments."""
+    import numpy as np
+    from tests import emu
+    emu.build()
+    runs = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        r = _run({}, "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "1", "--dump-outputs", str(d))
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = _json_lines(r.stdout)
+        assert len(lines) == 1, r.stdout
+        j = lines[0]
+        assert j["steps"] == 3 and j["ms_per_step"] > 0 and len(j["repetitions"]["ms_per_step"]) == 1
+        assert not {"roofline", "cpu_baseline", "other_dtype", "tblock", "lka_modules", "lka2d", "fullnet"} & set(j)
+        files = sorted(d.glob("*.npy"))
+        assert {f.name for f in files} >= {"params_sample.npy", "grads_sample.npy", "y_chain0_C32.npy", "grad_x_chain0_C32.npy"}
+        assert sum(f.stat().st_size for f in files) <= 64 * 2 ** 20
+        arrs = {f.name: np.load(f) for f in files}
+        for name, a in arrs.items():
+            assert a.dtype == np.float32 and a.size and np.isfinite(a).all(), name
+        runs.append(arrs)
+    assert runs[0].keys() == runs[1].keys()
+    for name, a in runs[0].items():
+        b = runs[1][name]
+        assert a.shape == b.shape, name
+        np.testing.assert_allclose(b, a, rtol=1e-5, atol=1e-5 * float(np.abs(a).max()), err_msg=name)
