@@ -19,6 +19,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "_lib", "libdlka_hip.so")
 
 DLKA_F32, DLKA_BF16, DLKA_F64 = 0, 1, 2
+DLKA_TILES_MAX_T, DLKA_TILES_K_MAX = 64, 32                            # include/dlka.h: dlka_tiles_*
+DLKA_TILES_IDENTITY, DLKA_TILES_SOFTMAX, DLKA_TILES_SIGMOID = 0, 1, 2
 LKA3D_SYNAPSE, LKA3D_ACDC = 0, 1   # dlka_lka3d_variant (include/dlka.h)
 
 
@@ -175,6 +177,11 @@ SIGNATURES = {
                                          POINTER(TBlock3dPtrs), POINTER(Lka3dPtrs), c_void_p, c_size_t] + [c_int] * 7 + [c_void_p]),
     "dlka_tblock3d_backward_phase_v": (c_int, [POINTER(TBlock3dPtrs), POINTER(Lka3dPtrs), c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p,
                                          POINTER(TBlock3dPtrs), POINTER(Lka3dPtrs), c_void_p, c_size_t] + [c_int] * 8 + [c_void_p]),
+    "dlka_tiles_gather": (c_int, [c_void_p] + [c_int] * 4 + [POINTER(c_int), c_int, POINTER(c_int)] + [c_int] * 7 + [ctypes.c_float, c_void_p, c_void_p]),
+    "dlka_tiles_blend": (c_int, [c_void_p, c_int, c_int, c_int, ctypes.c_float] + [c_void_p] * 3 + [c_int] * 3
+                         + [POINTER(c_int), c_int, POINTER(c_int)] + [c_int] * 4 + [c_void_p]),
+    "dlka_tiles_finalize": (c_int, [c_void_p] * 2 + [c_int] * 10 + [c_void_p] * 3),
+    "dlka_tiles_launch_count": (ctypes.c_long, []),
     "dlka_trace_start": (c_int, [c_int, c_void_p]),
     "dlka_trace_mark": (c_int, [c_void_p]),
     "dlka_trace_stop": (c_int, []),

@@ -355,9 +355,16 @@ class D_LKA_FormerUpBlock(nn.Module):
         return _chain(blk, out) if isinstance(blk, nn.Sequential) else blk(out)
 
 
+def _identity(x):
+    return x
+
+
 class D_LKA_Former(nn.Module):
-    """d_lka_former_synapse.py:8-167 (``SegmentationNetwork`` there is nnU-Net's inference base class; the sliding-window predictor
-    lives in ``deformablelka_amd.inference``)."""
+    """d_lka_former_synapse.py:8-167 (``SegmentationNetwork`` there is nnU-Net's inference base class: its ``predict_3D`` is restated
+    below, the sliding-window machinery lives in ``deformablelka_amd.inference``)."""
+
+    # SegmentationNetwork.__init__ (neural_network.py): identity until the trainer sets softmax (training.initialize_network)
+    inference_apply_nonlin = staticmethod(_identity)
 
     def __init__(self, in_channels: int, out_channels: int, img_size: Sequence[int] = (64, 128, 128), feature_size: int = 16,
                  hidden_size: int = 256, num_heads: int = 4, pos_embed: str = "perceptron", norm_name: Union[Tuple, str] = "instance",
@@ -373,6 +380,7 @@ class D_LKA_Former(nn.Module):
         if pos_embed not in ("conv", "perceptron"):
             raise KeyError(f"Position embedding layer of type {pos_embed} is not supported.")
         self.patch_size = tuple(patch_size)
+        self.img_size = tuple(int(v) for v in img_size)
         self.feat_size = tuple(img_size[i] // self.patch_size[i] // 8 for i in range(3))
         self.hidden_size = hidden_size
         tok = [int(np.prod([img_size[a] // self.patch_size[a] // (2 ** s) for a in range(3)])) for s in range(4)]   # 32^3, 16^3, 8^3, 4^3 for Synapse
@@ -409,6 +417,68 @@ class D_LKA_Former(nn.Module):
         if self.do_ds:
             return [self.out1(out), self.out2(dec1), self.out3(dec2)]
         return self.out1(out)
+
+    def predict_3D(self, x, do_mirroring: bool, mirror_axes: Tuple[int, ...] = (0, 1, 2), use_sliding_window: bool = False,
+                   step_size: float = 0.5, patch_size: Tuple[int, ...] = None, regions_class_order: Tuple[int, ...] = None,
+                   use_gaussian: bool = False, pad_border_mode: str = "constant", pad_kwargs: dict = None, all_in_gpu: bool = False,
+                   verbose: bool = True, mixed_precision: bool = True) -> Tuple[np.ndarray, np.ndarray]:
+        """nnU-Net's ``SegmentationNetwork.predict_3D`` (3D/d_lka_former/network_architecture/neural_network.py:73-166) with its 3-D
+        branches ``_internal_predict_3D_3Dconv_tiled`` (:292-428), ``_internal_predict_3D_3Dconv`` (:462-500) and test-time mirroring
+        ``_internal_maybe_mirror_and_pred_3D`` (:502-560): same signature, defaults and checks, returns (segmentation, class
+        probabilities) as numpy arrays.  ``x``: numpy array or tensor (c, x, y, z); it runs where the net's parameters live (on the GPU
+        through the HIP tile kernels, deformablelka_amd.inference).  Deep supervision: the prediction comes from the first head.
+
+        Deviations from the reference:
+          * ``mixed_precision=True`` is **bf16** autocast (the net's tested mixed mode); the reference autocasts to fp16;
+          * ``all_in_gpu`` is accepted, but accumulation is always fp32 and resident on the device (the reference's ``all_in_gpu``
+            accumulates in fp16);
+          * only ``pad_border_mode="constant"`` (value ``pad_kwargs['constant_values']``, default 0); other modes raise
+            NotImplementedError;
+          * ``use_sliding_window=False`` pads to the patch (default: the net's ``img_size``) and needs the padded shape to BE ``img_size``
+            (the token counts of this net are fixed by it): ValueError otherwise."""
+        from . import inference
+        assert step_size <= 1, 'step_size must be smaller than 1. Otherwise there will be a gap between consecutive predictions'
+        if verbose:
+            print("debug: mirroring", do_mirroring, "mirror_axes", mirror_axes)
+        if pad_border_mode != "constant":
+            raise NotImplementedError(f"pad_border_mode={pad_border_mode!r}: only 'constant' padding is implemented")
+        pad_value = float((pad_kwargs or {}).get("constant_values", 0))
+        if len(mirror_axes) and max(mirror_axes) > 2:
+            raise ValueError("mirror axes. duh")
+        if self.training:
+            print('WARNING! Network is in train mode during inference. This may be intended, or not...')
+        assert len(x.shape) == 4, "data must have shape (c,x,y,z)"
+        dev = next(self.parameters()).device
+        xt = torch.from_numpy(np.ascontiguousarray(x)) if isinstance(x, np.ndarray) else x
+        xt = xt.to(device=dev, dtype=torch.float32)
+        axes = tuple(mirror_axes) if do_mirroring else ()
+        with torch.no_grad(), torch.autocast(dev.type, dtype=torch.bfloat16, enabled=bool(mixed_precision)):
+            if use_sliding_window:
+                assert patch_size is not None, "patch_size cannot be None for tiled prediction"
+                if verbose:
+                    print("step_size:", step_size)
+                    print("do mirror:", do_mirroring)
+                tile, step, gauss = tuple(patch_size), step_size, use_gaussian
+            else:
+                tile = tuple(patch_size) if patch_size is not None else self.img_size
+                padded = tuple(max(n, p) for n, p in zip(xt.shape[1:], tile))
+                if padded != self.img_size:
+                    raise ValueError(f"fully convolutional prediction: the input {tuple(xt.shape[1:])} padded to {padded}, but this net only "
+                                     f"takes img_size {self.img_size}; use use_sliding_window=True")
+                tile, step, gauss = self.img_size, 1.0, False
+            # mirror_axes=() is the reference's do_mirroring=False: one forward per tile, num_results = 1
+            seg, probs = inference.predict_3d_tiled(self, xt, tile, step, gauss, nonlin=self.inference_apply_nonlin, tile_batch=2,
+                                                    do_mirroring=True, mirror_axes=axes, pad_value=pad_value)
+        probs = probs.float().cpu().numpy()
+        if regions_class_order is None:
+            seg = seg.cpu().numpy()
+        else:
+            seg = np.zeros(probs.shape[1:], dtype=np.float32)
+            for i, c in enumerate(regions_class_order):
+                seg[probs[i] > 0.5] = c
+        if verbose:
+            print("prediction done")
+        return seg, probs
 
     def dlka_blocks(self):
         """The 21 D-LKA transformer blocks, in forward order."""

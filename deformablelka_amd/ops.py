@@ -912,3 +912,60 @@ def ndhwc_to_ncdhw(x):
     out = torch.empty((B, C, *x.shape[1:-1]), dtype=x.dtype, device=x.device)
     L.check(L.get_lib().dlka_ndhwc_to_ncdhw(L.ptr(x), L.ptr(out), B, C, x.numel() // (B * C), L.dtype_code(x), L.stream_ptr(x)), "ndhwc_to_ncdhw")
     return out
+
+
+# ---- sliding-window prediction with test-time mirroring (include/dlka.h: dlka_tiles_*) ---------------------------------------------------
+def _int_array(vals):
+    vals = [int(v) for v in vals]
+    return (ctypes.c_int * max(len(vals), 1))(*vals)
+
+
+def tiles_gather(x, origins, masks, patch, pad_lo, pad_value=0.0):
+    """x (C, X, Y, Z) fp32, unpadded; origins [(x, y, z)] in padded coordinates; masks: mirror masks (bit 0 = x, 1 = y, 2 = z).
+    Returns the network input [T*M, C, pd, ph, pw] (b = t*M + m) = torch.flip of the constant-padded slice."""
+    L.require_device(x)
+    if x.dtype != torch.float32 or x.ndim != 4:
+        raise RuntimeError(f"tiles_gather: x must be a (C, X, Y, Z) float32 tensor, got {tuple(x.shape)} {x.dtype}")
+    x = x.contiguous()
+    T, M = len(origins), len(masks)
+    pd, ph, pw = (int(v) for v in patch)
+    out = torch.empty((T * M, x.shape[0], pd, ph, pw), dtype=torch.float32, device=x.device)
+    L.check(L.get_lib().dlka_tiles_gather(L.ptr(x), *x.shape, _int_array(v for o in origins for v in o), T, _int_array(masks), M, pd, ph, pw,
+                                          *(int(v) for v in pad_lo), float(pad_value), L.ptr(out), L.stream_ptr(x)), "tiles_gather")
+    return out
+
+
+def tiles_blend(logits, nonlin: int, mirror_scale: float, gauss, score, weight, origins, masks):
+    """score [K, X', Y', Z'] / weight [X', Y', Z'] (fp32, in place) += the chunk's blended prediction; logits [T*M, K, pd, ph, pw] fp32 or bf16;
+    nonlin: L.DLKA_TILES_*; gauss [pd, ph, pw] fp32 or None."""
+    L.require_device(logits, gauss, score, weight)
+    if score.dtype != torch.float32 or weight.dtype != torch.float32 or not score.is_contiguous() or not weight.is_contiguous():
+        raise RuntimeError("tiles_blend: score and weight must be contiguous float32 tensors (updated in place)")
+    logits = logits.contiguous()
+    T, M = len(origins), len(masks)
+    K = logits.shape[1]
+    if logits.ndim != 5 or logits.shape[0] != T * M or score.shape != (K,) + tuple(weight.shape):
+        raise RuntimeError(f"tiles_blend: logits {tuple(logits.shape)} / score {tuple(score.shape)} / weight {tuple(weight.shape)} do not fit T={T}, M={M}")
+    if gauss is not None:
+        gauss = gauss.contiguous().float()
+        if tuple(gauss.shape) != tuple(logits.shape[2:]):
+            raise RuntimeError(f"tiles_blend: importance map {tuple(gauss.shape)} is not the patch {tuple(logits.shape[2:])}")
+    L.check(L.get_lib().dlka_tiles_blend(L.ptr(logits), L.dtype_code(logits), K, int(nonlin), float(mirror_scale), L.ptr(gauss), L.ptr(score),
+                                         L.ptr(weight), *weight.shape, _int_array(v for o in origins for v in o), T, _int_array(masks), M,
+                                         *logits.shape[2:], L.stream_ptr(logits)), "tiles_blend")
+
+
+def tiles_finalize(score, weight, pad_lo, shape):
+    """The kept region [pad_lo, pad_lo + shape): (seg (X, Y, Z) int64 = argmax, probs (K, X, Y, Z) fp32 = score / weight)."""
+    L.require_device(score, weight)
+    score, weight = score.contiguous(), weight.contiguous()
+    K = score.shape[0]
+    probs = torch.empty((K,) + tuple(shape), dtype=torch.float32, device=score.device)
+    seg = torch.empty(tuple(shape), dtype=torch.int64, device=score.device)
+    L.check(L.get_lib().dlka_tiles_finalize(L.ptr(score), L.ptr(weight), K, *weight.shape, *(int(v) for v in pad_lo), *(int(v) for v in shape),
+                                            L.ptr(probs), L.ptr(seg), L.stream_ptr(score)), "tiles_finalize")
+    return seg, probs
+
+
+def tiles_launch_count() -> int:
+    return int(L.get_lib().dlka_tiles_launch_count())

@@ -10,6 +10,7 @@ from typing import Callable, Sequence
 import torch
 import torch.nn as nn
 
+from . import inference
 from .network import D_LKA_Former
 from .transformerblock import TransformerBlock_3D_single_deform_LKA
 
@@ -25,7 +26,7 @@ def initialize_network(input_channels: int = 1, num_classes: int = 14, crop_size
                        dims=[32, 64, 128, 256], do_ds=True, trans_block=trans_block, skip_connections=list(skip_connections), patch_size=patch_size)
     if device is not None:
         net = net.to(device)
-    net.inference_apply_nonlin = lambda x: torch.softmax(x, 1)
+    net.inference_apply_nonlin = inference.softmax_helper   # the HIP tile blend fuses it (inference.predict_3d_tiled)
     set_wgrad_overlap(net, wgrad_overlap)
     return net
 

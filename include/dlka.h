@@ -552,6 +552,51 @@ int dlka_tblock3d_backward_phase_v(const dlka_tblock3d_params *p, const dlka_lka
                                    int variant, int phase, void *stream);
 
 /* =======================================================================================
+ * Sliding-window prediction with test-time mirroring — csrc/cl_tiles.hip
+ * =======================================================================================
+ * nnU-Net's SegmentationNetwork._internal_predict_3D_3Dconv_tiled (3D/d_lka_former/network_architecture/neural_network.py:292-428)
+ * with _internal_maybe_mirror_and_pred_3D (:502-560): per tile the patch and its flips go through the net, the nonlinearity's
+ * outputs are flipped back and averaged, multiplied by the Gaussian importance map and added into the score map.  Here a CHUNK of
+ * T tiles and its M mirrors is one network batch [T*M] (tile-major: b = t*M + m), produced by dlka_tiles_gather and consumed by
+ * dlka_tiles_blend; dlka_tiles_finalize runs once at the end.
+ *
+ *   origins  HOST int[T][3]: the tiles' low corners (x, y, z) in PADDED coordinates, in the reference's step order (:374-380)
+ *   masks    HOST int[M]: mirror masks, bit 0 = flip x, bit 1 = flip y, bit 2 = flip z, in the order the reference visits them
+ *            (m = 0..7 at :526-557 is the mask {0, z, y, yz, x, xz, xy, xyz} filtered by mirror_axes)
+ *   patch    pd x ph x pw; volumes x (C, X, Y, Z), score map [K][Xp][Yp][Zp] fp32, weight map [Xp][Yp][Zp] fp32, contiguous
+ *
+ * Addition order (dlka_tiles_blend; bitwise that of the reference's sequential loops, :403-415 and :526-559):
+ *   for each voxel, for t = 0 .. T-1 among the tiles covering it:
+ *       r_k  = 0;  for m in masks order: r_k = r_k + mirror_scale * nonlin(logits)[t*M + m][k][flip_m(voxel - origin_t)]
+ *       r_k  = r_k * g[voxel - origin_t]          (g = 1 without importance map)
+ *       score_k = score_k + r_k;  weight = weight + g
+ * Every product and sum is rounded on its own (no FMA contraction); no atomics: two calls give identical bits.  mirror_scale is
+ * 1 / 2^len(mirror_axes) (:517-518).  Return codes: DLKA_ERR_NULL, DLKA_ERR_SHAPE (non-positive size; a tile outside the score map;
+ * a kept region outside it), DLKA_ERR_UNSUPPORTED (T > DLKA_TILES_MAX_T, M > 8, a mask outside 0..7, K > DLKA_TILES_K_MAX or an
+ * unknown nonlinearity: nothing is launched), DLKA_ERR_DTYPE. */
+#define DLKA_TILES_MAX_T 64      /* tiles per chunk */
+#define DLKA_TILES_K_MAX 32      /* classes the blend keeps in registers (Synapse 14, ACDC 4) */
+#define DLKA_TILES_IDENTITY 0    /* nonlinearity codes of dlka_tiles_blend: inference_apply_nonlin = identity (neural_network.py SegmentationNetwork default) */
+#define DLKA_TILES_SOFTMAX 1     /*   softmax over the K classes (softmax_helper, d_lka_former_trainer_synapse.py:185) */
+#define DLKA_TILES_SIGMOID 2     /*   elementwise sigmoid */
+/* out [T*M][C][pd][ph][pw] fp32 = torch.flip(pad(x)[:, o:o+p], flipped axes of mask m) for b = t*M + m.  x is the UNPADDED volume
+ * (C, X, Y, Z); pad_x/y/z = the low-side constant padding of pad_nd_image(..., 'constant') (d // 2); a read outside x gives
+ * pad_value (pad_kwargs['constant_values']).  A pure copy (bitwise). */
+int dlka_tiles_gather(const float *x, int C, int X, int Y, int Z, const int *origins, int T, const int *masks, int M, int pd, int ph,
+                      int pw, int pad_x, int pad_y, int pad_z, float pad_value, float *out, void *stream);
+/* score / weight += the chunk's blended prediction (order above).  logits [T*M][K][pd][ph][pw], dtype DLKA_F32 or DLKA_BF16 (the net
+ * under bf16 autocast; arithmetic fp32); nonlin DLKA_TILES_*; gauss [pd][ph][pw] fp32 or NULL. */
+int dlka_tiles_blend(const void *logits, int dtype, int K, int nonlin, float mirror_scale, const float *gauss, float *score,
+                     float *weight, int Xp, int Yp, int Zp, const int *origins, int T, const int *masks, int M, int pd, int ph, int pw,
+                     void *stream);
+/* The kept region [pad, pad + (X, Y, Z)) (:420-428): probs [K][X][Y][Z] fp32 = score / weight, seg [X][Y][Z] int64 = the index of the
+ * first maximum over K (torch.argmax: a NaN counts as the maximum). */
+int dlka_tiles_finalize(const float *score, const float *weight, int K, int Xp, int Yp, int Zp, int pad_x, int pad_y, int pad_z, int X,
+                        int Y, int Z, float *probs, int64_t *seg, void *stream);
+/* Diagnostics: launches so far (this process) of the three kernels above; the tests assert that the HIP path ran. */
+long dlka_tiles_launch_count(void);
+
+/* =======================================================================================
  * Launch trace — measurement aid (no reference counterpart; the reference has no profiling hooks)
  * =======================================================================================
  * Between dlka_trace_start and dlka_trace_stop every kernel launch of the library is followed by a HIP timing event on the

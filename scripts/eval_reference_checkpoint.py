@@ -10,7 +10,8 @@ never produced this number: VERDICT r5, missing #6).
   against the reference class);
 * the cases: `<id>.npz` as nnU-Net's preprocessing writes them (`data`: [channels + 1, D, H, W], last channel = the label map, -1 = outside) or pairs
   `<id>_img.npy` ([C, D, H, W] or [D, H, W]) / `<id>_seg.npy`;
-* inference: the reference's sliding window (`predict_3D` with Gaussian importance weighting, step 0.5: deformablelka_amd.inference.predict_3d_tiled, SURVEY §8 row f4) on the HIP kernels;
+* inference: the reference's validation protocol — `predict_3D` with sliding window, Gaussian importance weighting, step 0.5 and test-time mirroring along all
+  three axes (D_LKA_Former.predict_3D, the HIP tile kernels; --no-mirroring for one forward per tile);
 * metric: Dice per foreground class over the classes present in either map, and their mean per case and over cases (Synapse: 13 organs; the paper's table averages 8 of them —
   pass --classes 1 2 3 4 6 7 8 11 for that subset, evaluate_synapse-style).
 No reference number is hard-coded here: compare the output with the paper's table."""
@@ -64,14 +65,14 @@ def main():
     ap.add_argument("--patch", type=int, nargs=3, default=[64, 128, 128])
     ap.add_argument("--stem", type=int, nargs=3, default=[2, 4, 4], help="patch-embedding stride of the net (Synapse (2,4,4); ACDC (1,4,4); pancreas (2,2,2))")
     ap.add_argument("--step", type=float, default=0.5)
-    ap.add_argument("--tile-batch", type=int, default=2)
     ap.add_argument("--classes", type=int, nargs="*", default=None, help="foreground classes to score (default: 1 .. num_classes - 1)")
     ap.add_argument("--bf16", action="store_true", help="run the D-LKA blocks on bf16 activations (torch.autocast)")
+    ap.add_argument("--no-mirroring", action="store_true", help="predict without test-time mirroring (the paper's protocol mirrors)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("needs the MI355X: the product has no CPU path")
-    from deformablelka_amd import inference, training
+    from deformablelka_amd import training
     dev = torch.device("cuda", 0)
     net = training.initialize_network(1, args.num_classes, tuple(args.patch), device=dev, patch_size=tuple(args.stem), wgrad_overlap=False)
     sd = load_reference_state_dict(args.checkpoint)
@@ -86,16 +87,15 @@ def main():
     per_case = {}
     for f in files:
         img, seg = load_case(f)
-        x = torch.from_numpy(img).to(dev)
-        with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16, enabled=args.bf16):
-            pred, _ = inference.predict_3d_tiled(net, x, tuple(args.patch), step_size=args.step, tile_batch=args.tile_batch)
-        d = dice_per_class(pred.cpu().numpy(), np.where(seg < 0, 0, seg), classes)
+        pred, _ = net.predict_3D(img, not args.no_mirroring, mirror_axes=(0, 1, 2), use_sliding_window=True, step_size=args.step,
+                                 patch_size=tuple(args.patch), use_gaussian=True, verbose=False, mixed_precision=args.bf16)
+        d = dice_per_class(pred, np.where(seg < 0, 0, seg), classes)
         per_case[os.path.basename(f)] = {"dice": d, "mean": float(np.mean(list(d.values()))) if d else None}
         print(os.path.basename(f), per_case[os.path.basename(f)]["mean"], flush=True)
     means = [v["mean"] for v in per_case.values() if v["mean"] is not None]
     by_class = {c: float(np.mean([v["dice"][c] for v in per_case.values() if c in v["dice"]])) for c in classes if any(c in v["dice"] for v in per_case.values())}
     res = {"checkpoint": args.checkpoint, "cases": len(files), "mean_dsc": float(np.mean(means)) if means else None, "dsc_by_class": by_class, "per_case": per_case,
-           "activations": "bf16" if args.bf16 else "fp32", "patch": args.patch, "step": args.step}
+           "activations": "bf16" if args.bf16 else "fp32", "patch": args.patch, "step": args.step, "mirroring": not args.no_mirroring}
     print(json.dumps({k: v for k, v in res.items() if k != "per_case"}))
     if args.out:
         json.dump(res, open(args.out, "w"), indent=1)
