@@ -1,0 +1,270 @@
+// =========================================================================================================================
+// The 2-D D-LKA block (deformable_LKA_Attention, 2D/deformable_LKA/deformable_LKA.py:124-140) on the channels-last kernels.
+// x / y arrive in the reference's NCHW layout; the block transposes once on the way in and once on the way out (two passes of E
+// floats against ~100 E of work) and runs entirely in [B][H][W][C]:
+//   1x1 projections (+GELU / gate / residual epilogues)      cl_pointwise_kernel
+//   offset nets C -> 50 (5x5) and C -> 98 (7x7 dil 3)        cl_igemm_kernel (3-D kernel with D = kd = 1), planar offsets as torchvision wants them;
+//                                                            split-bf16 MFMA as in the 3-D block (forward fp32-equivalent three-term)
+//   the two depthwise deformable convs                       cl_ddw2d.hip
+// Supported: fp32, C / 32 in {1, 2, 3, 4, 6, 8, 12} (the net's 96 / 192 / 384 / 768 -> the first three; 768 never runs).
+// =========================================================================================================================
+#include "cl_fork.h"
+
+using namespace dlka;
+
+namespace dlka {
+
+namespace {
+
+SameConv block_conv2d(int B, int C, int Cout, int H, int W, int k, int pad, int dil, int act_bf16 = 0)
+{
+    SameConv s;
+    s.act_bf16 = act_bf16;
+    s.B = B; s.D = 1; s.H = H; s.W = W; s.N = H * W; s.M = B * s.N; s.Cin = C; s.Cout = Cout; s.group = 1;
+    s.kd = 1; s.kh = s.kw = k; s.pd = 0; s.ph = s.pw = pad; s.dd = 1; s.dh = s.dw = dil; s.K = k * k;
+    return s;
+}
+
+// DLKA_BF16 (BASELINE.json config 2: "224x224 bf16 training, batch 24") is MIXED precision, like the 3-D block (TokGeoms): bf16 storage for x, y,
+// every saved activation and the intermediate gradients — except the chain that decides WHERE the two deformable convs sample:
+//     a = GELU(proj_1 x)  ->  o5 = offnet5(a)  ->  t1 = DDW5(a, o5)  ->  o7 = offnet7(t1)
+// runs on fp32 tensors (a32, t1_32: forward-only workspace) with the fp32 path's own kernels, so that both offset fields equal the fp32 block's to
+// fp32 rounding.  The bf16 copies of a / t1 (saved for the backward pass) ride in the producing kernels.
+struct Lka2dCl {
+    SameConv pw, off5, off7;      // activation-typed (bf16 on DLKA_BF16): the pointwise convs, the offset nets' backward passes
+    SameConv off5_f, off7_f;      // the offset nets' FORWARD passes: fp32 input on both paths
+    size_t E, O5, O7, SB;
+    int B, C, H, W, bf;
+    Lka2dCl(int B_, int C_, int H_, int W_, int dtype = DLKA_F32) : B(B_), C(C_), H(H_), W(W_)
+    {
+        bf = dtype == DLKA_BF16 ? 1 : 0;
+        SB = bf ? 2 : 4;
+        pw = block_conv2d(B, C, C, H, W, 1, 0, 1, bf);
+        off5 = block_conv2d(B, C, 50, H, W, 5, 2, 1, bf);
+        off7 = block_conv2d(B, C, 98, H, W, 7, 9, 3, bf);
+        off5_f = block_conv2d(B, C, 50, H, W, 5, 2, 1, 0);
+        off7_f = block_conv2d(B, C, 98, H, W, 7, 9, 3, 0);
+        E = (size_t)B * C * H * W; O5 = (size_t)B * 50 * H * W; O7 = (size_t)B * 98 * H * W;
+    }
+    size_t pw_floats() const { return (size_t)C * C; }
+    size_t off5_floats() const { return dense_wp_floats(off5); }
+    size_t off7_floats() const { return dense_wp_floats(off7); }
+    size_t prep_floats() const { return 6 * (pw_floats() + 64) + 2 * (off5_floats() + 64) + 2 * (off7_floats() + 64) + (size_t)(25 + 49) * C + 256; }
+    size_t part_pw() const { return (cl_wgrad_part_floats_mode(pw.M, 1, C, C, 0) + 63) & ~(size_t)63; }
+    size_t part_o5() const { return (cl_wgrad_part_floats_mode(pw.M, 25, 50, C, 0) + 63) & ~(size_t)63; }
+    size_t part_o7() const { return (cl_wgrad_part_floats_mode(pw.M, 49, 98, C, 0) + 63) & ~(size_t)63; }
+    size_t part_dw() const { return (cl_ddw2d_part_floats(pw.M, 49, C) + 63) & ~(size_t)63; }
+    size_t part_floats() const { return 3 * part_pw() + part_o5() + part_o7() + part_dw(); }
+};
+
+struct Prep2d { float *pw_f[3], *pw_b[3], *o5_f, *o5_b, *o7_f, *o7_b, *dw5, *dw7; };
+
+int carve_prep2d(const Lka2dCl &G, float *base, Prep2d &t, const dlka_lka2d_params *p, hipStream_t st, bool fill)
+{
+    float *q = base;
+    auto take = [&](size_t n) { float *r = q; q += (n + 63) & ~(size_t)63; return r; };
+    for (int k = 0; k < 3; ++k) { t.pw_f[k] = take(G.pw_floats()); t.pw_b[k] = take(G.pw_floats()); }
+    t.o5_f = take(G.off5_floats()); t.o5_b = take(G.off5_floats());
+    t.o7_f = take(G.off7_floats()); t.o7_b = take(G.off7_floats());
+    t.dw5 = take((size_t)25 * G.C); t.dw7 = take((size_t)49 * G.C);
+    if (!fill) return DLKA_OK;
+    PrepBatch pb;
+    memset(&pb, 0, sizeof(pb));
+    const int C = G.C;
+    const void *pw_w[3] = {p->proj_1_w, p->conv1_w, p->proj_2_w};
+    for (int k = 0; k < 3; ++k) {
+        add_job(pb, pw_w[k], t.pw_f[k], C, C, 1, C, C, 0);
+        add_job(pb, pw_w[k], t.pw_b[k], C, C, 1, C, C, 1);
+    }
+    add_job(pb, p->conv0_offset_w, t.o5_f, 50, C, 25, C, 64, split_mode_flag(use_split(G.off5_f, true)));
+    add_job(pb, p->conv0_offset_w, t.o5_b, 50, C, 25, 64, C, use_split(G.off5, false) ? 9 : 1);
+    add_job(pb, p->conv_spatial_offset_w, t.o7_f, 98, C, 49, C, 128, split_mode_flag(use_split(G.off7_f, true)));
+    add_job(pb, p->conv_spatial_offset_w, t.o7_b, 98, C, 49, 128, C, use_split(G.off7, false) ? 9 : 1);
+    add_job(pb, p->conv0_w, t.dw5, C, C, 25, 0, 0, 3);
+    add_job(pb, p->conv_spatial_w, t.dw7, C, C, 49, 0, 0, 3);
+    return launch_cl_prep_batch(pb, st);
+}
+
+void fill_ddw(DwArgs2d &d, const Lka2dCl &G, int k, int pad, int dil)
+{
+    memset(&d, 0, sizeof(d));
+    d.B = G.B; d.H = G.H; d.W = G.W; d.C = G.C; d.kh = d.kw = k; d.ph = d.pw = pad; d.dh = d.dw = dil;
+}
+
+}  // namespace
+
+int lka2d_cl_supported(int B, int C, int H, int W, int dtype)
+{
+    if ((dtype != DLKA_F32 && dtype != DLKA_BF16) || B <= 0 || H <= 0 || W <= 0 || !cl_ddw2d_supported(C)) return 0;
+    if (!(nt_ok(C) || C == 192 || C == 384)) return 0;   // the offset nets' data gradient has C columns: the igemm launcher's tile menu
+    if ((long)B * H * W * C >= (1l << 29)) return 0;
+    return dense_fwd_supported(block_conv2d(B, C, 50, H, W, 5, 2, 1)) ? 1 : 0;
+}
+
+// saved: xt, h, a, t1, t2, g1, m, (spare) — activation-typed —, o5, o7 (fp32), prepared weights
+size_t lka2d_cl_saved_bytes(int B, int C, int H, int W, int dtype)
+{
+    Lka2dCl G(B, C, H, W, dtype);
+    return 8 * align256(G.E * G.SB) + align256(G.O5 * 4) + align256(G.O7 * 4) + align256(G.prep_floats() * 4);
+}
+
+// (the nine gradient buffers keep their fp32 size on the bf16 path: the two grad_input accumulators ARE fp32, two more serve as the forward
+//  pass's fp32 chain tensors and as landing zones of tap-split sums)
+// (diagnostics) the offset tensors inside `saved`: lka2d_cl_forward carves xt, h, a, t1, t2, g1, m, spare, then o5, o7 (fp32 on both paths)
+int lka2d_cl_saved_offsets(int B, int C, int H, int W, int dtype, size_t byte_offsets[2], int *elem_bytes)
+{
+    Lka2dCl G(B, C, H, W, dtype);
+    byte_offsets[0] = 8 * align256(G.E * G.SB);
+    byte_offsets[1] = byte_offsets[0] + align256(G.O5 * 4);
+    *elem_bytes = 4;
+    return DLKA_OK;
+}
+
+size_t lka2d_cl_workspace_bytes(int B, int C, int H, int W, int dtype)
+{
+    Lka2dCl G(B, C, H, W, dtype);
+    return 9 * align256(G.E * 4) + align256(G.O7 * 4) + align256(G.O5 * 4) + align256(G.part_floats() * 4) + align256(4096) +   // (O5: the second conv's grad_offset, see lka2d_cl_backward)
+           dense_wgrad_pad_bytes(G.off7) + dense_wgrad_pad_bytes(G.off5);   // the zero-padded copies the offset nets' weight gradients read (round 5)
+}
+
+int lka2d_cl_forward(const void *x_, const dlka_lka2d_params *p, void *y_, void *saved, size_t saved_bytes, void *workspace, size_t workspace_bytes, int B,
+                     int C, int H, int W, int dtype, hipStream_t st)
+{
+    Lka2dCl G(B, C, H, W, dtype);
+    const size_t SB = G.SB;
+    const int bf = G.bf;
+    Carver sv(saved, saved_bytes), cv(workspace, workspace_bytes);
+    float *xt = (float *)sv.take(G.E * SB), *h = (float *)sv.take(G.E * SB), *a = (float *)sv.take(G.E * SB), *t1 = (float *)sv.take(G.E * SB);
+    float *t2 = (float *)sv.take(G.E * SB), *g1 = (float *)sv.take(G.E * SB), *m = (float *)sv.take(G.E * SB), *spare = (float *)sv.take(G.E * SB);
+    float *o5 = (float *)sv.take(G.O5 * 4), *o7 = (float *)sv.take(G.O7 * 4);
+    float *prep = (float *)sv.take(G.prep_floats() * 4);
+    float *yt = (float *)cv.take(G.E * 4);
+    float *a32 = (float *)cv.take(G.E * 4), *t1_32 = (float *)cv.take(G.E * 4);   // bf16 path: the fp32 offset-determining chain
+    (void)spare;
+    if (!sv.ok() || !cv.ok()) return DLKA_ERR_WORKSPACE;
+    const float *N0 = nullptr;
+    Prep2d PW;
+    DLKA_TRY(carve_prep2d(G, prep, PW, p, st, true));
+    DLKA_TRY(launch_cl_transpose((const float *)x_, xt, B, C, G.pw.N, 1, st, bf));                                           // NCHW -> NHWC
+    DLKA_TRY(dense_forward(G.pw, xt, N0, (const float *)p->proj_1_b, h, 0, PW.pw_f[0], 1, nullptr, a, st, false, nullptr, bf ? a32 : nullptr));   // :135-136 (+GELU)
+    const float *a_in = bf ? a32 : a;
+    DLKA_TRY(dense_forward(G.off5_f, a_in, N0, (const float *)p->conv0_offset_b, o5, 1, PW.o5_f, 0, nullptr, nullptr, st));     // :28 offset_net
+    DwArgs2d d;
+    fill_ddw(d, G, 5, 2, 1);
+    d.in = a_in; d.off = o5; d.wp = PW.dw5; d.out = bf ? t1_32 : t1; d.out_lo = bf ? t1 : nullptr;
+    DLKA_TRY(launch_cl_ddw2d_fwd(d, st));                                                                                     // :29
+    const float *t1_in = bf ? t1_32 : t1;
+    DLKA_TRY(dense_forward(G.off7_f, t1_in, N0, (const float *)p->conv_spatial_offset_b, o7, 1, PW.o7_f, 0, nullptr, nullptr, st));
+    fill_ddw(d, G, 7, 9, 3);
+    d.in = t1_in; d.off = o7; d.wp = PW.dw7; d.out = bf ? nullptr : t2; d.out_lo = bf ? t2 : nullptr;
+    DLKA_TRY(launch_cl_ddw2d_fwd(d, st));
+    DLKA_TRY(dense_forward(G.pw, t2, N0, (const float *)p->conv1_b, g1, 0, PW.pw_f[1], 2, a, m, st));                          // :102-104 conv1 + gate
+    DLKA_TRY(dense_forward(G.pw, m, N0, (const float *)p->proj_2_b, yt, 0, PW.pw_f[2], 3, xt, nullptr, st));                   // :138-139 proj_2 + shortcut
+    return launch_cl_transpose(yt, (float *)y_, B, C, G.pw.N, 0, st, bf);
+}
+
+int lka2d_cl_backward(const void *x_, const dlka_lka2d_params *p, const void *gy_, const void *saved, size_t saved_bytes, void *gx_, const dlka_lka2d_grads *gr,
+                      void *workspace, size_t workspace_bytes, int B, int C, int H, int W, int dtype, hipStream_t st)
+{
+    (void)x_;
+    Lka2dCl G(B, C, H, W, dtype);
+    const size_t SB = G.SB;
+    const int bf = G.bf;
+    Carver sv((void *)saved, saved_bytes), cv(workspace, workspace_bytes);
+    const float *xt = (float *)sv.take(G.E * SB), *h = (float *)sv.take(G.E * SB), *a = (float *)sv.take(G.E * SB), *t1 = (float *)sv.take(G.E * SB);
+    const float *t2 = (float *)sv.take(G.E * SB), *g1 = (float *)sv.take(G.E * SB), *m = (float *)sv.take(G.E * SB);
+    (void)sv.take(G.E * SB);
+    const float *o5 = (float *)sv.take(G.O5 * 4), *o7 = (float *)sv.take(G.O7 * 4);
+    float *prep = (float *)sv.take(G.prep_floats() * 4);
+    float *gyt = (float *)cv.take(G.E * 4), *gg1 = (float *)cv.take(G.E * 4), *ga1 = (float *)cv.take(G.E * 4), *gt2 = (float *)cv.take(G.E * 4);
+    float *gta = (float *)cv.take(G.E * 4), *gt1 = (float *)cv.take(G.E * 4), *gaa = (float *)cv.take(G.E * 4), *gab = (float *)cv.take(G.E * 4);
+    float *gh = (float *)cv.take(G.E * 4);
+    float *goff = (float *)cv.take(G.O7 * 4);
+    float *goff5 = (float *)cv.take(G.O5 * 4);   // the 5x5 conv's grad_offset in a buffer of its own: the 7x7 offset net's weight gradient may still be reading `goff`
+    float *part = (float *)cv.take(G.part_floats() * 4);
+    (void)cv.take(4096);
+    float *pad7 = (float *)cv.take_opt(dense_wgrad_pad_bytes(G.off7), dense_wgrad_pad_bytes(G.off7) != 0);   // (own buffers: both weight gradients may be in flight on the
+    float *pad5 = (float *)cv.take_opt(dense_wgrad_pad_bytes(G.off5), dense_wgrad_pad_bytes(G.off5) != 0);   //  internal stream at once)
+    if (!sv.ok() || !cv.ok()) return DLKA_ERR_WORKSPACE;
+    const float *N0 = nullptr;
+    Prep2d PW;
+    DLKA_TRY(carve_prep2d(G, prep, PW, p, st, false));
+    // The two offset nets' WEIGHT gradients (the largest kernels of this pass after grad_input: C -> 98 / 50 channels over 49 / 25 taps) only read grad_offset and a saved
+    // activation, and nothing before the finalisation reads their partial sums: they run on the library's internal stream (aux_ctx) beside the data chain — fork behind
+    // each depthwise deformable conv's backward, one join in front of the finalisation.  DLKA_LKA2D_FORK=0: one stream (A/B; read per call).  Measured in
+    // profiles/r06_notes.md.
+    int fork_mode = 0;
+#if !defined(HIPEMU)
+    fork_mode = fork_env().lka2d_fork;
+#endif
+    ForkLease lease(st, fork_mode != 0);   // (joins whatever is still forked when a DLKA_TRY below returns early)
+    const bool fork2d = lease.ok();
+    // ... and each depthwise deformable conv's grad_input (the pass's largest kernel) beside its grad_offset / weight-gradient kernel on a second internal stream:
+    // fork in front of the pair, join in front of the offset net's data gradient, which adds grad_input (DLKA_LKA2D_FORK=1: the weight gradients only)
+    const bool forkgx = fork2d && fork_mode == 2;
+    hipStream_t gst = forkgx ? lease.stream(2) : nullptr;
+    auto fork_gx = [&]() -> int { return forkgx ? lease.fork(2) : DLKA_OK; };
+    auto join_gx = [&]() -> int { return forkgx ? lease.join(2) : DLKA_OK; };
+    hipStream_t wst = fork2d ? lease.stream(1) : st;
+    auto fork_to_aux = [&]() -> int { return fork2d ? lease.fork(1) : DLKA_OK; };
+    float *part_p2 = part, *part_c1 = part_p2 + G.part_pw(), *part_p1 = part_c1 + G.part_pw(), *part_o5 = part_p1 + G.part_pw();
+    float *part_o7 = part_o5 + G.part_o5(), *part_dw = part_o7 + G.part_o7();
+    FinalizeBatch fb;
+    memset(&fb, 0, sizeof(fb));
+    // bf16: the fp32 landing zone of a tap-split offset-net data gradient (converted into its bf16 destination afterwards): gg1 is dead by then for
+    // the first one, gt2 for the second
+    ZeroBatch zb;
+    memset(&zb, 0, sizeof(zb));
+    zb.add(gta, G.E);   // grad_input targets of the two depthwise deformable convs (fp32 atomics)
+    zb.add(gaa, G.E);
+    const bool split7 = dense_backward_data_splits(G.off7, 3) > 1, split5 = dense_backward_data_splits(G.off5, 3) > 1;
+    if (bf && split7) zb.add(gh, G.E);     // (gh is written last: free until then)
+    if (zb.overflow) return DLKA_ERR_WORKSPACE;
+    DLKA_TRY(launch_zero_batch(zb, st));
+    float *gxt = gt2;   // (gt2 is dead by the time the last projection's data gradient is written)
+    DLKA_TRY(launch_cl_transpose((const float *)gy_, gyt, B, C, G.pw.N, 1, st, bf));
+    // proj_2 data gradient with the gate's backward in the epilogue: gg1 = gm * a, ga1 = gm * g1
+    DLKA_TRY(dense_backward_data(G.pw, gyt, 0, N0, gg1, PW.pw_b[2], 4, a, st, g1, ga1));
+    DLKA_TRY(dense_backward_data(G.pw, gg1, 0, N0, gt2, PW.pw_b[1], 0, nullptr, st));                                           // conv1
+    // conv_spatial = DeformConv(7x7 dil 3): t2 = DDW7(t1, o7 = offnet7(t1))
+    DwArgs2d d;
+    fill_ddw(d, G, 7, 9, 3);
+    d.act_bf16 = bf;
+    d.in = t1; d.off = o7; d.wp = PW.dw7; d.g = gt2; d.gx = gta; d.goff = goff; d.part = part_dw;
+    DLKA_TRY(fork_gx());
+    DLKA_TRY(launch_cl_ddw2d_bwd(d, (float *)gr->conv_spatial_w, st, gst));
+    DLKA_TRY(fork_to_aux());
+    DLKA_TRY(dense_backward_weight(G.off7, t1, goff, 1, (float *)gr->conv_spatial_offset_w, (float *)gr->conv_spatial_offset_b, part_o7, wst, &fb.j[fb.njobs++], 0, pad7));
+    DLKA_TRY(join_gx());
+    DLKA_TRY(dense_backward_data(G.off7, goff, 1, N0, gt1, PW.o7_b, 3, gta, st, nullptr, nullptr, bf && split7, false, bf != 0, bf ? gh : nullptr));   // gt1 = gta + offnet7^T goff
+    // conv0 = DeformConv(5x5): t1 = DDW5(a, o5 = offnet5(a))
+    fill_ddw(d, G, 5, 2, 1);
+    d.act_bf16 = bf;
+    d.in = a; d.off = o5; d.wp = PW.dw5; d.g = gt1; d.gx = gaa; d.goff = goff5; d.part = part_dw;
+    DLKA_TRY(fork_gx());
+    DLKA_TRY(launch_cl_ddw2d_bwd(d, (float *)gr->conv0_w, st, gst));
+    DLKA_TRY(fork_to_aux());
+    DLKA_TRY(dense_backward_weight(G.off5, a, goff5, 1, (float *)gr->conv0_offset_w, (float *)gr->conv0_offset_b, part_o5, wst, &fb.j[fb.njobs++], 0, pad5));
+    DLKA_TRY(join_gx());
+    if (bf && split5) DLKA_TRY(launch_zero(gh, G.E * 4, st));
+    DLKA_TRY(dense_backward_data(G.off5, goff5, 1, N0, gab, PW.o5_b, 3, gaa, st, nullptr, nullptr, bf && split5, false, bf != 0, bf ? gh : nullptr));   // gab = gaa + offnet5^T goff
+    // a = GELU(h) feeds the gate and conv0: gh = (ga1 + gab) * gelu'(h)
+    if (bf) DLKA_TRY(launch_gelu_bwd_sum<bf16_t>((const bf16_t *)h, (const bf16_t *)ga1, (const bf16_t *)gab, (bf16_t *)gh, (long)G.E, st));
+    else DLKA_TRY(launch_gelu_bwd_sum<float>(h, ga1, gab, gh, (long)G.E, st));
+    {
+        WgradArgs jobs[3];
+        fill_pw_wgrad(jobs[0], G.pw, m, gyt, part_p2);
+        fill_pw_wgrad(jobs[1], G.pw, t2, gg1, part_c1);
+        fill_pw_wgrad(jobs[2], G.pw, xt, gh, part_p1);
+        float *const gws[3] = {(float *)gr->proj_2_w, (float *)gr->conv1_w, (float *)gr->proj_1_w};
+        float *const gbs[3] = {(float *)gr->proj_2_b, (float *)gr->conv1_b, (float *)gr->proj_1_b};
+        DLKA_TRY(launch_cl_wgrad_pw3(jobs, gws, gbs, st, &fb.j[fb.njobs]));
+        fb.njobs += 3;
+    }
+    if (fork2d) DLKA_TRY(lease.join(1));   // the folds read the offset nets' partial sums
+    DLKA_TRY(launch_cl_wgrad_finalize(fb, st));
+    DLKA_TRY(dense_backward_data(G.pw, gh, 0, N0, gxt, PW.pw_b[0], 3, gyt, st));                                                // gx = P1^T gh + gy
+    return launch_cl_transpose(gxt, (float *)gx_, B, C, G.pw.N, 0, st, bf);
+}
+
+}  // namespace dlka

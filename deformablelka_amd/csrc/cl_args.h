@@ -40,7 +40,7 @@ struct IgemmArgs {
     float *out;          // OMODE 0: [M][Cout] channels-last; OMODE 1: [B][Cout][N] planar
     float *out2;         // second epilogue output or null
     float *out2_f32;     // act_bf16, epi 1 (pointwise kernel): ALSO store out2 = gelu(out) unrounded, fp32 [M][Cout] — the input of the fp32 chain
-                         // that decides the sampling cells (dlka_capi_cl.hip: "offset-determining chain"); null = off
+                         // that decides the sampling cells (capi_lka3d_tokens.hip: "offset-determining chain"); null = off
     int B, D, H, W, N, M;
     int Cin, CinReal, CinP, Cout, NP;
     int kd, kh, kw, pd, ph, pw, dd, dh, dw, K;

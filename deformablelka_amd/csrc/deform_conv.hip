@@ -10,7 +10,7 @@
 //
 // Kernels in this file are the GENERAL path (any kernel size / stride / pad / dilation / groups /
 // deformable groups).  The shape-specialised kernels of the D-LKA hot configuration are the channels-last ones
-// (cl_*.hip), entered through dlka_capi_cl.hip.
+// (cl_*.hip), entered through capi_*.hip.
 #include "deform_sample.h"
 #include "cl_gather.h"
 #include "cl_ddw2d_describe.h"

@@ -757,7 +757,7 @@ size_t dlka_lka2d_saved_bytes(int B, int C, int H, int W, int dtype)
     if (check_block(B, C, 1, H, W)) return 0;
     Lka2dGeoms G(B, C, H, W);
     size_t n = 5 * align256(G.E * esz(dtype)) + align256(G.Off5 * esz(dtype)) + align256(G.Off7 * esz(dtype));
-    if (lka2d_cl_supported(B, C, H, W, dtype)) n = std::max(n, lka2d_cl_saved_bytes(B, C, H, W, dtype));   // channels-last fast path (dlka_capi_cl.hip)
+    if (lka2d_cl_supported(B, C, H, W, dtype)) n = std::max(n, lka2d_cl_saved_bytes(B, C, H, W, dtype));   // channels-last fast path (capi_lka2d_cl.hip)
     return n;
 }
 

@@ -22,7 +22,7 @@ def lka3d_attention_volume(x, P, store=None, chain_store=None, offsets_override=
     (minus the token permutes), LKA3d_deform.forward :644-652, DeformConvPack.forward synapse/deform_conv.py:93-105.
     store: None = the reference's fp32 block; ``bf16_storage`` = the model of the DLKA_BF16 path: the same arithmetic with every activation
     that path writes to HBM AS bf16 rounded where it is written.  The chain that decides the sampling cells — a = GELU(proj_1 x) -> conv0 ->
-    conv_spatial -> conv_offset — stays fp32 there (deformablelka_amd/csrc/dlka_capi_cl.hip, TokGeoms), so it is not rounded here either; the
+    conv_spatial -> conv_offset — stays fp32 there (deformablelka_amd/csrc/capi_lka3d_tokens.h, TokGeoms), so it is not rounded here either; the
     gate and the deformable conv's SAMPLES read the bf16 copies of a and t.
     chain_store: rounding applied to the chain tensors a / t1 / t as the offset-determining convs READ them (None = fp32, what the product does;
     ``bf16_storage`` = the round-2 design with every activation in bf16 — kept so that tests/test_oracle_bf16_model.py can show why it was dropped).
@@ -140,7 +140,7 @@ def lka2d_attention(x, P, store=None, offsets_override=None, offsets_out=None):
     """deformable_LKA_Attention.forward — deformable_LKA.py:133-140 with deformable_LKA.forward :98-104.
     store: None = the reference's fp32 block; ``bf16_storage`` = the model of the DLKA_BF16 2-D path: every activation that path writes to HBM as
     bf16 is rounded where it is written; the chain that decides the sampling cells (a -> offset net 5 -> t1 = DDW5(a) -> offset net 7) stays fp32
-    there (dlka_capi_cl.hip, Lka2dCl) and is not rounded here either.
+    there (capi_lka2d_cl.hip, Lka2dCl) and is not rounded here either.
     offsets_override: (conv0's offsets, conv_spatial's offsets) VALUES from another implementation's forward pass (straight through, see
     ``lka3d_attention_volume``); offsets_out: list that receives the two offset tensors this run samples with."""
     st = store if store is not None else (lambda t: t)

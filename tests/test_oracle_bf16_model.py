@@ -4,7 +4,7 @@ floor() of a sampling coordinate is discontinuous.  With EVERY activation stored
 a = GELU(proj_1 x) -> conv0 -> conv_spatial -> conv_offset predicts offsets ~0.4 % away from the fp32 block's, the samples that close to an integer
 coordinate change cell, each flip moves that sample's grad_offset by O(1), and the gradients that sum grad_offset (conv_offset.*) or receive it
 through grad_t (conv_spatial, conv0, proj_1) land far outside SURVEY §8c's 2e-2 bar — for ANY implementation.  With the chain kept in fp32 and
-everything else in bf16 (what dlka_capi_cl.hip's TokGeoms does) every gradient is inside the bar.  Both models are oracle.blocks with per-tensor
+everything else in bf16 (what capi_lka3d_tokens.h's TokGeoms does) every gradient is inside the bar.  Both models are oracle.blocks with per-tensor
 storage flags; no kernel is involved."""
 import pytest
 import torch
