@@ -64,7 +64,8 @@ int cl_prep_table_blocks(const PrepJob &j);   // workgroups job j takes in a pre
 int launch_cl_prep_table(const PrepJob *jobs_dev, const int *first_dev, int job_lo, int job_hi, int nblocks, hipStream_t st);
 int cl_igemm_pick_splits(int M, int units, int epi, int K);
 int launch_cl_pointwise(const IgemmArgs &a, hipStream_t st);
-int launch_cl_pointwise_pair(const PwPairArgs &a, hipStream_t st);   // two dependent pointwise convs in one launch (C = 32 / 64)
+int launch_cl_pointwise_pair(const PwPairArgs &a, hipStream_t st);   // two dependent pointwise convs in one launch, one wave per row tile (C = 32)
+int launch_cl_pointwise_chain(const PwPairArgs &a, hipStream_t st);  // ... a workgroup per row tile, waves split columns and channel chunks (C = 64 / 128 / 256)
 int launch_cl_conv_wave(int amode, int omode, const IgemmArgs &a, int splits, hipStream_t st);
 bool cl_conv_kw_applies(int amode, int omode, int split_bf16, int K, int epi, int NP, bool act_bf16, bool volume);   // cl_conv_kw.hip: K split over the waves of a workgroup
 int launch_cl_conv_kw(int amode, int omode, const IgemmArgs &a, hipStream_t st);   // deterministic small-volume contraction (no tap split, no atomics, no zero fill)

@@ -505,6 +505,10 @@ long dlka_conv_brick_launch_count(void);
 /* launches so far of the fused small-volume depthwise pair (csrc/cl_dwpair.hip: dw 5^3 -> dw 7^3 dil 3, or their data gradients + GELU', of a volume of at most
  * 512 voxels with W in {4, 8} in ONE launch; DLKA_DWPAIR=0, read per call, keeps one launch per conv): parity tests assert which kernel ran */
 long dlka_dwpair_launch_count(void);
+/* launches so far of the workgroup-tiled pointwise chain (csrc/cl_pointwise.hip, cl_pointwise_chain_kernel: conv1 + gate -> proj_2 + shortcut, or their data
+ * gradients, of a token-layout block with C = 64 / 128 in ONE launch, bit-identical to the two launches; C = 256 only with DLKA_PW_CHAIN_256=1: it measured slower; DLKA_PW_UNFUSED=1, read per call, keeps those):
+ * parity tests assert which kernel ran */
+long dlka_pw_chain_launch_count(void);
 /* Diagnostics: launches of cl_conv_kw_kernel (round 6: the small-volume split-operand convs — offset-predict conv, its data gradient, UnetResBlock's 3^3 convs at the
  * 16^3 / 8^3 / 4^3 stages — with the contraction split over the waves of ONE workgroup and summed in wave order in LDS: bitwise reproducible, no global atomics;
  * DLKA_CONV_KW=0 restores the tap split over the grid) and of the deformable forward's workgroup-split variants.  Tests assert which kernel ran. */
