@@ -22,6 +22,9 @@ DLKA_F32, DLKA_BF16, DLKA_F64 = 0, 1, 2
 DLKA_TILES_MAX_T, DLKA_TILES_K_MAX = 64, 32                            # include/dlka.h: dlka_tiles_*
 DLKA_TILES_IDENTITY, DLKA_TILES_SOFTMAX, DLKA_TILES_SIGMOID = 0, 1, 2
 LKA3D_SYNAPSE, LKA3D_ACDC = 0, 1   # dlka_lka3d_variant (include/dlka.h)
+DLKA_SEG_LOSS_K_MAX = 32                                               # include/dlka.h: dlka_seg_loss_*
+DLKA_SEG_LOSS_NNUNET, DLKA_SEG_LOSS_DICE2D = 0, 1
+DLKA_LABEL_F32, DLKA_LABEL_I64 = 0, 1
 
 
 class ConvGeom(ctypes.Structure):
@@ -56,8 +59,16 @@ class Lka2dPtrs(ctypes.Structure):
     _fields_ = [(n, c_void_p) for n in LKA2D_FIELDS]
 
 
+class SegLossDesc(ctypes.Structure):
+    """``dlka_seg_loss_desc`` (include/dlka.h)."""
+    _fields_ = [("B", c_int32), ("K", c_int32), ("N", c_int64), ("dtype", c_int32), ("label_dtype", c_int32), ("mode", c_int32),
+                ("batch_dice", c_int32), ("do_bg", c_int32), ("smooth", ctypes.c_float), ("weight_ce", ctypes.c_float),
+                ("weight_dice", ctypes.c_float), ("class_weight", ctypes.c_float * DLKA_SEG_LOSS_K_MAX)]
+
+
 # name -> (restype, argtypes); every symbol include/dlka.h declares
 _G = POINTER(ConvGeom)
+_SD = POINTER(SegLossDesc)
 SIGNATURES = {
     "dlka_abi_version": (c_int, []),
     "dlka_status_string": (c_char_p, [c_int]),
@@ -183,6 +194,11 @@ SIGNATURES = {
                          + [POINTER(c_int), c_int, POINTER(c_int)] + [c_int] * 4 + [c_void_p]),
     "dlka_tiles_finalize": (c_int, [c_void_p] * 2 + [c_int] * 10 + [c_void_p] * 3),
     "dlka_tiles_launch_count": (ctypes.c_long, []),
+    "dlka_seg_loss_workspace_bytes": (c_size_t, [_SD]),
+    "dlka_seg_loss_forward": (c_int, [c_void_p, c_void_p, _SD, c_void_p, c_size_t] + [c_void_p] * 5),
+    "dlka_seg_loss_backward": (c_int, [c_void_p, c_void_p, _SD] + [c_void_p] * 4),
+    "dlka_seg_eval_counts": (c_int, [c_void_p, c_void_p, _SD, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "dlka_seg_loss_launch_count": (ctypes.c_long, []),
     "dlka_trace_start": (c_int, [c_int, c_void_p]),
     "dlka_trace_mark": (c_int, [c_void_p]),
     "dlka_trace_stop": (c_int, []),

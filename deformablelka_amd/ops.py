@@ -969,3 +969,68 @@ def tiles_finalize(score, weight, pad_lo, shape):
 
 def tiles_launch_count() -> int:
     return int(L.get_lib().dlka_tiles_launch_count())
+
+
+# ---- the trainers' segmentation losses (include/dlka.h: dlka_seg_loss_*, dlka_seg_eval_counts) ---------------------------------------------
+def _seg_desc(logits, labels, mode=L.DLKA_SEG_LOSS_NNUNET, batch_dice=False, do_bg=True, smooth=1.0, weight_ce=1.0, weight_dice=1.0, class_weight=None):
+    """Checks of the planar pair (logits (B, K, *), labels (B, 1, *) or (B, *) float32 / int64, read as they are) and the description of the call."""
+    L.require_device(logits, labels)
+    if logits.ndim < 3:
+        raise RuntimeError(f"seg_loss: logits must be (B, K, *spatial), got {tuple(logits.shape)}")
+    B, K = int(logits.shape[0]), int(logits.shape[1])
+    N = logits[0, 0].numel()
+    if K > L.DLKA_SEG_LOSS_K_MAX:
+        raise NotImplementedError(f"seg_loss: K = {K} classes (the kernels keep at most {L.DLKA_SEG_LOSS_K_MAX} in registers)")
+    spatial = tuple(logits.shape[2:])
+    if tuple(labels.shape) not in ((B, 1) + spatial, (B,) + spatial):
+        raise RuntimeError(f"seg_loss: labels {tuple(labels.shape)} are not a label map of logits {tuple(logits.shape)}")
+    if labels.device != logits.device:
+        raise RuntimeError("seg_loss: logits and labels live on different devices")
+    if labels.dtype not in (torch.float32, torch.int64):
+        labels = labels.float() if labels.is_floating_point() else labels.long()
+    d = L.SegLossDesc()
+    d.B, d.K, d.N = B, K, N
+    d.dtype, d.label_dtype = L.dtype_code(logits), (L.DLKA_LABEL_F32 if labels.dtype == torch.float32 else L.DLKA_LABEL_I64)
+    d.mode, d.batch_dice, d.do_bg = int(mode), int(bool(batch_dice)), int(bool(do_bg))
+    d.smooth, d.weight_ce, d.weight_dice = float(smooth), float(weight_ce), float(weight_dice)
+    for k in range(K):
+        d.class_weight[k] = 1.0 if class_weight is None else float(class_weight[k])
+    return d, logits.contiguous(), labels.contiguous()
+
+
+def seg_loss_forward(logits, labels, **kw):
+    """Returns (loss (), dc (B, K), stats (B, 4K + 2), coef (3BK + 1,), desc, logits, labels): the last three are what ``seg_loss_backward`` takes."""
+    d, logits, labels = _seg_desc(logits, labels, **kw)
+    lib = L.get_lib()
+    B, K = d.B, d.K
+    ws = L.scratch(lib.dlka_seg_loss_workspace_bytes(ctypes.byref(d)), logits)
+    out = torch.empty(1 + B * K + B * (4 * K + 2) + 3 * B * K + 1, dtype=torch.float32, device=logits.device)
+    loss, dc, stats, coef = out[0:1], out[1:1 + B * K], out[1 + B * K:1 + B * K + B * (4 * K + 2)], out[1 + B * K + B * (4 * K + 2):]
+    L.check(lib.dlka_seg_loss_forward(L.ptr(logits), L.ptr(labels), ctypes.byref(d), L.ptr(ws), ws.numel(), L.ptr(loss), L.ptr(dc), L.ptr(stats),
+                                      L.ptr(coef), L.stream_ptr(logits)), "seg_loss_forward")
+    return loss.reshape(()), dc.view(B, K), stats.view(B, 4 * K + 2), coef, d, logits, labels
+
+
+def seg_loss_backward(logits, labels, d, coef, grad_output):
+    """The logits' gradient, in their dtype; ``grad_output`` is read on the device (one float32 value)."""
+    grad_output = grad_output.to(torch.float32).contiguous()
+    L.require_device(logits, labels, coef, grad_output)
+    gx = torch.empty_like(logits)
+    L.check(L.get_lib().dlka_seg_loss_backward(L.ptr(logits), L.ptr(labels), ctypes.byref(d), L.ptr(coef), L.ptr(grad_output), L.ptr(gx),
+                                               L.stream_ptr(logits)), "seg_loss_backward")
+    return gx
+
+
+def seg_eval_counts(logits, labels):
+    """(tp, fp, fn), each (K - 1,) int64: hard counts of the foreground classes over the batch (argmax: first maximum)."""
+    d, logits, labels = _seg_desc(logits, labels)
+    lib = L.get_lib()
+    ws = L.scratch(lib.dlka_seg_loss_workspace_bytes(ctypes.byref(d)), logits)
+    counts = torch.empty((3, d.K - 1), dtype=torch.int64, device=logits.device)
+    L.check(lib.dlka_seg_eval_counts(L.ptr(logits), L.ptr(labels), ctypes.byref(d), L.ptr(ws), ws.numel(), L.ptr(counts), L.stream_ptr(logits)),
+            "seg_eval_counts")
+    return counts[0], counts[1], counts[2]
+
+
+def seg_loss_launch_count() -> int:
+    return int(L.get_lib().dlka_seg_loss_launch_count())

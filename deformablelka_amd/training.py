@@ -11,6 +11,7 @@ import torch
 import torch.nn as nn
 
 from . import inference
+from .losses import DC_and_CE_loss, MultipleOutputLoss2
 from .network import D_LKA_Former
 from .transformerblock import TransformerBlock_3D_single_deform_LKA
 
@@ -89,6 +90,31 @@ def deep_supervision_loss(outputs, target, weights=None, base_loss: Callable = N
             tgt = nn.functional.interpolate(tgt[:, None].float(), size=out.shape[-3:], mode="nearest")[:, 0].long()
         total = total + (weights[i] / s) * base_loss(out, tgt)
     return total
+
+
+class DeepSupervisionDiceCE(MultipleOutputLoss2):
+    """``MultipleOutputLoss2`` as the 3-D trainer wraps its loss, which also takes ONE full-resolution label volume ((B, 1, *) or (B, *)) in place of the
+    list the reference's data loader delivers: it is then nearest-neighbour down-sampled to each head's extents (as ``deep_supervision_loss`` does)."""
+
+    def forward(self, x, y):
+        if isinstance(y, torch.Tensor):
+            if y.ndim == x[0].ndim - 1:
+                y = y[:, None]
+            full = y if y.is_floating_point() else y.float()
+            y = [y if y.shape[2:] == out.shape[2:] else nn.functional.interpolate(full, size=out.shape[2:], mode="nearest") for out in x]
+        return super().forward(x, y)
+
+
+def initialize_loss(deep_supervision: bool = True, num_heads: int = 3, batch_dice: bool = True):
+    """What the 3-D trainer steps: ``DC_and_CE_loss({'batch_dice': batch_dice, 'smooth': 1e-5, 'do_bg': False}, {})`` (Trainer_synapse.py:109) on the fused HIP
+    kernels (``losses.py``), wrapped for deep supervision with the weights 1, 1/2, 1/4, ... normalised to sum 1 (d_lka_former_trainer_synapse.py:99-108).
+    Pass it as ``loss_fn`` to ``run_iteration`` / ``GraphedIteration``; their default stays ``deep_supervision_loss``."""
+    loss = DC_and_CE_loss({"batch_dice": batch_dice, "smooth": 1e-5, "do_bg": False}, {})
+    if not deep_supervision:
+        return loss
+    weights = [1.0 / (2 ** i) for i in range(num_heads)]
+    total = sum(weights)
+    return DeepSupervisionDiceCE(loss, [w / total for w in weights])
 
 
 def run_iteration(net: nn.Module, optimizer, data: torch.Tensor, target, loss_fn: Callable = deep_supervision_loss, do_backprop: bool = True,

@@ -601,6 +601,64 @@ int dlka_tiles_finalize(const float *score, const float *weight, int K, int Xp, 
 long dlka_tiles_launch_count(void);
 
 /* =======================================================================================
+ * Segmentation losses of the two trainers — csrc/cl_seg_loss.hip
+ * =======================================================================================
+ * The 3-D trainer steps nnU-Net's DC_and_CE_loss({'batch_dice': True, 'smooth': 1e-5, 'do_bg': False}, {})
+ * (3D/d_lka_former/training/network_training/Trainer_synapse.py:109; loss_functions/dice_loss.py:158-194 SoftDiceLoss, :304-361
+ * DC_and_CE_loss, :100-155 get_tp_fp_fn_tn) per deep-supervision head; the 2-D trainer steps 0.4 CE + 0.6 DiceLoss(softmax=True)
+ * (2D/trainer_MaxViT_deform_LKA.py:137-139; 2D/utils.py:11-47).  Both are functions of per-(sample, class) sums over the voxels of
+ * p = softmax(logits, 1):
+ *      tp = sum p_k [y = k]     sp = sum p_k     sq = sum p_k^2     cnt = sum [y = k]     and per sample  ce = sum (logsumexp - x_y)
+ * (nnU-Net's fp = sp - tp and fn = cnt - tp, so 2 tp + fp + fn = sp + cnt).
+ *
+ *   logits   planar [B][K][N], N = product of the spatial extents (rank 4 and rank 5 alike), DLKA_F32 or DLKA_BF16, contiguous
+ *   labels   [B][N] label map, DLKA_LABEL_F32 (what both reference loaders deliver) or DLKA_LABEL_I64, read as they are
+ *
+ * mode DLKA_SEG_LOSS_NNUNET:   dc = (2 tp + smooth) / (sp + cnt + smooth + 1e-8) per (b, k), or per k with the sums taken over the batch
+ *                              (batch_dice); class 0 dropped unless do_bg;  loss = weight_ce * mean_voxels(ce) - weight_dice * mean(dc)
+ * mode DLKA_SEG_LOSS_DICE2D:   dice_k = 1 - (2 sum_b tp + 1e-5) / (sum_b sq + sum_b cnt + 1e-5);  loss = sum_k class_weight[k] dice_k / K
+ *                              (smooth, weight_*, batch_dice, do_bg are not read)
+ *
+ * A label that is not an integer in [0, K) never indexes anything: it belongs to no class.  In NNUNET mode (the reference's scatter_
+ * would raise) the loss and the gradient are NaN; in DICE2D mode (one-hot by equality, utils.py:16-22) that is the reference's result.
+ *
+ * forward: one streaming launch (one partial row per workgroup in `workspace`) and one finishing launch that adds the rows in a fixed
+ * order in double precision: no atomics, no host read, bitwise reproducible, capturable.  Outputs (device, fp32):
+ *   loss[1];  dc[B][K] (NNUNET: the Dice coefficients, all rows equal under batch_dice, 0 for a dropped background; DICE2D: 1 - dice_k);
+ *   stats[B][4K + 2] = tp[K], sp[K], sq[K], cnt[K], ce, number of invalid labels;
+ *   coef[B][3][K] + 1: the backward's per-class scalars, dloss/dp_k(v) = coef[b][0][k] + coef[b][1][k] p_k + coef[b][2][k] [y(v) = k], then
+ *   the cross-entropy scale weight_ce / (B N).
+ * backward: one streaming launch; recomputes the softmax, grad_logits_j = grad_output * (p_j (g_j - sum_k g_k p_k) + ce_scale (p_j - [y = j])),
+ * written once in the logits' dtype.  grad_output: one fp32 value in device memory.
+ * Return codes: DLKA_ERR_NULL, DLKA_ERR_SHAPE, DLKA_ERR_DTYPE, DLKA_ERR_UNSUPPORTED (K > DLKA_SEG_LOSS_K_MAX, unknown mode),
+ * DLKA_ERR_WORKSPACE. */
+#define DLKA_SEG_LOSS_K_MAX 32
+#define DLKA_SEG_LOSS_NNUNET 0
+#define DLKA_SEG_LOSS_DICE2D 1
+#define DLKA_LABEL_F32 0
+#define DLKA_LABEL_I64 1
+typedef struct dlka_seg_loss_desc {
+    int32_t B, K;
+    int64_t N;
+    int32_t dtype, label_dtype, mode, batch_dice, do_bg;
+    float smooth, weight_ce, weight_dice;
+    float class_weight[DLKA_SEG_LOSS_K_MAX];   /* DICE2D: `weight` of DiceLoss.forward (utils.py:37-38: ones when absent) */
+} dlka_seg_loss_desc;
+/* bytes of `workspace` for dlka_seg_loss_forward and dlka_seg_eval_counts of this shape (0 for an invalid description) */
+size_t dlka_seg_loss_workspace_bytes(const dlka_seg_loss_desc *d);
+int dlka_seg_loss_forward(const void *logits, const void *labels, const dlka_seg_loss_desc *d, void *workspace, size_t workspace_bytes,
+                          float *loss, float *dc, float *stats, float *coef, void *stream);
+int dlka_seg_loss_backward(const void *logits, const void *labels, const dlka_seg_loss_desc *d, const float *coef, const float *grad_output,
+                           void *grad_logits, void *stream);
+/* Trainer_synapse.py:697-718 (run_online_evaluation) without its softmax and masked passes: seg = first-maximum argmax of the logits
+ * (torch.argmax; softmax is monotonic), counts[3][K - 1] int64 = hard tp / fp / fn of the foreground classes 1 .. K-1, summed over the
+ * batch.  Reads B, K, N and the two dtypes of `d`.  Two launches (stream + finish), integer arithmetic throughout. */
+int dlka_seg_eval_counts(const void *logits, const void *labels, const dlka_seg_loss_desc *d, void *workspace, size_t workspace_bytes,
+                         int64_t *counts, void *stream);
+/* Diagnostics: kernel launches so far (this process) of the three entries above. */
+long dlka_seg_loss_launch_count(void);
+
+/* =======================================================================================
  * Launch trace — measurement aid (no reference counterpart; the reference has no profiling hooks)
  * =======================================================================================
  * Between dlka_trace_start and dlka_trace_stop every kernel launch of the library is followed by a HIP timing event on the
