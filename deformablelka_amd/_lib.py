@@ -25,6 +25,8 @@ LKA3D_SYNAPSE, LKA3D_ACDC = 0, 1   # dlka_lka3d_variant (include/dlka.h)
 DLKA_SEG_LOSS_K_MAX = 32                                               # include/dlka.h: dlka_seg_loss_*
 DLKA_SEG_LOSS_NNUNET, DLKA_SEG_LOSS_DICE2D = 0, 1
 DLKA_LABEL_F32, DLKA_LABEL_I64 = 0, 1
+DLKA_SD_K_MAX = 32                                                     # include/dlka.h: dlka_sd_*
+DLKA_SD_U8, DLKA_SD_I16, DLKA_SD_I32, DLKA_SD_I64 = 0, 1, 2, 3
 
 
 class ConvGeom(ctypes.Structure):
@@ -66,9 +68,16 @@ class SegLossDesc(ctypes.Structure):
                 ("weight_dice", ctypes.c_float), ("class_weight", ctypes.c_float * DLKA_SEG_LOSS_K_MAX)]
 
 
+class SurfaceDistDesc(ctypes.Structure):
+    """``dlka_sd_desc`` (include/dlka.h)."""
+    _fields_ = [("rank", c_int32), ("connectivity", c_int32), ("label_dtype", c_int32), ("K", c_int32), ("mask_mode", c_int32),
+                ("ext", c_int64 * 3), ("spacing", ctypes.c_double * 3), ("class_id", c_int64 * DLKA_SD_K_MAX)]
+
+
 # name -> (restype, argtypes); every symbol include/dlka.h declares
 _G = POINTER(ConvGeom)
 _SD = POINTER(SegLossDesc)
+_SDD = POINTER(SurfaceDistDesc)
 SIGNATURES = {
     "dlka_abi_version": (c_int, []),
     "dlka_status_string": (c_char_p, [c_int]),
@@ -199,6 +208,11 @@ SIGNATURES = {
     "dlka_seg_loss_backward": (c_int, [c_void_p, c_void_p, _SD] + [c_void_p] * 4),
     "dlka_seg_eval_counts": (c_int, [c_void_p, c_void_p, _SD, c_void_p, c_size_t, c_void_p, c_void_p]),
     "dlka_seg_loss_launch_count": (ctypes.c_long, []),
+    "dlka_sd_stats_workspace_bytes": (c_size_t, [_SDD]),
+    "dlka_sd_label_stats": (c_int, [c_void_p, c_void_p, _SDD, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "dlka_sd_distance_cells": (c_int64, [_SDD, POINTER(c_int64)]),
+    "dlka_sd_distances": (c_int, [c_void_p, c_void_p, _SDD, POINTER(c_int64), c_void_p, c_size_t, c_void_p, c_int64, c_void_p]),
+    "dlka_sd_launch_count": (ctypes.c_long, []),
     "dlka_trace_start": (c_int, [c_int, c_void_p]),
     "dlka_trace_mark": (c_int, [c_void_p]),
     "dlka_trace_stop": (c_int, []),

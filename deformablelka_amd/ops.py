@@ -1034,3 +1034,92 @@ def seg_eval_counts(logits, labels):
 
 def seg_loss_launch_count() -> int:
     return int(L.get_lib().dlka_seg_loss_launch_count())
+
+
+# ---- overlap counts and surface distances of label maps (include/dlka.h: dlka_sd_*) ----------------------------------------------------------
+_SD_DTYPES = {torch.uint8: L.DLKA_SD_U8, torch.bool: L.DLKA_SD_U8, torch.int16: L.DLKA_SD_I16, torch.int32: L.DLKA_SD_I32, torch.int64: L.DLKA_SD_I64}
+
+
+def _sd_desc(prediction, label, class_ids=None, voxelspacing=None, connectivity=1):
+    """Checks of the pair of maps and the description of the call; ``class_ids=None``: the maps are masks (value != 0)."""
+    L.require_device(prediction, label)
+    rank = prediction.ndim
+    if rank not in (2, 3):
+        raise RuntimeError(f"surface distances: the maps must have rank 2 or 3, got {tuple(prediction.shape)}")
+    if tuple(prediction.shape) != tuple(label.shape):
+        raise RuntimeError(f"surface distances: the two maps differ in extents, {tuple(prediction.shape)} against {tuple(label.shape)}")
+    if prediction.numel() == 0:
+        raise RuntimeError(f"surface distances: empty extents {tuple(prediction.shape)}")
+    if prediction.device != label.device:
+        raise RuntimeError("surface distances: the two maps live on different devices")
+    for t in (prediction, label):
+        if t.dtype not in _SD_DTYPES:
+            raise RuntimeError(f"surface distances: label maps are uint8, int16, int32, int64 or bool, got {t.dtype}")
+    if prediction.dtype != label.dtype:
+        common = torch.promote_types(prediction.dtype, label.dtype)
+        common = common if common in _SD_DTYPES else torch.int64
+        prediction, label = prediction.to(common), label.to(common)
+    if voxelspacing is None:
+        spacing = [1.0] * rank
+    else:
+        spacing = [float(s) for s in voxelspacing]
+        if len(spacing) != rank:
+            raise RuntimeError(f"surface distances: voxelspacing has {len(spacing)} entries for rank {rank}")
+        if not all(0.0 < s < 1e100 for s in spacing):
+            raise RuntimeError(f"surface distances: voxelspacing must be positive, got {spacing}")
+    connectivity = int(connectivity)
+    if not 1 <= connectivity <= rank:
+        raise RuntimeError(f"surface distances: connectivity must be between 1 and the rank ({rank}), got {connectivity}")
+    ids = [0] if class_ids is None else [int(c) for c in class_ids]
+    if not 1 <= len(ids) <= L.DLKA_SD_K_MAX:
+        raise RuntimeError(f"surface distances: between 1 and {L.DLKA_SD_K_MAX} classes per call, got {len(ids)}")
+    d = L.SurfaceDistDesc()
+    d.rank, d.connectivity, d.label_dtype, d.K, d.mask_mode = rank, connectivity, _SD_DTYPES[prediction.dtype], len(ids), int(class_ids is None)
+    for ax in range(3):
+        d.ext[ax] = 1 if ax < 3 - rank else int(prediction.shape[ax - (3 - rank)])
+        d.spacing[ax] = 1.0 if ax < 3 - rank else spacing[ax - (3 - rank)]
+    for k, c in enumerate(ids):
+        d.class_id[k] = c
+    return d, prediction.contiguous(), label.contiguous()
+
+
+def sd_label_stats(prediction, label, class_ids=None, voxelspacing=None, connectivity=1):
+    """Returns (stats (K, 9) int64 on the device = |a & b|, |a|, |b|, box lo d h w, box hi d h w per class; desc, prediction, label): the last
+    three are what ``sd_distances`` takes."""
+    d, prediction, label = _sd_desc(prediction, label, class_ids, voxelspacing, connectivity)
+    lib = L.get_lib()
+    ws = L.scratch(lib.dlka_sd_stats_workspace_bytes(ctypes.byref(d)), prediction)
+    stats = torch.empty((d.K, 9), dtype=torch.int64, device=prediction.device)
+    L.check(lib.dlka_sd_label_stats(L.ptr(prediction), L.ptr(label), ctypes.byref(d), L.ptr(ws), ws.numel(), L.ptr(stats), L.stream_ptr(prediction)),
+            "sd_label_stats")
+    return stats, d, prediction, label
+
+
+def sd_distances(prediction, label, d, boxes):
+    """boxes: K rows (lo d, h, w, extent d, h, w) on the host, an extent of 0 skips the class.  Returns (sqdist float64 on the device, offsets):
+    class c with n_c box cells has the squared distances prediction -> label at sqdist[offsets[c] : offsets[c] + n_c] and label -> prediction in
+    the n_c cells behind them, -1 off the border."""
+    L.require_device(prediction, label)
+    flat = [int(v) for row in boxes for v in row]
+    if len(flat) != 6 * d.K:
+        raise RuntimeError(f"sd_distances: {d.K} boxes of 6 integers expected")
+    arr = (ctypes.c_int64 * len(flat))(*flat)
+    lib = L.get_lib()
+    total = int(lib.dlka_sd_distance_cells(ctypes.byref(d), arr))
+    if total < 0:
+        raise RuntimeError("sd_distances: a box lies outside the maps")
+    offsets, off = [], 0
+    for k in range(d.K):
+        offsets.append(off)
+        n = flat[6 * k + 3] * flat[6 * k + 4] * flat[6 * k + 5]
+        off += 2 * n
+    sq = torch.empty(total, dtype=torch.float64, device=prediction.device)
+    ws = L.scratch(12 * total, prediction)
+    if total:
+        L.check(lib.dlka_sd_distances(L.ptr(prediction), L.ptr(label), ctypes.byref(d), arr, L.ptr(ws), ws.numel(), L.ptr(sq), total,
+                                      L.stream_ptr(prediction)), "sd_distances")
+    return sq, offsets
+
+
+def sd_launch_count() -> int:
+    return int(L.get_lib().dlka_sd_launch_count())

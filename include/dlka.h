@@ -659,6 +659,57 @@ int dlka_seg_eval_counts(const void *logits, const void *labels, const dlka_seg_
 long dlka_seg_loss_launch_count(void);
 
 /* =======================================================================================
+ * Overlap counts and surface distances of label maps (DSC, HD, HD95, ASD) — csrc/cl_surface_dist.hip
+ * =======================================================================================
+ * Every evaluator of the reference scores a prediction with medpy.metric.binary.dc and hd95 on whole volumes, per organ
+ * (2D/utils.py:50-60 calculate_metric_percase, :96-98 test_single_volume; 3D/d_lka_former/inference_synapse.py:11-21;
+ * inference_acdc.py:29-51; 3D/pancreas_code/test_util.py:130; 3D/d_lka_former/evaluation/metrics.py:314-383 hausdorff_distance,
+ * hausdorff_distance_95, avg_surface_distance, avg_surface_distance_symmetric).  MedPy 0.4.0:
+ *      border(m) = m ^ binary_erosion(m, generate_binary_structure(rank, connectivity))       (cells outside the array count as 0)
+ *      sds(a, b) = distance_transform_edt(~border(b), sampling = spacing)[border(a)]
+ * and dc = 2 |a & b| / (|a| + |b|), hd = max, hd95 = 95th percentile of sds(a, b) ++ sds(b, a), asd = mean of sds(a, b).
+ *
+ *   prediction, label   two maps of equal extents ext[3] = (d, h, w), w contiguous; rank 2 has ext[0] = 1 (and no neighbours along d: a
+ *                       rank-3 map of depth 1 is all border).  Same dtype, DLKA_SD_U8 (bool too) / I16 / I32 / I64, read as they are.
+ *   classes             class_id[K]: mask_c = (map == class_id[c]).  mask_mode != 0: K = 1 and mask = (map != 0), medpy's astype(bool).
+ *
+ * dlka_sd_label_stats: stats[K][9] int64 (device) = |a & b|, |a|, |b|, then lo d h w and hi d h w of the bounding box of a | b (lo > hi when
+ * the class is absent from both maps).  One pass over both maps per 4 classes and one finishing launch; integers, fixed order.
+ *
+ * dlka_sd_distances: boxes[K][6] int64 (HOST) = lo d h w, extent d h w of the region to transform for each class, inside the array; an
+ * extent of 0 skips the class.  The box must contain both masks of its class (the box of the stats above does; so does the whole array):
+ * then the result equals that of the whole array, because outside the box both masks are 0 just as outside the array.  For class c with
+ * n_c box cells, sqdist[off_c .. off_c + n_c) holds, in box order, the SQUARED Euclidean distance sum_i (delta_i spacing_i)^2 (float64;
+ * with unit spacing an exact integer) from each border cell of the prediction's mask to the nearest border cell of the label's, and -1 at
+ * every other cell; sqdist[off_c + n_c .. off_c + 2 n_c) the same from the label's border to the prediction's.  off_c = sum of 2 n_j over
+ * the classes before c; dlka_sd_distance_cells returns the total (-1 for an invalid description or box).  Exact: every candidate of every
+ * line is visited.  No atomics: bitwise reproducible.  workspace: 12 bytes per cell of the total.
+ * Return codes: DLKA_ERR_NULL, DLKA_ERR_SHAPE (rank not 2 or 3, extents, spacing not positive, a box outside the array, sqdist too short),
+ * DLKA_ERR_DTYPE, DLKA_ERR_UNSUPPORTED (connectivity outside 1..rank, K outside 1..DLKA_SD_K_MAX, more than 2^31 - 1 cells, w > 32768),
+ * DLKA_ERR_WORKSPACE.  Nothing is read before the checks pass. */
+#define DLKA_SD_K_MAX 32
+#define DLKA_SD_U8 0
+#define DLKA_SD_I16 1
+#define DLKA_SD_I32 2
+#define DLKA_SD_I64 3
+typedef struct dlka_sd_desc {
+    int32_t rank, connectivity, label_dtype, K, mask_mode;
+    int64_t ext[3];
+    double spacing[3];                    /* per axis d, h, w (rank 2: [0] is not read); None of medpy = 1.0 */
+    int64_t class_id[DLKA_SD_K_MAX];
+} dlka_sd_desc;
+size_t dlka_sd_stats_workspace_bytes(const dlka_sd_desc *d);   /* 0 for an invalid description */
+/* dc's three counts per class (medpy.metric.binary.dc; inference_synapse.py:11-21) and the crop box of the transform */
+int dlka_sd_label_stats(const void *prediction, const void *label, const dlka_sd_desc *d, void *workspace, size_t workspace_bytes,
+                        int64_t *stats, void *stream);
+int64_t dlka_sd_distance_cells(const dlka_sd_desc *d, const int64_t *boxes);
+/* medpy.metric.binary.__surface_distances for every class and both directions (hd, hd95, asd, assd; metrics.py:314-383) */
+int dlka_sd_distances(const void *prediction, const void *label, const dlka_sd_desc *d, const int64_t *boxes, void *workspace,
+                      size_t workspace_bytes, double *sqdist, int64_t sqdist_cells, void *stream);
+/* Diagnostics: kernel launches so far (this process) of the entries above. */
+long dlka_sd_launch_count(void);
+
+/* =======================================================================================
  * Launch trace — measurement aid (no reference counterpart; the reference has no profiling hooks)
  * =======================================================================================
  * Between dlka_trace_start and dlka_trace_stop every kernel launch of the library is followed by a HIP timing event on the

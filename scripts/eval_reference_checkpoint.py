@@ -12,8 +12,9 @@ never produced this number: VERDICT r5, missing #6).
   `<id>_img.npy` ([C, D, H, W] or [D, H, W]) / `<id>_seg.npy`;
 * inference: the reference's validation protocol — `predict_3D` with sliding window, Gaussian importance weighting, step 0.5 and test-time mirroring along all
   three axes (D_LKA_Former.predict_3D, the HIP tile kernels; --no-mirroring for one forward per tile);
-* metric: Dice per foreground class over the classes present in either map, and their mean per case and over cases (Synapse: 13 organs; the paper's table averages 8 of them —
-  pass --classes 1 2 3 4 6 7 8 11 for that subset, evaluate_synapse-style).
+* metric: Dice and HD95 per foreground class (deformablelka_amd.metrics.evaluate_label_maps: medpy's definitions on the HIP kernels, nnU-Net's convention — a class
+  absent from both maps is skipped, HD95 is reported where both masks exist) and their means per case and over cases (Synapse: 13 organs; the paper's table averages 8
+  of them — pass --classes 1 2 3 4 6 7 8 11 for that subset, evaluate_synapse-style; --spacing for HD95 in millimetres).
 No reference number is hard-coded here: compare the output with the paper's table."""
 import argparse
 import glob
@@ -36,7 +37,7 @@ def load_reference_state_dict(path):
 
 
 def dice_per_class(pred, target, classes):
-    """{class: 2 |P ∩ T| / (|P| + |T|)} over the classes present in `pred` or `target` (absent in both: skipped, as nnU-Net's evaluator reports NaN for them)."""
+    """Host helper for small arrays (main() scores with deformablelka_amd.metrics on the device).  {class: 2 |P ∩ T| / (|P| + |T|)} over the classes present in `pred` or `target` (absent in both: skipped, as nnU-Net's evaluator reports NaN for them)."""
     out = {}
     for c in classes:
         p, t = pred == c, target == c
@@ -68,11 +69,12 @@ def main():
     ap.add_argument("--classes", type=int, nargs="*", default=None, help="foreground classes to score (default: 1 .. num_classes - 1)")
     ap.add_argument("--bf16", action="store_true", help="run the D-LKA blocks on bf16 activations (torch.autocast)")
     ap.add_argument("--no-mirroring", action="store_true", help="predict without test-time mirroring (the paper's protocol mirrors)")
+    ap.add_argument("--spacing", type=float, nargs=3, default=None, help="voxel spacing (D, H, W) for HD95; default: voxels, as inference_synapse.py")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("needs the MI355X: the product has no CPU path")
-    from deformablelka_amd import training
+    from deformablelka_amd import metrics, training
     dev = torch.device("cuda", 0)
     net = training.initialize_network(1, args.num_classes, tuple(args.patch), device=dev, patch_size=tuple(args.stem), wgrad_overlap=False)
     sd = load_reference_state_dict(args.checkpoint)
@@ -89,12 +91,17 @@ def main():
         img, seg = load_case(f)
         pred, _ = net.predict_3D(img, not args.no_mirroring, mirror_axes=(0, 1, 2), use_sliding_window=True, step_size=args.step,
                                  patch_size=tuple(args.patch), use_gaussian=True, verbose=False, mixed_precision=args.bf16)
-        d = dice_per_class(pred, np.where(seg < 0, 0, seg), classes)
-        per_case[os.path.basename(f)] = {"dice": d, "mean": float(np.mean(list(d.values()))) if d else None}
+        m = metrics.evaluate_label_maps(pred, np.where(seg < 0, 0, seg), classes, voxelspacing=args.spacing, nan_for_nonexisting=True)
+        d = {int(c): float(v) for c, v in zip(classes, m["dice"]) if not np.isnan(v)}
+        h = {int(c): float(v) for c, v in zip(classes, m["hd95"]) if not np.isnan(v)}
+        per_case[os.path.basename(f)] = {"dice": d, "mean": float(np.mean(list(d.values()))) if d else None, "hd95": h,
+                                         "mean_hd95": float(np.mean(list(h.values()))) if h else None}
         print(os.path.basename(f), per_case[os.path.basename(f)]["mean"], flush=True)
     means = [v["mean"] for v in per_case.values() if v["mean"] is not None]
     by_class = {c: float(np.mean([v["dice"][c] for v in per_case.values() if c in v["dice"]])) for c in classes if any(c in v["dice"] for v in per_case.values())}
-    res = {"checkpoint": args.checkpoint, "cases": len(files), "mean_dsc": float(np.mean(means)) if means else None, "dsc_by_class": by_class, "per_case": per_case,
+    hd_by_class = {c: float(np.mean([v["hd95"][c] for v in per_case.values() if c in v["hd95"]])) for c in classes if any(c in v["hd95"] for v in per_case.values())}
+    res = {"checkpoint": args.checkpoint, "cases": len(files), "mean_dsc": float(np.mean(means)) if means else None, "dsc_by_class": by_class,
+           "mean_hd95": float(np.mean(list(hd_by_class.values()))) if hd_by_class else None, "hd95_by_class": hd_by_class, "per_case": per_case,
            "activations": "bf16" if args.bf16 else "fp32", "patch": args.patch, "step": args.step, "mirroring": not args.no_mirroring}
     print(json.dumps({k: v for k, v in res.items() if k != "per_case"}))
     if args.out:
