@@ -27,6 +27,8 @@ DLKA_SEG_LOSS_NNUNET, DLKA_SEG_LOSS_DICE2D = 0, 1
 DLKA_LABEL_F32, DLKA_LABEL_I64 = 0, 1
 DLKA_SD_K_MAX = 32                                                     # include/dlka.h: dlka_sd_*
 DLKA_SD_U8, DLKA_SD_I16, DLKA_SD_I32, DLKA_SD_I64 = 0, 1, 2, 3
+DLKA_CC_K_MAX, DLKA_CC_IDS_MAX = 32, 64                                # include/dlka.h: dlka_cc_*
+DLKA_CC_SUMMARY = 1 + 2 * DLKA_CC_K_MAX
 
 
 class ConvGeom(ctypes.Structure):
@@ -74,10 +76,18 @@ class SurfaceDistDesc(ctypes.Structure):
                 ("ext", c_int64 * 3), ("spacing", ctypes.c_double * 3), ("class_id", c_int64 * DLKA_SD_K_MAX)]
 
 
+class ConnCompDesc(ctypes.Structure):
+    """``dlka_cc_desc`` (include/dlka.h)."""
+    _fields_ = [("rank", c_int32), ("connectivity", c_int32), ("label_dtype", c_int32), ("K", c_int32), ("mask_mode", c_int32),
+                ("n_ids", c_int32), ("has_min", c_int32), ("ext", c_int64 * 3), ("class_id", c_int64 * DLKA_CC_IDS_MAX),
+                ("entry_of", c_int32 * DLKA_CC_IDS_MAX), ("min_count", c_int64 * DLKA_CC_K_MAX)]
+
+
 # name -> (restype, argtypes); every symbol include/dlka.h declares
 _G = POINTER(ConvGeom)
 _SD = POINTER(SegLossDesc)
 _SDD = POINTER(SurfaceDistDesc)
+_CCD = POINTER(ConnCompDesc)
 SIGNATURES = {
     "dlka_abi_version": (c_int, []),
     "dlka_status_string": (c_char_p, [c_int]),
@@ -213,6 +223,10 @@ SIGNATURES = {
     "dlka_sd_distance_cells": (c_int64, [_SDD, POINTER(c_int64)]),
     "dlka_sd_distances": (c_int, [c_void_p, c_void_p, _SDD, POINTER(c_int64), c_void_p, c_size_t, c_void_p, c_int64, c_void_p]),
     "dlka_sd_launch_count": (ctypes.c_long, []),
+    "dlka_cc_workspace_bytes": (c_size_t, [_CCD]),
+    "dlka_cc_components": (c_int, [c_void_p, _CCD, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "dlka_cc_component_table": (c_int, [_CCD, c_void_p, c_size_t, c_int64, c_void_p, c_void_p, c_void_p]),
+    "dlka_cc_launch_count": (ctypes.c_long, []),
     "dlka_trace_start": (c_int, [c_int, c_void_p]),
     "dlka_trace_mark": (c_int, [c_void_p]),
     "dlka_trace_stop": (c_int, []),

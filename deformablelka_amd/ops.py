@@ -1123,3 +1123,72 @@ def sd_distances(prediction, label, d, boxes):
 
 def sd_launch_count() -> int:
     return int(L.get_lib().dlka_sd_launch_count())
+
+
+# ---- connected components of label maps and the largest-component filter (include/dlka.h: dlka_cc_*) -----------------------------------------
+def _cc_desc(image, entries=None, connectivity=1, min_counts=None):
+    """Checks of the map and the description of one pass; ``entries``: sequences of class ids, pairwise disjoint; None: the mask (value != 0)."""
+    L.require_device(image)
+    rank = image.ndim
+    if rank not in (1, 2, 3):
+        raise RuntimeError(f"connected components: the map must have rank 1, 2 or 3, got {tuple(image.shape)}")
+    if image.numel() == 0:
+        raise RuntimeError(f"connected components: empty extents {tuple(image.shape)}")
+    if image.numel() >= 2 ** 31:
+        raise RuntimeError(f"connected components: fewer than 2^31 cells per map, got {image.numel()}")
+    if image.dtype not in _SD_DTYPES:
+        raise RuntimeError(f"connected components: label maps are uint8, int16, int32, int64 or bool, got {image.dtype}")
+    connectivity = int(connectivity)
+    if not 1 <= connectivity <= rank:
+        raise RuntimeError(f"connected components: connectivity must be between 1 and the rank ({rank}), got {connectivity}")
+    d = L.ConnCompDesc()
+    d.rank, d.connectivity, d.label_dtype, d.mask_mode = rank, connectivity, _SD_DTYPES[image.dtype], int(entries is None)
+    for ax in range(3):
+        d.ext[ax] = 1 if ax < 3 - rank else int(image.shape[ax - (3 - rank)])
+    if entries is None:
+        d.K, d.n_ids = 1, 0
+    else:
+        pairs = [(int(c), k) for k, ids in enumerate(entries) for c in ids]
+        if not 1 <= len(entries) <= L.DLKA_CC_K_MAX or not 1 <= len(pairs) <= L.DLKA_CC_IDS_MAX:
+            raise RuntimeError(f"connected components: between 1 and {L.DLKA_CC_K_MAX} entries and at most {L.DLKA_CC_IDS_MAX} class ids per pass, "
+                               f"got {len(entries)} and {len(pairs)}")
+        if len({c for c, _ in pairs}) != len(pairs):
+            raise RuntimeError("connected components: the entries of one pass must not share a class id")
+        d.K, d.n_ids = len(entries), len(pairs)
+        for j, (c, k) in enumerate(pairs):
+            d.class_id[j], d.entry_of[j] = c, k
+    if min_counts is not None:
+        if len(min_counts) != d.K:
+            raise RuntimeError(f"connected components: {d.K} minimum counts expected, got {len(min_counts)}")
+        d.has_min = 1
+        for k, t in enumerate(min_counts):
+            d.min_count[k] = int(t)
+    return d, image.contiguous()
+
+
+def cc_components(image, entries=None, connectivity=1, min_counts=None, want_filtered=True):
+    """One pass.  Returns (labels int32 like the map, filtered (dtype of the map) or None, summary int32 (DLKA_CC_SUMMARY,) on the device =
+    [components, largest size per entry ..., largest removed size per entry ...], state): ``state`` is what ``cc_component_table`` takes."""
+    d, image = _cc_desc(image, entries, connectivity, min_counts)
+    lib = L.get_lib()
+    ws = L.scratch(lib.dlka_cc_workspace_bytes(ctypes.byref(d)), image)
+    labels = torch.empty(image.shape, dtype=torch.int32, device=image.device)
+    filtered = torch.empty_like(image) if want_filtered else None
+    summary = torch.empty(L.DLKA_CC_SUMMARY, dtype=torch.int32, device=image.device)
+    L.check(lib.dlka_cc_components(L.ptr(image), ctypes.byref(d), L.ptr(ws), ws.numel(), L.ptr(labels), L.ptr(filtered), L.ptr(summary),
+                                   L.stream_ptr(image)), "cc_components")
+    return labels, filtered, summary, (d, ws)
+
+
+def cc_component_table(state, n):
+    """(sizes int64 (n,), owner int32 (n,)) of the components 1..n of the pass that returned ``state``."""
+    d, ws = state
+    sizes = torch.empty(n, dtype=torch.int64, device=ws.device)
+    owner = torch.empty(n, dtype=torch.int32, device=ws.device)
+    L.check(L.get_lib().dlka_cc_component_table(ctypes.byref(d), L.ptr(ws), ws.numel(), n, L.ptr(sizes), L.ptr(owner), L.stream_ptr(ws)),
+            "cc_component_table")
+    return sizes, owner
+
+
+def cc_launch_count() -> int:
+    return int(L.get_lib().dlka_cc_launch_count())

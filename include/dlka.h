@@ -710,6 +710,53 @@ int dlka_sd_distances(const void *prediction, const void *label, const dlka_sd_d
 long dlka_sd_launch_count(void);
 
 /* =======================================================================================
+ * Connected components of label maps and the "largest component" filter — csrc/cl_conn_comp.hip
+ * =======================================================================================
+ * nnU-Net's post-processing as the reference runs it at the end of Trainer_synapse.validate() / Trainer_acdc.validate()
+ * (determine_postprocessing) and for every predicted case in inference/predict.py (load_remove_save):
+ * remove_all_but_the_largest_connected_component, 3D/d_lka_former/postprocessing/connected_components.py:48-105 — per class or region
+ * one scipy.ndimage.label (:76), object sizes (:80-81), the largest object and every object of its size kept (:89-94), the others removed
+ * when no minimum size is given or when they are smaller than it (:96-100), the largest removed size recorded (:101-104).
+ *
+ *   image               one map of rank 1..3, extents left-padded with 1 to ext[3] = (d, h, w), w contiguous; DLKA_SD_U8 (bool too) / I16 / I32 / I64.
+ *   entries             K entries, each a set of class ids: class_id[j] belongs to entry entry_of[j], j < n_ids; the ids are pairwise different
+ *                       (a cell belongs to at most one entry).  mask_mode != 0: K = 1, the entry is (image != 0), scipy.ndimage.label's input.
+ *   neighbourhood       generate_binary_structure(rank, connectivity), connectivity 1..rank; cells outside the array are background.  Two
+ *                       neighbouring cells are connected iff they belong to the same entry.
+ *   filter              a component is kept when its size equals its entry's largest, or when has_min != 0 and its size >= min_count[entry]
+ *                       (cells; the caller turns the reference's float threshold into the count that compares alike).
+ *
+ * dlka_cc_components: labels[N] int32 = 0 for background, else 1 + the number of components whose first cell comes earlier in raster order
+ * (scipy's numbering, over all entries of the pass together); filtered[N] (dtype of the image; may be NULL, must not be the image) = the image
+ * with the removed components set to 0; summary[DLKA_CC_SUMMARY] int32 (device) = [0] the number of components, [1 + e] the largest size of
+ * entry e (0: no cell), [1 + DLKA_CC_K_MAX + e] the largest removed size of entry e (0: nothing removed).  Six launches and one memset on
+ * `stream`; integer atomics only, every output bitwise reproducible (the argument is in the file's header).
+ * dlka_cc_component_table: after dlka_cc_components with the same description and workspace (untouched in between): sizes[capacity] int64 and
+ * owner[capacity] int32 (the entry) of component r + 1 at index r; components beyond `capacity` are not written.  One launch.
+ * workspace: 9 bytes per cell plus 4 per 2048 cells (dlka_cc_workspace_bytes; 0 for an invalid description).
+ * Return codes: DLKA_ERR_NULL, DLKA_ERR_SHAPE (rank outside 1..3, an extent < 1, a padded extent != 1, entry_of outside 0..K-1, a negative
+ * min_count or capacity), DLKA_ERR_DTYPE, DLKA_ERR_UNSUPPORTED (connectivity outside 1..rank, K outside 1..DLKA_CC_K_MAX, n_ids outside
+ * 1..DLKA_CC_IDS_MAX, an id listed twice, 2^31 cells or more, filtered == image), DLKA_ERR_WORKSPACE.  Nothing is launched before the
+ * checks pass.  The contiguous axis has no limit of its own: a line longer than a tile (64 cells; 2048 for a single line) spans tiles. */
+#define DLKA_CC_K_MAX 32
+#define DLKA_CC_IDS_MAX 64
+#define DLKA_CC_SUMMARY (1 + 2 * DLKA_CC_K_MAX)
+typedef struct dlka_cc_desc {
+    int32_t rank, connectivity, label_dtype, K, mask_mode, n_ids, has_min;
+    int64_t ext[3];
+    int64_t class_id[DLKA_CC_IDS_MAX];
+    int32_t entry_of[DLKA_CC_IDS_MAX];
+    int64_t min_count[DLKA_CC_K_MAX];
+} dlka_cc_desc;
+size_t dlka_cc_workspace_bytes(const dlka_cc_desc *d);
+int dlka_cc_components(const void *image, const dlka_cc_desc *d, void *workspace, size_t workspace_bytes, int32_t *labels, void *filtered,
+                       int32_t *summary, void *stream);
+int dlka_cc_component_table(const dlka_cc_desc *d, const void *workspace, size_t workspace_bytes, int64_t capacity, int64_t *sizes,
+                            int32_t *owner, void *stream);
+/* Diagnostics: kernel launches so far (this process) of the entries above. */
+long dlka_cc_launch_count(void);
+
+/* =======================================================================================
  * Launch trace — measurement aid (no reference counterpart; the reference has no profiling hooks)
  * =======================================================================================
  * Between dlka_trace_start and dlka_trace_stop every kernel launch of the library is followed by a HIP timing event on the
