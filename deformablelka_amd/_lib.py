@@ -29,6 +29,7 @@ DLKA_SD_K_MAX = 32                                                     # include
 DLKA_SD_U8, DLKA_SD_I16, DLKA_SD_I32, DLKA_SD_I64 = 0, 1, 2, 3
 DLKA_CC_K_MAX, DLKA_CC_IDS_MAX = 32, 64                                # include/dlka.h: dlka_cc_*
 DLKA_CC_SUMMARY = 1 + 2 * DLKA_CC_K_MAX
+DLKA_RESAMPLE_SPLINE_PAD = 12                                          # scipy.ndimage: edge samples in front of the prefilter for mode 'nearest'
 
 
 class ConvGeom(ctypes.Structure):
@@ -83,11 +84,17 @@ class ConnCompDesc(ctypes.Structure):
                 ("entry_of", c_int32 * DLKA_CC_IDS_MAX), ("min_count", c_int64 * DLKA_CC_K_MAX)]
 
 
+class ResampleDesc(ctypes.Structure):
+    """``dlka_resample_desc`` (include/dlka.h)."""
+    _fields_ = [("C", c_int32), ("dtype", c_int32), ("taps", c_int32 * 3), ("in_", c_int64 * 3), ("out", c_int64 * 3)]
+
+
 # name -> (restype, argtypes); every symbol include/dlka.h declares
 _G = POINTER(ConvGeom)
 _SD = POINTER(SegLossDesc)
 _SDD = POINTER(SurfaceDistDesc)
 _CCD = POINTER(ConnCompDesc)
+_RSD = POINTER(ResampleDesc)
 SIGNATURES = {
     "dlka_abi_version": (c_int, []),
     "dlka_status_string": (c_char_p, [c_int]),
@@ -227,6 +234,13 @@ SIGNATURES = {
     "dlka_cc_components": (c_int, [c_void_p, _CCD, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]),
     "dlka_cc_component_table": (c_int, [_CCD, c_void_p, c_size_t, c_int64, c_void_p, c_void_p, c_void_p]),
     "dlka_cc_launch_count": (ctypes.c_long, []),
+    "dlka_resample_argmax": (c_int, [c_void_p, c_void_p, _RSD, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "dlka_resample_linear": (c_int, [c_void_p, c_void_p, _RSD, c_void_p, c_void_p, c_void_p]),
+    "dlka_resample_labels": (c_int, [c_void_p, c_void_p, _RSD, c_void_p, c_void_p, c_int, c_void_p]),
+    "dlka_resample_spline_pad": (c_int, [c_void_p, c_void_p, c_int, POINTER(c_int64), POINTER(c_int64), c_void_p]),
+    "dlka_resample_spline_prefilter": (c_int, [c_void_p, POINTER(c_int64), c_int, c_void_p]),
+    "dlka_resample_spline_eval": (c_int, [c_void_p, c_void_p, _RSD, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "dlka_resample_launch_count": (ctypes.c_long, []),
     "dlka_trace_start": (c_int, [c_int, c_void_p]),
     "dlka_trace_mark": (c_int, [c_void_p]),
     "dlka_trace_stop": (c_int, []),

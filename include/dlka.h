@@ -757,6 +757,49 @@ int dlka_cc_component_table(const dlka_cc_desc *d, const void *workspace, size_t
 long dlka_cc_launch_count(void);
 
 /* =======================================================================================
+ * Resampling of probabilities, images and label maps; resampling fused with the argmax — csrc/cl_resample.hip
+ * =======================================================================================
+ * resample_data_or_seg (3D/d_lka_former/preprocessing/preprocessing.py:112-201) as save_segmentation_nifti_from_softmax calls it for the class
+ * probabilities (inference/segmentation_export.py:104-106, followed by the argmax of :119-125) and resample_patient for a case and its label
+ * map (preprocessing.py:99-108).  skimage's resize(mode='edge', anti_aliasing=False), batchgenerators' resize_segmentation and the
+ * reference's own z step (:163-187) all sample the source at (i + 0.5) * n_in / n_out - 0.5 per axis.
+ *
+ *   volumes     C channels of extents in[3], the last axis contiguous, channels in_cells apart; results out[3] likewise.
+ *   tables      built by the caller in float64, on the device, the three axes one after the other (axis ax starts at row out[0] + .. +
+ *               out[ax - 1]).  Linear entries: idx[2 * row + k] (source cell, 0 <= idx < in[ax]) and w[2 * row + k], k < 2; an axis with
+ *               taps[ax] == 1 reads k = 0 only (order 0: the nearest cell, weight 1).  Spline entries: start[row], w4[4 * row + k];
+ *               taps[ax] is 4 (cells start .. start + 3 of the coefficient array) or 1.  The library cannot check the cells a table names.
+ *
+ * dlka_resample_argmax (:104-106 and :119-125 in one pass): labels[out cells] uint8 = the first maximum over the C resampled channels
+ * (numpy.argmax), or with region_class (C values, device) the value of the last channel whose resampled value is > 0.5, else 0.  The
+ * resampled channels are never stored.  dlka_resample_linear (:153-158, :177, :196 for orders 0 and 1): every channel stored; the same
+ * arithmetic in the same order, so the argmax of its output is dlka_resample_argmax's map bit for bit.  dtype: DLKA_F32 or DLKA_F64.
+ * dlka_resample_labels (resize_segmentation as :127, :153-158, :196 bind it; strict != 0: the z step of :180-187): int32 maps; per output cell
+ * the largest label whose summed weight is >= 0.5 (strict: > 0.5) among the source cells, 0 when there is none.
+ * dlka_resample_spline_pad / _prefilter / _eval (order 3, :130-131 with :153-158 or :196): float64; pad[ax] edge samples on both sides, the
+ * cubic B-spline prefilter in place along one axis of ext[3], the 4-tap evaluation of one channel clipped to [lo[s], hi[s]], s = the output
+ * index along clip_axis, or 0 when clip_axis < 0.
+ * One launch each, no atomics: results are bitwise reproducible.  Return codes: DLKA_ERR_NULL, DLKA_ERR_SHAPE (C or an extent < 1, a negative
+ * pad, an axis outside 0..2), DLKA_ERR_DTYPE, DLKA_ERR_UNSUPPORTED (taps other than 1 or 2 (spline: 4), 2^31 cells or more, C > 256 for the
+ * argmax, C != 1 for the spline, output == input).  Nothing is launched before the checks pass. */
+typedef struct dlka_resample_desc {
+    int32_t C, dtype;
+    int32_t taps[3];
+    int64_t in[3], out[3];
+} dlka_resample_desc;
+int dlka_resample_argmax(const void *x, uint8_t *labels, const dlka_resample_desc *d, const int32_t *idx, const double *w,
+                         const int32_t *region_class, void *stream);
+int dlka_resample_linear(const void *x, void *y, const dlka_resample_desc *d, const int32_t *idx, const double *w, void *stream);
+int dlka_resample_labels(const int32_t *seg, int32_t *out, const dlka_resample_desc *d, const int32_t *idx, const double *w, int strict,
+                         void *stream);
+int dlka_resample_spline_pad(const void *x, double *padded, int dtype, const int64_t *in, const int64_t *pad, void *stream);
+int dlka_resample_spline_prefilter(double *coef, const int64_t *ext, int axis, void *stream);
+int dlka_resample_spline_eval(const double *coef, double *y, const dlka_resample_desc *d, const int32_t *start, const double *w4,
+                              const double *lo, const double *hi, int clip_axis, void *stream);
+/* Diagnostics: kernel launches so far (this process) of the entries above. */
+long dlka_resample_launch_count(void);
+
+/* =======================================================================================
  * Launch trace — measurement aid (no reference counterpart; the reference has no profiling hooks)
  * =======================================================================================
  * Between dlka_trace_start and dlka_trace_stop every kernel launch of the library is followed by a HIP timing event on the
