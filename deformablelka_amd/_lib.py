@@ -30,6 +30,11 @@ DLKA_SD_U8, DLKA_SD_I16, DLKA_SD_I32, DLKA_SD_I64 = 0, 1, 2, 3
 DLKA_CC_K_MAX, DLKA_CC_IDS_MAX = 32, 64                                # include/dlka.h: dlka_cc_*
 DLKA_CC_SUMMARY = 1 + 2 * DLKA_CC_K_MAX
 DLKA_RESAMPLE_SPLINE_PAD = 12                                          # scipy.ndimage: edge samples in front of the prefilter for mode 'nearest'
+DLKA_AUG_I16 = 3                                                       # include/dlka.h: dlka_augment_*
+DLKA_AUG_CONSTANT, DLKA_AUG_NEAREST = 0, 1
+DLKA_AUG_RADIUS_MAX, DLKA_AUG_OPS_MAX = 32, 4
+(DLKA_AUG_OP_NONE, DLKA_AUG_OP_NOISE, DLKA_AUG_OP_SCALE_ADD, DLKA_AUG_OP_CONTRAST, DLKA_AUG_OP_GAMMA, DLKA_AUG_OP_RETAIN,
+ DLKA_AUG_OP_REPLACE) = range(7)
 
 
 class ConvGeom(ctypes.Structure):
@@ -89,12 +94,19 @@ class ResampleDesc(ctypes.Structure):
     _fields_ = [("C", c_int32), ("dtype", c_int32), ("taps", c_int32 * 3), ("in_", c_int64 * 3), ("out", c_int64 * 3)]
 
 
+class AugmentDesc(ctypes.Structure):
+    """``dlka_augment_desc`` (include/dlka.h)."""
+    _fields_ = [("B", c_int32), ("C", c_int32), ("dtype", c_int32), ("order", c_int32), ("mode", c_int32), ("pad", c_int32),
+                ("src", c_int64 * 3), ("out", c_int64 * 3), ("cval", ctypes.c_double)]
+
+
 # name -> (restype, argtypes); every symbol include/dlka.h declares
 _G = POINTER(ConvGeom)
 _SD = POINTER(SegLossDesc)
 _SDD = POINTER(SurfaceDistDesc)
 _CCD = POINTER(ConnCompDesc)
 _RSD = POINTER(ResampleDesc)
+_AGD = POINTER(AugmentDesc)
 SIGNATURES = {
     "dlka_abi_version": (c_int, []),
     "dlka_status_string": (c_char_p, [c_int]),
@@ -241,6 +253,14 @@ SIGNATURES = {
     "dlka_resample_spline_prefilter": (c_int, [c_void_p, POINTER(c_int64), c_int, c_void_p]),
     "dlka_resample_spline_eval": (c_int, [c_void_p, c_void_p, _RSD, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "dlka_resample_launch_count": (ctypes.c_long, []),
+    "dlka_augment_spatial": (c_int, [c_void_p, c_void_p, c_void_p, _AGD, c_void_p, c_void_p, c_void_p]),
+    "dlka_augment_spatial_labels": (c_int, [c_void_p, c_void_p, _AGD, c_void_p, c_void_p, c_void_p]),
+    "dlka_augment_spline_prefilter_mirror": (c_int, [c_void_p, POINTER(c_int64), c_int, c_void_p]),
+    "dlka_augment_gaussian": (c_int, [c_void_p, c_void_p, c_int, c_int64, POINTER(c_int64), c_int, c_void_p, c_void_p, c_void_p]),
+    "dlka_augment_stats_workspace_bytes": (c_size_t, [c_int64, c_int64]),
+    "dlka_augment_channel_stats": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int64, c_int64, c_void_p]),
+    "dlka_augment_pointwise": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int64, POINTER(c_int64)] + [c_void_p] * 5),
+    "dlka_augment_launch_count": (ctypes.c_long, []),
     "dlka_trace_start": (c_int, [c_int, c_void_p]),
     "dlka_trace_mark": (c_int, [c_void_p]),
     "dlka_trace_stop": (c_int, []),

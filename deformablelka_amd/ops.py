@@ -1319,3 +1319,175 @@ def resample_spline(x, out, tables, pad, lo, hi, clip_axis=-1):
 
 def resample_launch_count() -> int:
     return int(L.get_lib().dlka_resample_launch_count())
+
+
+# ---- train-time augmentation (include/dlka.h: dlka_augment_*) -----------------------------------------------------------------------------
+_AUG_DTYPES = {torch.float32: L.DLKA_F32, torch.bfloat16: L.DLKA_BF16, torch.float64: L.DLKA_F64, torch.int16: L.DLKA_AUG_I16}
+
+
+def _aug_volume(x, what):
+    L.require_device(x)
+    if x.ndim != 5 or x.numel() == 0:
+        raise RuntimeError(f"augment: {what} is (b, c, x, y, z) with no empty axis, got {tuple(x.shape)}")
+    if x[0, 0].numel() >= 2 ** 31:
+        raise RuntimeError("augment: fewer than 2^31 cells per channel")
+    return x.contiguous()
+
+
+def _aug_desc(x, out, order, mode, cval, pad=0, dtype=L.DLKA_F32):
+    out = tuple(int(v) for v in out)
+    if len(out) != 3 or min(out) < 1 or out[0] * out[1] * out[2] >= 2 ** 31:
+        raise RuntimeError(f"augment: three positive patch extents below 2^31 cells, got {out}")
+    d = L.AugmentDesc()
+    d.B, d.C, d.dtype, d.order, d.mode, d.pad, d.cval = int(x.shape[0]), int(x.shape[1]), dtype, int(order), int(mode), int(pad), float(cval)
+    for ax in range(3):
+        d.src[ax], d.out[ax] = int(x.shape[2 + ax]), out[ax]
+    return d, out
+
+
+def _aug_sample_tables(x, out, maps, plain):
+    """maps (B, 3, 4) float64 and plain (B, 4) int (flag, lb0, lb1, lb2) on the device.  The kernels trust the boxes: checked here."""
+    maps = np.ascontiguousarray(np.asarray(maps, dtype=np.float64).reshape(-1, 12))
+    plain = np.ascontiguousarray(np.asarray(plain, dtype=np.int32).reshape(-1, 4))
+    if maps.shape[0] != x.shape[0] or plain.shape[0] != x.shape[0]:
+        raise RuntimeError(f"augment: one map and one crop record per sample ({x.shape[0]})")
+    for b in range(plain.shape[0]):
+        if plain[b, 0] and any(plain[b, 1 + ax] < 0 or plain[b, 1 + ax] + out[ax] > x.shape[2 + ax] for ax in range(3)):
+            raise RuntimeError(f"augment: the crop of sample {b} at {plain[b, 1:].tolist()} leaves the source {tuple(x.shape[2:])}")
+    return torch.from_numpy(maps).to(x.device), torch.from_numpy(plain).to(x.device)
+
+
+def augment_spline_coefficients(x, mode):
+    """float64 cubic B-spline coefficients of every channel of ``x`` (b, c, x, y, z), as scipy.ndimage.map_coordinates prepares them: mode
+    'nearest' pads DLKA_RESAMPLE_SPLINE_PAD edge samples and filters with the 'reflect' start values, 'constant' filters the array itself
+    with the 'mirror' ones.  Returns (coefficients (b, c, x + 2 pad, ...), pad)."""
+    x = _aug_volume(x, "data")
+    src = x if x.dtype in _RS_DTYPES else x.to(torch.float64 if x.dtype == torch.int16 else torch.float32)
+    pad = L.DLKA_RESAMPLE_SPLINE_PAD if mode == L.DLKA_AUG_NEAREST else 0
+    ext = [int(n) + 2 * pad for n in x.shape[2:]]
+    if ext[0] * ext[1] * ext[2] >= 2 ** 31:
+        raise RuntimeError("augment: fewer than 2^31 cells per padded channel")
+    lib, st = L.get_lib(), L.stream_ptr(x)
+    coef = torch.empty([x.shape[0], x.shape[1]] + ext, dtype=torch.float64, device=x.device)
+    i3 = ctypes.c_int64 * 3
+    for b in range(x.shape[0]):
+        for c in range(x.shape[1]):
+            L.check(lib.dlka_resample_spline_pad(L.ptr(src[b, c]), L.ptr(coef[b, c]), _RS_DTYPES[src.dtype], i3(*x.shape[2:]), i3(pad, pad, pad), st),
+                    "resample_spline_pad")
+            for ax in range(3):
+                if mode == L.DLKA_AUG_NEAREST:
+                    L.check(lib.dlka_resample_spline_prefilter(L.ptr(coef[b, c]), i3(*ext), ax, st), "resample_spline_prefilter")
+                else:
+                    L.check(lib.dlka_augment_spline_prefilter_mirror(L.ptr(coef[b, c]), i3(*ext), ax, st), "augment_spline_prefilter_mirror")
+    return coef, pad
+
+
+def augment_spatial(x, out, maps, plain, order, mode, cval):
+    """``x`` (b, c, x, y, z; float32, bfloat16, float64, int16) sampled at the per-sample affine ``maps`` with scipy's map_coordinates rules
+    (orders 0, 1, 3; mode DLKA_AUG_CONSTANT / DLKA_AUG_NEAREST); samples whose ``plain`` flag is set are copied boxes."""
+    x = _aug_volume(x, "data")
+    if x.dtype not in _AUG_DTYPES:
+        raise RuntimeError(f"augment: float32, bfloat16, float64 or int16 volumes, got {x.dtype}")
+    coef, pad = (augment_spline_coefficients(x, mode) if order == 3 and not all(int(p[0]) for p in np.asarray(plain).reshape(-1, 4))
+                 else (None, 0))
+    if order == 3 and coef is None:
+        order = 0                                            # every sample is a plain crop: nothing is interpolated
+    d, out = _aug_desc(x, out, order, mode, cval, pad, _AUG_DTYPES[x.dtype])
+    m, p = _aug_sample_tables(x, out, maps, plain)
+    y = torch.empty(tuple(x.shape[:2]) + out, dtype=x.dtype, device=x.device)
+    L.check(L.get_lib().dlka_augment_spatial(L.ptr(x), L.ptr(coef), L.ptr(y), ctypes.byref(d), L.ptr(m), L.ptr(p), L.stream_ptr(x)),
+            "augment_spatial")
+    return y
+
+
+def augment_spatial_labels(seg, out, maps, plain, order, mode, cval):
+    """int32 label maps (b, c, x, y, z) at the same coordinates: order 0 the nearest cell, order 1 the largest label whose trilinear weight is
+    >= 0.5, else 0."""
+    seg = _aug_volume(seg, "seg")
+    if seg.dtype != torch.int32:
+        raise RuntimeError(f"augment: int32 label maps, got {seg.dtype}")
+    d, out = _aug_desc(seg, out, order, mode, cval)
+    m, p = _aug_sample_tables(seg, out, maps, plain)
+    y = torch.empty(tuple(seg.shape[:2]) + out, dtype=torch.int32, device=seg.device)
+    L.check(L.get_lib().dlka_augment_spatial_labels(L.ptr(seg), L.ptr(y), ctypes.byref(d), L.ptr(m), L.ptr(p), L.stream_ptr(seg)),
+            "augment_spatial_labels")
+    return y
+
+
+def augment_gaussian(x, radius, weights):
+    """scipy.ndimage.gaussian_filter of every channel of ``x`` (b, c, x, y, z), one launch per axis: ``radius`` (b * c,) int, < 0 = the channel
+    is copied; ``weights`` (b * c, DLKA_AUG_RADIUS_MAX + 1) float64, centre first."""
+    x = _aug_volume(x, "data")
+    if x.dtype not in _AUG_DTYPES:
+        raise RuntimeError(f"augment: float32, bfloat16, float64 or int16 volumes, got {x.dtype}")
+    n = x.shape[0] * x.shape[1]
+    radius = np.ascontiguousarray(np.asarray(radius, dtype=np.int32).reshape(-1))
+    weights = np.ascontiguousarray(np.asarray(weights, dtype=np.float64))
+    if radius.shape != (n,) or weights.shape != (n, L.DLKA_AUG_RADIUS_MAX + 1) or radius.max() > L.DLKA_AUG_RADIUS_MAX:
+        raise RuntimeError(f"augment: {n} radii of at most {L.DLKA_AUG_RADIUS_MAX} and their weight rows expected")
+    r, w = torch.from_numpy(radius).to(x.device), torch.from_numpy(weights).to(x.device)
+    i3 = ctypes.c_int64 * 3
+    for ax in range(3):
+        y = torch.empty_like(x)
+        L.check(L.get_lib().dlka_augment_gaussian(L.ptr(x), L.ptr(y), _AUG_DTYPES[x.dtype], n, i3(*x.shape[2:]), ax, L.ptr(r), L.ptr(w),
+                                                  L.stream_ptr(x)), "augment_gaussian")
+        x = y
+    return x
+
+
+def augment_channel_stats(x):
+    """(b * c, 4) float64 on the device: sum, sum of squares about the mean, min, max of every channel of ``x`` (b, c, x, y, z)."""
+    x = _aug_volume(x, "data")
+    if x.dtype not in _AUG_DTYPES:
+        raise RuntimeError(f"augment: float32, bfloat16, float64 or int16 volumes, got {x.dtype}")
+    n, cells = x.shape[0] * x.shape[1], x[0, 0].numel()
+    if n > 65535:
+        raise RuntimeError("augment: at most 65535 channels in a batch")
+    lib = L.get_lib()
+    nbytes = lib.dlka_augment_stats_workspace_bytes(n, cells)
+    ws = torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=x.device)
+    stats = torch.empty((n, 4), dtype=torch.float64, device=x.device)
+    L.check(lib.dlka_augment_channel_stats(L.ptr(x), L.ptr(stats), L.ptr(ws), nbytes, _AUG_DTYPES[x.dtype], n, cells, L.stream_ptr(x)),
+            "augment_channel_stats")
+    return stats
+
+
+def augment_pointwise(x, steps, noise=None, stats0=None, stats1=None, flip=None):
+    """One streaming pass over ``x`` (b, c, x, y, z): ``steps`` (b * c, k <= DLKA_AUG_OPS_MAX, 6) float64 rows (code, p0 .. p4) applied in turn
+    per channel; ``flip`` (b,) int, bit a reverses spatial axis a of the stored result."""
+    x = _aug_volume(x, "data")
+    if x.dtype not in _AUG_DTYPES:
+        raise RuntimeError(f"augment: float32, bfloat16, float64 or int16 volumes, got {x.dtype}")
+    n = x.shape[0] * x.shape[1]
+    steps = np.asarray(steps, dtype=np.float64)
+    if steps.ndim != 3 or steps.shape[0] != n or steps.shape[1] > L.DLKA_AUG_OPS_MAX or steps.shape[2] != 6:
+        raise RuntimeError(f"augment: steps are ({n}, <= {L.DLKA_AUG_OPS_MAX}, 6), got {steps.shape}")
+    table = np.zeros((n, L.DLKA_AUG_OPS_MAX, 6))
+    table[:, :steps.shape[1]] = steps
+    codes = set(table[:, :, 0].reshape(-1).tolist())
+    if not codes <= set(float(c) for c in range(7)):
+        raise RuntimeError(f"augment: unknown step codes {sorted(codes)}")
+    if float(L.DLKA_AUG_OP_NOISE) in codes:
+        if noise is None or noise.shape != x.shape or noise.dtype != x.dtype or noise.device != x.device:
+            raise RuntimeError("augment: the noise step takes a field of the data's shape, dtype and device")
+        noise = noise.contiguous()
+    need0 = codes & {float(L.DLKA_AUG_OP_CONTRAST), float(L.DLKA_AUG_OP_GAMMA), float(L.DLKA_AUG_OP_RETAIN)}
+    for s, need in ((stats0, bool(need0)), (stats1, float(L.DLKA_AUG_OP_RETAIN) in codes)):
+        if need and (s is None or tuple(s.shape) != (n, 4) or s.dtype != torch.float64 or s.device != x.device or not s.is_contiguous()):
+            raise RuntimeError(f"augment: ({n}, 4) float64 channel statistics on the data's device expected")
+    f = None
+    if flip is not None:
+        flip = np.ascontiguousarray(np.asarray(flip, dtype=np.int32).reshape(-1))
+        if flip.shape != (x.shape[0],) or flip.min() < 0 or flip.max() > 7:
+            raise RuntimeError(f"augment: one flip mask 0..7 per sample ({x.shape[0]})")
+        f = torch.from_numpy(flip).to(x.device)
+    t = torch.from_numpy(table).to(x.device)
+    y = torch.empty_like(x)
+    i3 = ctypes.c_int64 * 3
+    L.check(L.get_lib().dlka_augment_pointwise(L.ptr(x), L.ptr(noise), L.ptr(y), _AUG_DTYPES[x.dtype], x.shape[0], x.shape[1], i3(*x.shape[2:]),
+                                               L.ptr(t), L.ptr(stats0), L.ptr(stats1), L.ptr(f), L.stream_ptr(x)), "augment_pointwise")
+    return y
+
+
+def augment_launch_count() -> int:
+    return int(L.get_lib().dlka_augment_launch_count())

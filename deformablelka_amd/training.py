@@ -182,3 +182,12 @@ class GraphedIteration:
                                "old value; build a new GraphedIteration after changing it")
         self.graph.replay()
         return self.loss.clone()   # (a copy: ``self.loss`` is the graph's static output buffer, overwritten by the next replay)
+
+
+def augmented_batches(loader, augmentation):
+    """The trainer's ``tr_gen`` with the transform chain on the device: every batch of ``loader`` (a dict with 'data' (B, C, D, H, W) and 'seg',
+    as the reference's DataLoader3D yields them) goes through ``augmentation`` (``augmentation.MoreDAAugmentation``) and comes out as
+    ``(data, target)`` for ``run_iteration(net, optimizer, data, target, loss_fn=initialize_loss())``."""
+    for batch in loader:
+        out = augmentation(batch["data"], batch["seg"])
+        yield out["data"], out["target"]

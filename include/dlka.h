@@ -800,6 +800,68 @@ int dlka_resample_spline_eval(const double *coef, double *y, const dlka_resample
 long dlka_resample_launch_count(void);
 
 /* =======================================================================================
+ * Train-time augmentation of a batch of patches — csrc/cl_augment.hip
+ * =======================================================================================
+ * The apply half of the 3-D trainer's transform chain (get_moreDA_augmentation, 3D/d_lka_former/training/data_augmentation/
+ * data_augmentation_moreDA.py:60-147; batchgenerators' SpatialTransform, noise, blur, brightness, contrast, gamma and mirror).  What is
+ * random is drawn by the caller on the host; every entry here is a pure function of its inputs.  Volumes are [B][C][D][H][W], W contiguous.
+ *
+ * storage      dtype is a dlka_dtype or DLKA_AUG_I16 (int16: a float64 result is truncated towards zero, as numpy's astype does).
+ * dlka_augment_spatial   per sample b a float64 map maps[12 b ..] (rows of 4: src[d] = m[4d] g0 + m[4d+1] g1 + m[4d+2] g2 + m[4d+3] with
+ *              g[e] = index[e] - (out[e] - 1) / 2, formed in the lane: no coordinate grid is stored) and plain[4 b ..] = (flag, lb0, lb1, lb2):
+ *              flag != 0 copies the box at lb bit for bit (batchgenerators does not interpolate an unmodified sample).  order 0 / 1 read x;
+ *              order 3 reads coef, float64 B-spline coefficients [B*C][src + 2 pad], prepared by dlka_resample_spline_pad and
+ *              dlka_resample_spline_prefilter (mode DLKA_AUG_NEAREST, pad 12: scipy's rule) or dlka_augment_spline_prefilter_mirror
+ *              (DLKA_AUG_CONSTANT, pad 0).  The border rule is scipy.ndimage.map_coordinates': 'constant' gives cval wherever a coordinate
+ *              is < 0 or > n - 1, 'nearest' clamps the coordinate; taps and weights are scipy's, summed in its order in float64.
+ * dlka_augment_spatial_labels   int32 maps.  order 0: the nearest cell (cval outside).  order 1: batchgenerators' per-label rule in one
+ *              visit of the 8 neighbours: the largest label whose summed trilinear weight is >= 0.5, else 0; outside under 'constant'
+ *              every label's interpolant is cval, which must be < 0.5: 0.
+ * dlka_augment_gaussian   one axis of scipy.ndimage.gaussian_filter per launch: radius[ch] taps on either side (radius < 0: the channel is
+ *              copied) with the weights w[ch][0 .. radius] (centre first, DLKA_AUG_RADIUS_MAX + 1 per channel), mode 'reflect', float64 sums.
+ * dlka_augment_channel_stats   stats[4 ch ..] = (sum, sum of squares about the mean, min, max) in float64: lanes, waves, workgroups and the
+ *              finish kernel fold in a fixed order, so the result does not depend on scheduling.
+ * dlka_augment_pointwise   per channel up to DLKA_AUG_OPS_MAX steps ops[ch][k][6] = (code, p0 .. p4) applied in turn in float64, rounded to
+ *              the storage type after each; stats0 / stats1 are dlka_augment_channel_stats results the steps read.  flip[b] bit a: the store
+ *              index of spatial axis a is reversed (the mirror).  y must not be x.
+ * No atomics anywhere: results are bitwise reproducible.  Return codes: DLKA_ERR_NULL, DLKA_ERR_SHAPE, DLKA_ERR_DTYPE,
+ * DLKA_ERR_UNSUPPORTED (an order, mode or step code outside the lists, 2^31 cells or more per channel, more than 65535 channels, a radius
+ * above DLKA_AUG_RADIUS_MAX, cval >= 0.5 for order-1 labels), DLKA_ERR_WORKSPACE.  Nothing is launched before the checks pass. */
+#define DLKA_AUG_I16 3
+#define DLKA_AUG_CONSTANT 0
+#define DLKA_AUG_NEAREST 1
+#define DLKA_AUG_RADIUS_MAX 32
+#define DLKA_AUG_OPS_MAX 4
+enum {
+    DLKA_AUG_OP_NONE = 0,
+    DLKA_AUG_OP_NOISE = 1,      /* x + noise                                                                        */
+    DLKA_AUG_OP_SCALE_ADD = 2,  /* x * p0 + p1                                                                      */
+    DLKA_AUG_OP_CONTRAST = 3,   /* clip((x - mean0) * p0 + mean0, min0, max0)                                       */
+    DLKA_AUG_OP_GAMMA = 4,      /* s = p1 (+-1): s * (((s x - mn) / (range0 + 1e-7)) ^ p0 * range0 + mn), mn of s x   */
+    DLKA_AUG_OP_RETAIN = 5,     /* (x - mean1) / (std1 + 1e-8) * std0 + mean0, population std                       */
+    DLKA_AUG_OP_REPLACE = 6     /* x == p0 ? p1 : x                                                                 */
+};
+typedef struct dlka_augment_desc {
+    int32_t B, C, dtype, order, mode, pad;
+    int64_t src[3], out[3];
+    double cval;
+} dlka_augment_desc;
+int dlka_augment_spatial(const void *x, const double *coef, void *y, const dlka_augment_desc *d, const double *maps, const int32_t *plain,
+                         void *stream);
+int dlka_augment_spatial_labels(const int32_t *seg, int32_t *out, const dlka_augment_desc *d, const double *maps, const int32_t *plain,
+                                void *stream);
+int dlka_augment_spline_prefilter_mirror(double *coef, const int64_t *ext, int axis, void *stream);
+int dlka_augment_gaussian(const void *x, void *y, int dtype, int64_t channels, const int64_t *ext, int axis, const int32_t *radius,
+                          const double *weights, void *stream);
+size_t dlka_augment_stats_workspace_bytes(int64_t channels, int64_t cells);
+int dlka_augment_channel_stats(const void *x, double *stats, void *workspace, size_t workspace_bytes, int dtype, int64_t channels,
+                               int64_t cells, void *stream);
+int dlka_augment_pointwise(const void *x, const void *noise, void *y, int dtype, int64_t B, int64_t C, const int64_t *ext, const double *ops,
+                           const double *stats0, const double *stats1, const int32_t *flip, void *stream);
+/* Diagnostics: kernel launches so far (this process) of the entries above. */
+long dlka_augment_launch_count(void);
+
+/* =======================================================================================
  * Launch trace — measurement aid (no reference counterpart; the reference has no profiling hooks)
  * =======================================================================================
  * Between dlka_trace_start and dlka_trace_stop every kernel launch of the library is followed by a HIP timing event on the

@@ -1,0 +1,200 @@
+"""deformablelka_amd.augmentation (csrc/cl_augment.hip) on the wavefront emulator against the fixture recorded from the scipy restatement of the
+3-D trainer's transform chain (tests/golden/reference_augmentation.pt), and the host-side draws.  Cases, bounds and checks:
+tests/augmentation_cases.py."""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from tests import augmentation_cases as C
+
+from deformablelka_amd import augmentation as A  # (the feature: without it nothing here can run)
+
+
+@pytest.fixture(scope="module", autouse=True)
+def emu_backend():
+    from deformablelka_amd import _lib
+    from tests import emu
+    _lib._set_backend_for_tests(emu.load())
+    yield
+    _lib._set_backend_for_tests(None)
+
+
+FX = C.load_fixture()
+ids = lambda calls: [c[0] for c in calls]   # noqa: E731
+
+
+@pytest.mark.parametrize("call", C.SPATIAL_CALLS, ids=ids(C.SPATIAL_CALLS))
+def test_spatial_values_are_scipys(call):
+    C.check_spatial(FX, call, "cpu")
+
+
+@pytest.mark.parametrize("call", C.LABEL_CALLS, ids=ids(C.LABEL_CALLS))
+def test_spatial_labels_are_the_per_label_rule(call):
+    C.check_labels(FX, call, "cpu")
+
+
+def test_exact_halves_later_label_wins():
+    C.check_halves("cpu")
+
+
+@pytest.mark.parametrize("name", list(C.BLUR_SHAPES))
+@pytest.mark.parametrize("i", [0, 1])
+def test_gaussian_blur(name, i):
+    C.check_blur(FX, name, i, "cpu")
+
+
+def test_channel_statistics():
+    C.check_stats("cpu")
+
+
+@pytest.mark.parametrize("stage", C.POINT_STAGES)
+def test_pointwise_stage(stage):
+    C.check_point(FX, stage, "cpu")
+
+
+def test_mirror_every_subset_of_axes():
+    C.check_mirror("cpu")
+
+
+def test_deep_supervision_targets_equal_the_references():
+    C.check_ds(FX, "cpu")
+
+
+def test_pipeline_with_the_trainers_parameters():
+    C.check_pipeline(FX, "cpu")
+
+
+def test_pipeline_seeded_runs_are_bitwise_equal():
+    C.check_seeded_runs("cpu")
+
+
+def test_unsupported_arguments_raise():
+    C.check_unsupported("cpu")
+
+
+def test_containers_and_dtypes():
+    C.check_containers("cpu")
+
+
+def test_the_fixture_is_small_and_plain():
+    assert os.path.getsize(C.FIXTURE) < 2 ** 20
+
+    def plain(v):
+        if isinstance(v, dict):
+            return all(isinstance(k, (str, int)) and plain(x) for k, x in v.items())
+        if isinstance(v, (list, tuple)):
+            return all(plain(x) for x in v)
+        return v is None or isinstance(v, (torch.Tensor, str, int, float, bool))
+    assert plain(FX)
+
+
+def test_augmented_batches_feed_run_iteration():
+    """training.augmented_batches: (data, target) as run_iteration(..., loss_fn=initialize_loss()) takes them."""
+    from deformablelka_amd import training
+    data, seg, _ = C.pipeline_inputs()
+    aug = A.MoreDAAugmentation(C.PIPE_PATCH, C.pipeline_params(), deep_supervision_scales=C.DS_SCALES, seed=3)
+    loader = [{"data": data, "seg": seg}, {"data": data, "seg": seg}]
+    batches = list(training.augmented_batches(loader, aug))
+    assert len(batches) == 2
+    for d, t in batches:
+        assert d.dtype == torch.float32 and tuple(d.shape) == (2, 1) + C.PIPE_PATCH
+        assert isinstance(t, list) and len(t) == 3 and all(v.dtype == torch.float32 for v in t)
+
+
+# ---- the draws (host only) ----------------------------------------------------------------------------------------------------------------------
+def _rate(hits, n, p):
+    sigma = np.sqrt(p * (1 - p) / n)
+    assert abs(hits / n - p) <= 4 * sigma, f"rate {hits / n:.4f} is more than 4 sigma from {p}"
+
+
+def test_draw_spatial_rates_ranges_and_branches():
+    rs = np.random.RandomState(1)
+    r = 30. / 360 * 2. * np.pi
+    n = 4000
+    rec = A.draw_spatial(rs, (80, 160, 160), (64, 128, 128), n, do_rotation=True, angle_x=(-r, r), angle_y=(-r, r), angle_z=(-r, r),
+                         do_scale=True, scale=(0.7, 1.4), random_crop=False, p_scale_per_sample=0.2, p_rot_per_sample=0.2)
+    assert isinstance(rec, dict) and all(isinstance(v, np.ndarray) for v in rec.values())
+    rotated = np.abs(rec["angles"]).sum(1) > 0
+    scaled = rec["scale"][:, 0] != 1
+    _rate(rotated.sum(), n, 0.2)
+    _rate(scaled.sum(), n, 0.2)
+    _rate(rec["modified"].sum(), n, 0.36)
+    assert np.array_equal(rec["modified"], rotated | scaled)
+    assert np.abs(rec["angles"]).max() <= r and (rec["scale"] >= 0.7).all() and (rec["scale"] <= 1.4).all()
+    assert (rec["scale"][scaled] < 1).any() and (rec["scale"][scaled] > 1).any()                    # both branches of the factor
+    _rate((rec["scale"][scaled, 0] < 1).sum(), int(scaled.sum()), 0.5)
+    assert (rec["scale"][:, 0] == rec["scale"][:, 1]).all()
+    assert np.array_equal(rec["center"][rec["modified"]], np.tile([39.5, 79.5, 79.5], (int(rec["modified"].sum()), 1)))
+    assert np.array_equal(rec["crop_lb"][~rec["modified"]], np.tile([8, 16, 16], (int((~rec["modified"]).sum()), 1)))
+    b = int(np.argmax(rotated))
+    a = rec["angles"][b]
+    assert np.allclose(rec["rotation"][b], C.rotation(*a)) and np.allclose(rec["rotation"][b] @ rec["rotation"][b].T, np.identity(3))
+    per_axis = A.draw_spatial(rs, (80, 160, 160), (64, 128, 128), n, angle_x=(-r, r), angle_y=(-r, r), angle_z=(-r, r), do_scale=False,
+                              random_crop=False, p_rot_per_axis=0.5)
+    _rate((per_axis["angles"][:, 1] != 0).sum(), n, 0.5)
+    ind = A.draw_spatial(rs, (80, 160, 160), (64, 128, 128), 50, do_rotation=False, scale=(0.7, 1.4), independent_scale_for_each_axis=True,
+                         random_crop=True, patch_center_dist_from_border=[32, 64, 64])
+    assert (ind["scale"][:, 0] != ind["scale"][:, 1]).any()
+    assert (ind["center"] >= [32, 64, 64]).all() and (ind["center"] <= [48, 96, 96]).all()
+    with pytest.raises(NotImplementedError, match="do_elastic_deform"):
+        A.draw_spatial(rs, (8, 8, 8), (4, 4, 4), 1, do_elastic_deform=True)
+
+
+def test_draw_colour_rates_and_ranges():
+    rs = np.random.RandomState(2)
+    n = 4000
+    noise = A.draw_gaussian_noise(rs, n, (0, 0.1), 0.1)
+    _rate(noise["apply"].sum(), n, 0.1)
+    assert (noise["variance"] >= 0).all() and (noise["variance"] <= 0.1).all() and (noise["variance"][~noise["apply"]] == 0).all()
+    blur = A.draw_gaussian_blur(rs, n, 2, (0.5, 1.), True, 0.5, 0.2)
+    _rate(blur["apply"].sum(), n, 0.2)
+    on = blur["sigma"][blur["apply"]].reshape(-1)
+    _rate((on > 0).sum(), on.size, 0.5)
+    assert (on[on > 0] >= 0.5).all() and (on[on > 0] <= 1.0).all() and (blur["sigma"][~blur["apply"]] == 0).all()
+    bright = A.draw_brightness_multiplicative(rs, n, 2, (0.75, 1.25), True, 0.15)
+    _rate(bright["apply"].sum(), n, 0.15)
+    m = bright["multiplier"][bright["apply"]]
+    assert (m >= 0.75).all() and (m <= 1.25).all() and (bright["multiplier"][~bright["apply"]] == 1).all()
+    add = A.draw_brightness_additive(rs, n, 2, 0.0, 0.1, True, 0.15, 0.5)
+    _rate(add["apply"].sum(), n, 0.15)
+    contrast = A.draw_contrast(rs, n, 2, (0.75, 1.25), True, 0.15)
+    _rate(contrast["apply"].sum(), n, 0.15)
+    f = contrast["factor"][contrast["apply"]]
+    assert (f >= 0.75).all() and (f <= 1.25).all() and (f < 1).any() and (f > 1).any()
+    low = A.draw_linear_downsampling_scipy(rs, n, 2, (0.5, 1), True, 0.5, 0.25)
+    _rate(low["apply"].sum(), n, 0.25)
+    z = low["zoom"][low["apply"]].reshape(-1)
+    _rate((z > 0).sum(), z.size, 0.5)
+    assert (z[z > 0] >= 0.5).all() and (z[z > 0] <= 1).all()
+    gamma = A.draw_gamma(rs, n, 2, (0.7, 1.5), True, 0.3)
+    _rate(gamma["apply"].sum(), n, 0.3)
+    g = gamma["gamma"][gamma["apply"]]
+    assert (g >= 0.7).all() and (g <= 1.5).all() and (g < 1).any() and (g > 1).any()
+    mirror = A.draw_mirroring(rs, n, (0, 1, 2))
+    for a in range(3):
+        _rate(mirror["flip"][:, a].sum(), n, 0.5)
+    assert not A.draw_mirroring(rs, 100, (1,))["flip"][:, [0, 2]].any()
+    for rec in (noise, blur, bright, add, contrast, low, gamma, mirror):
+        assert isinstance(rec, dict) and all(isinstance(v, np.ndarray) for v in rec.values())
+
+
+def test_pipeline_draw_is_the_chain_in_order():
+    aug = A.MoreDAAugmentation(C.PIPE_PATCH, C.pipeline_params(), seed=7)
+    rec = aug.draw(2, C.PIPE_SRC[2:], 1)
+    assert list(rec) == ["spatial", "noise", "blur", "brightness", "contrast", "lowres", "gamma_inverted", "gamma", "mirror"]
+    again = A.MoreDAAugmentation(C.PIPE_PATCH, C.pipeline_params(), seed=7).draw(2, C.PIPE_SRC[2:], 1)
+    assert all(np.array_equal(rec[k][f], again[k][f]) for k in rec for f in rec[k])
+    extra = A.MoreDAAugmentation(C.PIPE_PATCH, dict(C.pipeline_params(), do_additive_brightness=True), seed=7).draw(2, C.PIPE_SRC[2:], 1)
+    assert list(extra)[4] == "additive"
+
+
+def test_restatement_blur_weights_are_scipys():
+    """The product's weight table is scipy's gaussian_filter1d kernel, bit for bit."""
+    pytest.importorskip("scipy")
+    from scipy.ndimage import _filters
+    for sigma in (0.5, 0.77, 1.0):
+        radius, w = A._gaussian_weights(sigma)
+        ref = _filters._gaussian_kernel1d(sigma, 0, radius)
+        assert radius == int(4.0 * sigma + 0.5) and np.array_equal(w, ref[radius:])
