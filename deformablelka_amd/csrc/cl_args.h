@@ -77,12 +77,12 @@ struct WgradArgs {
     const float *samp;  // AMODE 1, optional: [K][M][Cin] samples (fp32; bf16 when act_bf16) stored by cl_deform_goff2_kernel (DeformBwdArgs::samp) — no gather
     int samp_f16;       // fp32 activations only: the samples are IEEE halves (DeformBwdArgs::samp_f16)
     int samp_b16mfma;   // ... and the contraction runs on the bf16 matrix cores with two-term operands (DLKA_SAMP_B16MFMA, A/B)
-    float *part;        // [chunks][K][CoutP][Cin] partial weight-gradient tiles, followed by [chunks][CoutP] partial bias sums
+    float *part;        // [sets][K][CoutP][Cin] partial weight-gradient tiles, followed by [sets][CoutP] partial bias sums; sets = workgroups along M (cl_wgrad_pick_chunks)
     float *bpart;       // = part + chunks*K*CoutP*Cin when the bias gradient is wanted, else null (set by the launcher)
     int B, D, H, W, N, M;
     int Cin, Cout, CoutP;
     int kd, kh, kw, pd, ph, pw, dd, dh, dw, K;
-    int rows_per_chunk;  // multiple of 32
+    int rows_per_chunk;  // multiple of 32: the rows ONE WAVE walks (a workgroup of WV waves covers WV consecutive chunks)
     int act_bf16;        // 1: `in` (and a channels-last `g`) are bf16 storage; a planar `g` (grad_offset) stays fp32
     int CT;              // Cin / 32
     int w16;             // set by the launcher: W % 16 == 0 (fast row addressing in cl_wgrad_dense_kernel)

@@ -11,6 +11,10 @@
 // One wave (64-thread workgroup) owns one 32(co) x 32(ci) output tile for TPW taps and walks a chunk of rows, 32 at a
 // time: MFMA A operand = G^T (lane i = co), B operand = A(m,tap,ci) (lane j = ci), k = 32 rows per step pair.
 // Partial sums per row-chunk go to a workspace and are folded by cl_wgrad_reduce_kernel (no same-address atomics).
+//
+// Workgroups of WV waves: the waves of a workgroup own the SAME tiles over WV consecutive row chunks; their accumulator tiles meet in LDS
+// (wg_sum_tiles) and the workgroup stores ONE partial tile set — the workspace and the fold see 1/WV of the chunks.  DLKA_WGRAD_WAVES=1 keeps
+// one-wave workgroups (wgrad_plan).
 #include <stdlib.h>
 
 #include "deform_sample.h"
@@ -20,21 +24,69 @@
 
 namespace dlka {
 
+// waves per workgroup of the weight-gradient kernels (compile-time per family, so that a variant can be built for an A/B run)
+#ifndef DLKA_WGRAD_W_DENSE
+#define DLKA_WGRAD_W_DENSE 4   // 3x3 dense (offset conv): one wave per SIMD, one workgroup per CU
+#endif
+#ifndef DLKA_WGRAD_W_SAMP
+#define DLKA_WGRAD_W_SAMP 4    // deformable conv, stored samples and gather
+#endif
+#ifndef DLKA_WGRAD_W_PW
+#define DLKA_WGRAD_W_PW 4      // pointwise (K = 1)
+#endif
+
+// Sum of the accumulator tiles (and bias sums) of the WV waves of a workgroup, pairwise through LDS in a fixed order: ((w0 + w1) + (w2 + w3)) + ...
+// Round s: the waves with (wave mod 2s) == s put their tiles into slot wave / 2s, the waves with (wave mod 2s) == 0 add them.  Wave 0 ends with the
+// total.  EVERY wave of the workgroup calls this (a wave without rows contributes its zeros): the barriers are unconditional.  No atomics, so the
+// result does not depend on the order in which the waves arrive.  red: (WV / 2) * (NT * 1024 + NB * 64) floats of LDS.
+template <int WV, int NT, int NB>
+__device__ __forceinline__ void wg_sum_tiles(f32x16 *acc, float *bs, float *red, const int wave, const int lane)
+{
+    constexpr int SLOT = NT * 1024 + NB * 64;
+#pragma unroll
+    for (int s = 1; s < WV; s *= 2) {
+        if (s > 1) __syncthreads();   // the previous round's slots have been read
+        float *slot = red + (wave / (2 * s)) * SLOT + lane;
+        if ((wave & (2 * s - 1)) == s) {
+#pragma unroll
+            for (int t = 0; t < NT; ++t)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) slot[t * 1024 + r * 64] = acc[t][r];
+#pragma unroll
+            for (int c = 0; c < NB; ++c) slot[NT * 1024 + c * 64] = bs[c];
+        }
+        __syncthreads();
+        if ((wave & (2 * s - 1)) == 0) {
+#pragma unroll
+            for (int t = 0; t < NT; ++t)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[t][r] += slot[t * 1024 + r * 64];
+#pragma unroll
+            for (int c = 0; c < NB; ++c) bs[c] += slot[NT * 1024 + c * 64];
+        }
+    }
+}
+template <int WV, int NT, int NB> struct WgSumLds { static constexpr int FLOATS = WV > 1 ? (WV / 2) * (NT * 1024 + NB * 64) : 1; };
+
 // ---------------------------------------------------------------------------------------------------------------------
 // Deformable weight gradient, second generation: the sample tile of each tap is gathered in the line-friendly layout of
 // cl_gather.h (8 whole 128-byte rows per load instruction), interpolated, and written to a wave-private LDS tile from
 // which the MFMA B operand is read; the corner loads of tap t+1 are in flight under the MFMAs of tap t.
 //     gW[co][ci][tap] = sum_m G[m][co] * S(m, tap, ci)
-// One wave = one 32(co) x 32(ci) tile x TPW taps over a chunk of rows.
+// One wave = one 32(co) x 32(ci) tile x TPW taps over a chunk of rows; the WV waves of a workgroup (own sample tiles and description table each) meet in wg_sum_tiles.
 // ---------------------------------------------------------------------------------------------------------------------
-template <int TPW, typename T = float>   // T: storage of `in` and `g` (both channels-last)
-__global__ __launch_bounds__(64) void cl_wgrad_deform_kernel(WgradArgs p)
+template <int TPW, typename T = float, int WV = 1>   // T: storage of `in` and `g` (both channels-last)
+__global__ __launch_bounds__(64 * WV) void cl_wgrad_deform_kernel(WgradArgs p)
 {
     constexpr unsigned XB = sizeof(T);
     constexpr int SROW = 36;
-    __shared__ __attribute__((aligned(16))) float Ssm[2][32 * SROW];
-    __shared__ __attribute__((aligned(16))) float Dt[32 * GATHER_DESC_WORDS];
-    const int lane = threadIdx.x, i = lane & 31, h = lane >> 5;
+    __shared__ __attribute__((aligned(16))) float Ssm_[WV][2][32 * SROW];
+    __shared__ __attribute__((aligned(16))) float Dt_[WV][32 * GATHER_DESC_WORDS];
+    __shared__ float red[WgSumLds<WV, TPW, 1>::FLOATS];
+    const int wave = wave_uniform((int)threadIdx.x >> 6);
+    float (*Ssm)[32 * SROW] = Ssm_[wave];
+    float *Dt = Dt_[wave];
+    const int lane = threadIdx.x & 63, i = lane & 31, h = lane >> 5;
     using GG = GatherGeom<T>;
     const int gr = lane >> GG::PSHIFT, gp = lane & ((1 << GG::PSHIFT) - 1);
     int chunk = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
@@ -59,7 +111,7 @@ __global__ __launch_bounds__(64) void cl_wgrad_deform_kernel(WgradArgs p)
         for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
     float bsum = 0.f;
 
-    const int m_lo = chunk * p.rows_per_chunk;
+    const int m_lo = (chunk * WV + wave) * p.rows_per_chunk;   // (at or past M: a wave without rows)
     const int m_hi = min(p.M, m_lo + p.rows_per_chunk);
     GatherPiece<T> xr[GG::NG][8];
     RowLook rd[GG::NG];
@@ -129,6 +181,8 @@ __global__ __launch_bounds__(64) void cl_wgrad_deform_kernel(WgradArgs p)
             for (int s = 0; s < 16; ++s) acc[t] = mfma_32x32x2(ga[s], srow[s * SROW], acc[t]);
         }
     }
+    wg_sum_tiles<WV, TPW, 1>(acc, &bsum, red, wave, lane);
+    if (wave != 0) return;
 #pragma unroll
     for (int t = 0; t < TPW; ++t) {
         const int tap = tap0 + t;
@@ -154,14 +208,16 @@ __global__ __launch_bounds__(64) void cl_wgrad_deform_kernel(WgradArgs p)
 // ---------------------------------------------------------------------------------------------------------------------
 // S16 (T = float only, round 6): the samples are IEEE halves (WgradArgs::samp_f16) — half the bytes this HBM-bound stream reads; grad_out, the products (fp32-input MFMA on the
 // widened sample) and the accumulation stay fp32.
-template <int TPW, typename T = float, bool S16 = false, bool B16M = false>   // T: storage of the channels-last `g`; B16M (S16 only): the contraction on the bf16 matrix cores
-__global__ __launch_bounds__(64, 2) void cl_wgrad_samp_kernel(WgradArgs p)
+template <int TPW, typename T = float, bool S16 = false, bool B16M = false, int WV = 1>   // T: storage of the channels-last `g`; B16M (S16 only): the contraction on the bf16 matrix cores
+__global__ __launch_bounds__(64 * WV, 2) void cl_wgrad_samp_kernel(WgradArgs p)
 {
+    __shared__ float red[WgSumLds<WV, TPW, 1>::FLOATS];
+    const int wave = wave_uniform((int)threadIdx.x >> 6);
     static_assert(!B16M || S16, "B16M is a variant of the half-sample kernel");
     static_assert(!S16 || sizeof(T) == 4, "half samples belong to the fp32 path");
     constexpr unsigned XB = sizeof(T);
     constexpr unsigned SB = S16 ? 2u : XB;   // bytes of a stored sample
-    const int lane = threadIdx.x, i = lane & 31, h = lane >> 5;
+    const int lane = threadIdx.x & 63, i = lane & 31, h = lane >> 5;
     int chunk = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
     if (p.xcd_total) {
         const int r = xcd_item(blockIdx.x, p.xcd_total);
@@ -181,7 +237,7 @@ __global__ __launch_bounds__(64, 2) void cl_wgrad_samp_kernel(WgradArgs p)
         for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
     float bsum = 0.f;
 
-    const int m_lo = chunk * p.rows_per_chunk;
+    const int m_lo = (chunk * WV + wave) * p.rows_per_chunk;   // (at or past M: a wave without rows)
     const int m_hi = min(p.M, m_lo + p.rows_per_chunk);
     // register ring of RAW loaded words: any conversion (bf16 half -> float) happens at compute time — a conversion next to its load makes the
     // compiler wait for that load on the spot, which serialises the prefetch (measured: 96 instead of 60 us with 2-byte loads converted at once)
@@ -278,6 +334,8 @@ __global__ __launch_bounds__(64, 2) void cl_wgrad_samp_kernel(WgradArgs p)
             compute(1);
         }
     }
+    wg_sum_tiles<WV, TPW, 1>(acc, &bsum, red, wave, lane);
+    if (wave != 0) return;
 #pragma unroll
     for (int t = 0; t < TPW; ++t) {
         const int tap = tap0 + t;
@@ -304,12 +362,14 @@ __global__ __launch_bounds__(64, 2) void cl_wgrad_samp_kernel(WgradArgs p)
 // of 144 x 64 for the 3 x 3 blocking.
 // T: storage of `in` and of a channels-last `g` (GMODE 0); a planar `g` (GMODE 1: grad_offset) is always fp32.  A bf16 `in` is its own high
 // term, so the split contraction drops the b_lo product.
-template <int GMODE, int COT, int TPW, bool N16, bool SPLIT, typename T, bool PAD = false>   // N16: N % 16 == 0 (the 16 rows of a half-wave never straddle two volumes)
+template <int GMODE, int COT, int TPW, bool N16, bool SPLIT, typename T, bool PAD = false, int WV = 1>   // N16: N % 16 == 0 (the 16 rows of a half-wave never straddle two volumes)
 __device__ __forceinline__ void wgrad_dense_body(const WgradArgs &p, const int bz_in)
 {
     constexpr unsigned XB = sizeof(T), GB = GMODE == 0 ? sizeof(T) : 4u;
     constexpr bool B16 = sizeof(T) == 2;
-    const int lane = threadIdx.x, i = lane & 31, h = lane >> 5;
+    __shared__ float red[WgSumLds<WV, COT * TPW, COT>::FLOATS];
+    const int wave = wave_uniform((int)threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63, i = lane & 31, h = lane >> 5;
     int chunk = blockIdx.x, by = blockIdx.y, bz = bz_in;
     if (p.xcd_total) {   // XCD-swizzled 1-D grid (see cl_wgrad_deform_kernel)
         const int r = xcd_item(blockIdx.x, p.xcd_total);
@@ -342,7 +402,7 @@ __device__ __forceinline__ void wgrad_dense_body(const WgradArgs &p, const int b
         oh[t] = ((tap / p.kw) % p.kh) * p.dh - p.ph;
         ow[t] = (tap % p.kw) * p.dw - p.pw;
     }
-    const int m_lo = chunk * p.rows_per_chunk;
+    const int m_lo = (chunk * WV + wave) * p.rows_per_chunk;   // (at or past M: a wave without rows)
     const int m_hi = min(p.M, m_lo + p.rows_per_chunk);
 
     float ga_n[COT][16], bv_n[TPW][16];
@@ -599,6 +659,8 @@ __device__ __forceinline__ void wgrad_dense_body(const WgradArgs &p, const int b
         }
     }
     // ---- partial tiles out: D row = co_local, col = ci_local ----
+    wg_sum_tiles<WV, COT * TPW, COT>(&acc[0][0], bsum, red, wave, lane);
+    if (wave != 0) return;
 #pragma unroll
     for (int c = 0; c < COT; ++c) {
         const int ot = otg * COT + c;
@@ -621,17 +683,17 @@ __device__ __forceinline__ void wgrad_dense_body(const WgradArgs &p, const int b
     }
 }
 
-template <int GMODE, int COT, int TPW, bool N16, bool SPLIT = false, typename T = float>
-__global__ __launch_bounds__(64) void cl_wgrad_dense_kernel(WgradArgs p)
+template <int GMODE, int COT, int TPW, bool N16, bool SPLIT = false, typename T = float, int WV = 1>
+__global__ __launch_bounds__(64 * WV) void cl_wgrad_dense_kernel(WgradArgs p)
 {
-    wgrad_dense_body<GMODE, COT, TPW, N16, SPLIT, T>(p, blockIdx.z);
+    wgrad_dense_body<GMODE, COT, TPW, N16, SPLIT, T, false, WV>(p, blockIdx.z);
 }
 
 // the same from the zero-padded copy of the input (WgradArgs::pad): planar fp32 grad_out, split contraction, three taps per wave
-template <int COT, bool N16, typename T>
-__global__ __launch_bounds__(64) void cl_wgrad_dense_pad_kernel(WgradArgs p)
+template <int COT, bool N16, typename T, int WV = 1>
+__global__ __launch_bounds__(64 * WV) void cl_wgrad_dense_pad_kernel(WgradArgs p)
 {
-    wgrad_dense_body<1, COT, 3, N16, true, T, true>(p, blockIdx.z);
+    wgrad_dense_body<1, COT, 3, N16, true, T, true, WV>(p, blockIdx.z);
 }
 
 // out[b][d + lo_d][h + lo_h][w + lo_w][c] = in[b][d][h][w][c], zeros around.  One workgroup per OUTPUT w-row (b, dp, hp): the row's coordinates are decoded once
@@ -664,10 +726,10 @@ __global__ __launch_bounds__(256) void cl_pad_copy_kernel(const T *__restrict__ 
 // The three pointwise weight gradients of a D-LKA block (proj_2, conv1, proj_1: same geometry, different operands) in ONE
 // launch, blockIdx.z = job: every dependent kernel node costs ~4.5 us inside the graph, and each of these is a ~1 us kernel.
 struct WgradArgs3 { WgradArgs a[3]; };
-template <int COT, bool N16, typename T = float>
-__global__ __launch_bounds__(64) void cl_wgrad_pw3_kernel(WgradArgs3 b)
+template <int COT, bool N16, typename T = float, int WV = 1>
+__global__ __launch_bounds__(64 * WV) void cl_wgrad_pw3_kernel(WgradArgs3 b)
 {
-    wgrad_dense_body<0, COT, 1, N16, false, T>(b.a[blockIdx.z], 0);
+    wgrad_dense_body<0, COT, 1, N16, false, T, false, WV>(b.a[blockIdx.z], 0);
 }
 
 // gW[co][ci][tap] (reference layout, storage type T) = sum_chunk part[chunk][tap][co][ci];  gb[co] = sum_chunk bpart[chunk][co]
@@ -709,7 +771,16 @@ __global__ __launch_bounds__(256) void cl_wgrad_reduce_kernel(const float *__res
 
 // Work decomposition.  Waves = chunks x (co-tile groups x ci-tiles) x tap groups; aim at ~2 waves per SIMD over the chip
 // so that small outputs (a 32x32 pointwise gradient is ONE tile) still get their parallelism from the row dimension.
-struct WgradPlan { int chunks, tpw, cot; };
+// chunks: row chunks = waves along M (as before the multi-wave workgroups); waves: waves per workgroup — cdiv(row chunks, waves) partial tile sets
+struct WgradPlan { int chunks, tpw, cot, waves; };
+
+// DLKA_WGRAD_WAVES=1: one-wave workgroups everywhere (one partial tile set per row chunk).  Read per call, not cached: a test toggles it; the size
+// queries and the launchers both come through wgrad_plan(), so a query and a launch made under the same setting agree.
+static bool wgrad_one_wave()
+{
+    const char *e = getenv("DLKA_WGRAD_WAVES");
+    return e && atoi(e) == 1;
+}
 
 static WgradPlan wgrad_plan(int M, int K, int Cout, int Cin, int amode)
 {
@@ -740,19 +811,24 @@ static WgradPlan wgrad_plan(int M, int K, int Cout, int Cin, int amode)
     if (chunks > 1024) chunks = 1024;
     if (chunks < 1) chunks = 1;
     pl.chunks = chunks;
+    pl.waves = wgrad_one_wave() ? 1 : (amode == 1 ? DLKA_WGRAD_W_SAMP : (K == 1 ? DLKA_WGRAD_W_PW : DLKA_WGRAD_W_DENSE));
     return pl;
 }
 
-int cl_wgrad_pick_chunks(int M, int K, int Cout, int Cin, int amode) { return wgrad_plan(M, K, Cout, Cin, amode).chunks; }
+// rows a wave walks, and the workgroups along M (= partial tile sets) of a plan
+static int wgrad_rows_per_chunk(int M, const WgradPlan &pl) { return cdiv(cdiv(M, 32), pl.chunks) * 32; }
+static int wgrad_part_sets(int M, const WgradPlan &pl) { return cdiv(cdiv(M, wgrad_rows_per_chunk(M, pl)), pl.waves); }
+
+int cl_wgrad_pick_chunks(int M, int K, int Cout, int Cin, int amode) { return wgrad_part_sets(M, wgrad_plan(M, K, Cout, Cin, amode)); }
 
 size_t cl_wgrad_part_floats_mode(int M, int K, int Cout, int Cin, int amode)
 {
-    return (size_t)wgrad_plan(M, K, Cout, Cin, amode).chunks * ((size_t)K * round_up(Cout, 32) * Cin + round_up(Cout, 32));
+    return (size_t)cl_wgrad_pick_chunks(M, K, Cout, Cin, amode) * ((size_t)K * round_up(Cout, 32) * Cin + round_up(Cout, 32));
 }
 
 size_t cl_wgrad_part_floats(int M, int K, int Cout, int Cin)
 {
-    const int c0 = wgrad_plan(M, K, Cout, Cin, 0).chunks, c1 = wgrad_plan(M, K, Cout, Cin, 1).chunks;
+    const int c0 = cl_wgrad_pick_chunks(M, K, Cout, Cin, 0), c1 = cl_wgrad_pick_chunks(M, K, Cout, Cin, 1);
     return (size_t)(c0 > c1 ? c0 : c1) * ((size_t)K * round_up(Cout, 32) * Cin + round_up(Cout, 32));
 }
 
@@ -766,9 +842,9 @@ template <typename T>
 int launch_cl_wgrad(int amode, int gmode, WgradArgs a, T *gw, T *gb, hipStream_t st, FinalizeJob *defer)
 {
     const WgradPlan pl = wgrad_plan(a.M, a.K, a.Cout, a.Cin, amode);
-    const int tiles = cdiv(a.M, 32);
-    a.rows_per_chunk = cdiv(tiles, pl.chunks) * 32;
-    const int nchunks = cdiv(a.M, a.rows_per_chunk);
+    a.rows_per_chunk = wgrad_rows_per_chunk(a.M, pl);
+    const int nchunks = wgrad_part_sets(a.M, pl);   // workgroups along M: pl.waves row chunks each, one partial tile set each
+    const bool wg = pl.waves > 1;
     a.CoutP = round_up(a.Cout, 32);
     a.CT = a.Cin / 32;
     constexpr bool slow_addr = false;
@@ -777,7 +853,7 @@ int launch_cl_wgrad(int amode, int gmode, WgradArgs a, T *gw, T *gb, hipStream_t
     const int OT = a.CoutP / 32;
     if ((long)a.M * a.Cin * 4 >= (1l << 31) || (long)a.M * a.Cout * 4 >= (1l << 31)) return DLKA_ERR_UNSUPPORTED;   // 32-bit buffer offsets
     a.bpart = gb ? a.part + (size_t)nchunks * a.K * a.CoutP * a.Cin : nullptr;
-    dim3 block(64);
+    dim3 block(64 * pl.waves);
     if (amode == 1) {
         if (gmode != 0 || a.K == 1) return DLKA_ERR_UNSUPPORTED;
         dim3 grid(nchunks, OT * a.CT, cdiv(a.K, pl.tpw));
@@ -788,17 +864,25 @@ int launch_cl_wgrad(int amode, int gmode, WgradArgs a, T *gw, T *gb, hipStream_t
         }
         if (a.samp) {   // samples stored by the grad_offset kernel: dense stream, no gather
             if (pl.tpw != 3 || (long)a.K * a.M * a.Cin * (a.act_bf16 ? 2 : 4) >= (1l << 31)) return DLKA_ERR_UNSUPPORTED;   // 32-bit buffer offsets below DLKA_OOB
-            if (a.act_bf16) { auto k = cl_wgrad_samp_kernel<3, bf16_t>; DLKA_LAUNCH(k, grid, block, 0, st, a); }
-            else if (a.samp_f16 && a.samp_b16mfma) { auto k = cl_wgrad_samp_kernel<3, float, true, true>; DLKA_LAUNCH(k, grid, block, 0, st, a); }
-            else if (a.samp_f16) { auto k = cl_wgrad_samp_kernel<3, float, true>; DLKA_LAUNCH(k, grid, block, 0, st, a); }
-            else { auto k = cl_wgrad_samp_kernel<3>; DLKA_LAUNCH(k, grid, block, 0, st, a); }
+            constexpr int WS = DLKA_WGRAD_W_SAMP;
+#define DLKA_WGS(...)                                                                                                     \
+    {                                                                                                                     \
+        if (wg) { auto k = cl_wgrad_samp_kernel<3, __VA_ARGS__, WS>; DLKA_LAUNCH(k, grid, block, 0, st, a); }             \
+        else { auto k = cl_wgrad_samp_kernel<3, __VA_ARGS__, 1>; DLKA_LAUNCH(k, grid, block, 0, st, a); }                 \
+    }
+            if (a.act_bf16) DLKA_WGS(bf16_t, false, false)
+            else if (a.samp_f16 && a.samp_b16mfma) DLKA_WGS(float, true, true)
+            else if (a.samp_f16) DLKA_WGS(float, true, false)
+            else DLKA_WGS(float, false, false)
+#undef DLKA_WGS
         }
+        else if (pl.tpw != 3) return DLKA_ERR_UNSUPPORTED;   // (4 and 7 taps per wave measured slower: more registers, fewer waves)
         else if (a.act_bf16) {
-            if (pl.tpw != 3) return DLKA_ERR_UNSUPPORTED;
-            auto k = cl_wgrad_deform_kernel<3, bf16_t>; DLKA_LAUNCH(k, grid, block, 0, st, a);
+            if (wg) { auto k = cl_wgrad_deform_kernel<3, bf16_t, DLKA_WGRAD_W_SAMP>; DLKA_LAUNCH(k, grid, block, 0, st, a); }
+            else { auto k = cl_wgrad_deform_kernel<3, bf16_t, 1>; DLKA_LAUNCH(k, grid, block, 0, st, a); }
         }
-        else if (pl.tpw == 3) { auto k = cl_wgrad_deform_kernel<3>; DLKA_LAUNCH(k, grid, block, 0, st, a); }
-        else return DLKA_ERR_UNSUPPORTED;   // (4 and 7 taps per wave measured slower: more registers, fewer waves)
+        else if (wg) { auto k = cl_wgrad_deform_kernel<3, float, DLKA_WGRAD_W_SAMP>; DLKA_LAUNCH(k, grid, block, 0, st, a); }
+        else { auto k = cl_wgrad_deform_kernel<3, float, 1>; DLKA_LAUNCH(k, grid, block, 0, st, a); }
     } else {
         dim3 grid(nchunks, cdiv(OT, pl.cot) * a.CT, cdiv(a.K, pl.tpw));
         static const bool no_xcd2 = getenv("DLKA_NO_XCD_SWIZZLE") != nullptr;
@@ -809,11 +893,16 @@ int launch_cl_wgrad(int amode, int gmode, WgradArgs a, T *gw, T *gb, hipStream_t
         static const bool exact = getenv("DLKA_EXACT_FP32") != nullptr;
         const bool split = !exact && a.K > 1;   // MFMA-bound contractions: bf16 x3 split (see cl_igemm.hip)
         if (a.g_cpad && !((a.N & 15) == 0 && split && gmode == 1)) return DLKA_ERR_UNSUPPORTED;   // packed g: split + N16 variant only
+        // (WV: the family's waves per workgroup, or 1 under DLKA_WGRAD_WAVES=1)
+#define DLKA_WG_W(GM, CO, TP, WV)                                                                                \
+    {                                                                                                            \
+        if ((a.N & 15) == 0 && split) { auto k = cl_wgrad_dense_kernel<GM, CO, TP, true, true, float, WV>; DLKA_LAUNCH(k, grid, block, 0, st, a); }  \
+        else if ((a.N & 15) == 0) { auto k = cl_wgrad_dense_kernel<GM, CO, TP, true, false, float, WV>; DLKA_LAUNCH(k, grid, block, 0, st, a); }  \
+        else { auto k = cl_wgrad_dense_kernel<GM, CO, TP, false, false, float, WV>; DLKA_LAUNCH(k, grid, block, 0, st, a); }              \
+    }
 #define DLKA_WG(GM, CO, TP)                                                                                      \
     {                                                                                                            \
-        if ((a.N & 15) == 0 && split) { auto k = cl_wgrad_dense_kernel<GM, CO, TP, true, true>; DLKA_LAUNCH(k, grid, block, 0, st, a); }  \
-        else if ((a.N & 15) == 0) { auto k = cl_wgrad_dense_kernel<GM, CO, TP, true>; DLKA_LAUNCH(k, grid, block, 0, st, a); }  \
-        else { auto k = cl_wgrad_dense_kernel<GM, CO, TP, false>; DLKA_LAUNCH(k, grid, block, 0, st, a); }              \
+        if (!wg) DLKA_WG_W(GM, CO, TP, 1) else if (a.K == 1) DLKA_WG_W(GM, CO, TP, DLKA_WGRAD_W_PW) else DLKA_WG_W(GM, CO, TP, DLKA_WGRAD_W_DENSE)   \
     }
         if (a.pad && a.K > 1 && gmode == 1 && split && !a.g_cpad && pl.tpw == 3 && (a.Cin * (a.act_bf16 ? 2 : 4)) % 16 == 0 &&
             cl_wgrad_pad_bytes(a.B, a.D, a.H, a.W, a.Cin, a.kd, a.kh, a.kw, a.dd, a.dh, a.dw, a.act_bf16) < ((size_t)1 << 31)) {
@@ -831,23 +920,33 @@ int launch_cl_wgrad(int amode, int gmode, WgradArgs a, T *gw, T *gb, hipStream_t
             }
             DLKA_CHECK_LAUNCH();
             const bool n16 = (a.N & 15) == 0;
+#define DLKA_WGP_W(CO, T_, WV)                                                                                             \
+    {                                                                                                                      \
+        if (n16) { auto k = cl_wgrad_dense_pad_kernel<CO, true, T_, WV>; DLKA_LAUNCH(k, grid, block, 0, st, a); }          \
+        else { auto k = cl_wgrad_dense_pad_kernel<CO, false, T_, WV>; DLKA_LAUNCH(k, grid, block, 0, st, a); }             \
+    }
 #define DLKA_WGP(CO, T_)                                                                                                   \
     {                                                                                                                      \
-        if (n16) { auto k = cl_wgrad_dense_pad_kernel<CO, true, T_>; DLKA_LAUNCH(k, grid, block, 0, st, a); }              \
-        else { auto k = cl_wgrad_dense_pad_kernel<CO, false, T_>; DLKA_LAUNCH(k, grid, block, 0, st, a); }                 \
+        if (wg) DLKA_WGP_W(CO, T_, DLKA_WGRAD_W_DENSE) else DLKA_WGP_W(CO, T_, 1)                                          \
     }
             if (a.act_bf16) { if (pl.cot == 3) DLKA_WGP(3, bf16_t) else if (pl.cot == 2) DLKA_WGP(2, bf16_t) else DLKA_WGP(1, bf16_t) }
             else { if (pl.cot == 3) DLKA_WGP(3, float) else if (pl.cot == 2) DLKA_WGP(2, float) else DLKA_WGP(1, float) }
 #undef DLKA_WGP
+#undef DLKA_WGP_W
         } else if (a.act_bf16) {   // DLKA_BF16 token path: only the offset-predict conv's weight gradient comes through here (planar fp32 g, bf16 in)
             if (a.K == 1 || gmode != 1 || !split || a.g_cpad || pl.tpw != 3) return DLKA_ERR_UNSUPPORTED;
+#define DLKA_WGB_W(CO, WV)                                                                                                                     \
+    {                                                                                                                                          \
+        if ((a.N & 15) == 0) { auto k = cl_wgrad_dense_kernel<1, CO, 3, true, true, bf16_t, WV>; DLKA_LAUNCH(k, grid, block, 0, st, a); }    \
+        else { auto k = cl_wgrad_dense_kernel<1, CO, 3, false, true, bf16_t, WV>; DLKA_LAUNCH(k, grid, block, 0, st, a); }                   \
+    }
 #define DLKA_WGB(CO)                                                                                                                           \
     {                                                                                                                                          \
-        if ((a.N & 15) == 0) { auto k = cl_wgrad_dense_kernel<1, CO, 3, true, true, bf16_t>; DLKA_LAUNCH(k, grid, block, 0, st, a); }    \
-        else { auto k = cl_wgrad_dense_kernel<1, CO, 3, false, true, bf16_t>; DLKA_LAUNCH(k, grid, block, 0, st, a); }                   \
+        if (wg) DLKA_WGB_W(CO, DLKA_WGRAD_W_DENSE) else DLKA_WGB_W(CO, 1)                                                                      \
     }
             if (pl.cot == 3) DLKA_WGB(3) else if (pl.cot == 2) DLKA_WGB(2) else DLKA_WGB(1)
 #undef DLKA_WGB
+#undef DLKA_WGB_W
         } else if (a.K == 1) {
             if (gmode != 0) return DLKA_ERR_UNSUPPORTED;
             if (pl.cot == 2) DLKA_WG(0, 2, 1) else DLKA_WG(0, 1, 1)
@@ -858,6 +957,7 @@ int launch_cl_wgrad(int amode, int gmode, WgradArgs a, T *gw, T *gb, hipStream_t
             if (pl.cot == 3) DLKA_WG(0, 3, 3) else if (pl.cot == 2) DLKA_WG(0, 2, 3) else DLKA_WG(0, 1, 3)
         }
 #undef DLKA_WG
+#undef DLKA_WG_W
     }
     DLKA_CHECK_LAUNCH();
     const long n = (long)a.K * a.Cout * a.Cin + (gb ? a.Cout : 0);
@@ -881,9 +981,9 @@ int launch_cl_wgrad_pw3(const WgradArgs *jobs, float *const *gw, float *const *g
     const WgradArgs &a0 = jobs[0];
     if (a0.K != 1) return DLKA_ERR_UNSUPPORTED;
     const WgradPlan pl = wgrad_plan(a0.M, 1, a0.Cout, a0.Cin, 0);
-    const int tiles = cdiv(a0.M, 32);
-    const int rpc = cdiv(tiles, pl.chunks) * 32;
-    const int nchunks = cdiv(a0.M, rpc);
+    const int rpc = wgrad_rows_per_chunk(a0.M, pl);
+    const int nchunks = wgrad_part_sets(a0.M, pl);
+    const bool wg = pl.waves > 1;
     const int CoutP = round_up(a0.Cout, 32), CT = a0.Cin / 32, OT = CoutP / 32;
     if ((long)a0.M * a0.Cin * 4 >= (1l << 31) || (long)a0.M * a0.Cout * 4 >= (1l << 31)) return DLKA_ERR_UNSUPPORTED;
     for (int k = 0; k < 3; ++k) {
@@ -896,18 +996,21 @@ int launch_cl_wgrad_pw3(const WgradArgs *jobs, float *const *gw, float *const *g
         d.part = a.part; d.bpart = a.bpart; d.gw = gw[k]; d.gb = gb[k];
         d.chunks = nchunks; d.K = 1; d.CoutP = CoutP; d.Cout = a.Cout; d.Cin = a.Cin; d.kind = 0; d.n = (long)a.Cout * a.Cin + (gb[k] ? a.Cout : 0);
     }
-    dim3 grid(nchunks, cdiv(OT, pl.cot) * CT, 3), block(64);
+    dim3 grid(nchunks, cdiv(OT, pl.cot) * CT, 3), block(64 * pl.waves);
     const bool n16 = (a0.N & 15) == 0;
-    if (a0.act_bf16) {
-        if (pl.cot == 2 && n16) { auto k = cl_wgrad_pw3_kernel<2, true, bf16_t>; DLKA_LAUNCH(k, grid, block, 0, st, b); }
-        else if (pl.cot == 2) { auto k = cl_wgrad_pw3_kernel<2, false, bf16_t>; DLKA_LAUNCH(k, grid, block, 0, st, b); }
-        else if (n16) { auto k = cl_wgrad_pw3_kernel<1, true, bf16_t>; DLKA_LAUNCH(k, grid, block, 0, st, b); }
-        else { auto k = cl_wgrad_pw3_kernel<1, false, bf16_t>; DLKA_LAUNCH(k, grid, block, 0, st, b); }
+#define DLKA_PW3_W(CO, T_, WV)                                                                                  \
+    {                                                                                                           \
+        if (n16) { auto k = cl_wgrad_pw3_kernel<CO, true, T_, WV>; DLKA_LAUNCH(k, grid, block, 0, st, b); }     \
+        else { auto k = cl_wgrad_pw3_kernel<CO, false, T_, WV>; DLKA_LAUNCH(k, grid, block, 0, st, b); }        \
     }
-    else if (pl.cot == 2 && n16) { auto k = cl_wgrad_pw3_kernel<2, true>; DLKA_LAUNCH(k, grid, block, 0, st, b); }
-    else if (pl.cot == 2) { auto k = cl_wgrad_pw3_kernel<2, false>; DLKA_LAUNCH(k, grid, block, 0, st, b); }
-    else if (n16) { auto k = cl_wgrad_pw3_kernel<1, true>; DLKA_LAUNCH(k, grid, block, 0, st, b); }
-    else { auto k = cl_wgrad_pw3_kernel<1, false>; DLKA_LAUNCH(k, grid, block, 0, st, b); }
+#define DLKA_PW3(CO, T_)                                                                                        \
+    {                                                                                                           \
+        if (wg) DLKA_PW3_W(CO, T_, DLKA_WGRAD_W_PW) else DLKA_PW3_W(CO, T_, 1)                                  \
+    }
+    if (a0.act_bf16) { if (pl.cot == 2) DLKA_PW3(2, bf16_t) else DLKA_PW3(1, bf16_t) }
+    else { if (pl.cot == 2) DLKA_PW3(2, float) else DLKA_PW3(1, float) }
+#undef DLKA_PW3
+#undef DLKA_PW3_W
     DLKA_CHECK_LAUNCH();
     return DLKA_OK;
 }
@@ -1022,7 +1125,10 @@ __global__ __launch_bounds__(256) void cl_wgrad_finalize_table_kernel(const Fina
 long cl_wgrad_finalize_plan_job(FinalizeJob &j)
 {
     constexpr bool no_tr = false;
-    j.tr = (!no_tr && j.kind == 0 && j.K > 1 && j.K <= 27 && j.chunks <= 16 && j.Cin % 32 == 0 && (long)j.Cout * j.Cin >= 1024) ? 1 : 0;
+#ifndef DLKA_FIN_TR_MAX_CHUNKS
+#define DLKA_FIN_TR_MAX_CHUNKS 16   // (compile-time for A/B builds; with four waves per workgroup the 16^3 stage's 13 partial sets come under it — profiles/r13_notes.md)
+#endif
+    j.tr = (!no_tr && j.kind == 0 && j.K > 1 && j.K <= 27 && j.chunks <= DLKA_FIN_TR_MAX_CHUNKS && j.Cin % 32 == 0 && (long)j.Cout * j.Cin >= 1024) ? 1 : 0;
     return j.tr ? (long)j.Cout * (j.Cin / 32) + (j.gb ? cdiv(j.Cout, 32) : 0) : cdivl(j.n, 32);
 }
 

@@ -154,7 +154,8 @@ class DLKABlockStack:
 
     def _build_finalize_plan(self, enable: bool):
         """The seven weight gradients of a block end in a "finalize" launch that folds their partial sums; nothing later in the backward pass
-        reads its results.  With block-PRIVATE partial-sum areas (288 GB of HBM: 0.4 GB for the 21 blocks) all blocks' finalisations become ONE
+        reads its results.  With block-PRIVATE partial-sum areas (288 GB of HBM: 0.31 GB for the 21 blocks at B = 2 — 1.18 GB before the weight-gradient
+        kernels summed their waves' tiles in the workgroup, which DLKA_WGRAD_WAVES=1 restores) all blocks' finalisations become ONE
         launch at the end of the backward pass (or of a slice of it) instead of 21 dependent launches of 15 - 30 us, most of each latency
         (include/dlka.h: dlka_wgrad_finalize_*).  The job table is recorded while the blocks go through their first backward pass (which still
         finalises block by block) and then lives on the device."""

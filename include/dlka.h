@@ -331,7 +331,9 @@ int dlka_lka3d_attention_tokens_backward(const void *x, const dlka_lka3d_params 
  * "finalize" launch (fold of the row-chunk partial sums, re-layout of the depthwise staging): 21 dependent launches of 15 - 30 us per step for the
  * blocks of a D_LKA_Former patch, most of each latency.  Nothing later in the backward pass reads their results, so a model that steps all its
  * blocks lets the partial sums of every block land in a block-PRIVATE area and folds them all at the end of the pass (or of a slice of it):
- *   _partials_bytes_v        size of a block's private partial-sum area;
+ *   _partials_bytes_v        size of a block's private partial-sum area (one tile set per WORKGROUP of the weight-gradient kernels; DLKA_WGRAD_WAVES=1,
+ *                            read per call, keeps one-wave workgroups and their larger areas: query and launch under the same setting — a launch that
+ *                            finds the area too small returns DLKA_ERR_WORKSPACE);
  *   _plan_bytes / _plan_init a HOST job table for n blocks;
  *   _backward_deferred_v     the backward call without its finalize launch; partial sums go to `partials`; with plan_host != NULL it records the
  *                            block's jobs in slot `plan_slot` (pointers of `partials` and of the gradient buffers: they must stay put);
