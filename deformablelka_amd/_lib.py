@@ -33,6 +33,8 @@ DLKA_RESAMPLE_SPLINE_PAD = 12                                          # scipy.n
 DLKA_AUG_I16 = 3                                                       # include/dlka.h: dlka_augment_*
 DLKA_AUG_CONSTANT, DLKA_AUG_NEAREST = 0, 1
 DLKA_AUG_RADIUS_MAX, DLKA_AUG_OPS_MAX = 32, 4
+DLKA_PREP_C_MAX, DLKA_PREP_REC = 32, 8                                  # include/dlka.h: dlka_prep_*
+DLKA_PREP_CT, DLKA_PREP_CT2, DLKA_PREP_NONCT = 0, 1, 2
 (DLKA_AUG_OP_NONE, DLKA_AUG_OP_NOISE, DLKA_AUG_OP_SCALE_ADD, DLKA_AUG_OP_CONTRAST, DLKA_AUG_OP_GAMMA, DLKA_AUG_OP_RETAIN,
  DLKA_AUG_OP_REPLACE) = range(7)
 
@@ -100,6 +102,12 @@ class AugmentDesc(ctypes.Structure):
                 ("src", c_int64 * 3), ("out", c_int64 * 3), ("cval", ctypes.c_double)]
 
 
+class PrepDesc(ctypes.Structure):
+    """``dlka_prep_desc`` (include/dlka.h)."""
+    _fields_ = [("rank", c_int32), ("C", c_int32), ("seg_channels", c_int32), ("nan_to_zero", c_int32), ("nonzero_label", c_int32),
+                ("ext", c_int64 * 3), ("lo", c_int64 * 3), ("hi", c_int64 * 3)]
+
+
 # name -> (restype, argtypes); every symbol include/dlka.h declares
 _G = POINTER(ConvGeom)
 _SD = POINTER(SegLossDesc)
@@ -107,6 +115,7 @@ _SDD = POINTER(SurfaceDistDesc)
 _CCD = POINTER(ConnCompDesc)
 _RSD = POINTER(ResampleDesc)
 _AGD = POINTER(AugmentDesc)
+_PPD = POINTER(PrepDesc)
 SIGNATURES = {
     "dlka_abi_version": (c_int, []),
     "dlka_status_string": (c_char_p, [c_int]),
@@ -261,6 +270,15 @@ SIGNATURES = {
     "dlka_augment_channel_stats": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int64, c_int64, c_void_p]),
     "dlka_augment_pointwise": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int64, POINTER(c_int64)] + [c_void_p] * 5),
     "dlka_augment_launch_count": (ctypes.c_long, []),
+    "dlka_prep_background": (c_int, [c_void_p, _PPD, c_void_p, c_void_p]),
+    "dlka_prep_fill_workspace_bytes": (c_size_t, [_PPD]),
+    "dlka_prep_fill_bbox": (c_int, [c_void_p, c_void_p, _PPD, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
+    "dlka_prep_mask_bbox": (c_int, [c_void_p, _PPD, c_void_p, c_void_p]),
+    "dlka_prep_crop": (c_int, [c_void_p, c_void_p, c_void_p, _PPD, c_void_p, c_void_p, c_void_p]),
+    "dlka_prep_stats_workspace_bytes": (c_size_t, [_PPD]),
+    "dlka_prep_channel_stats": (c_int, [c_void_p, c_void_p, _PPD, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "dlka_prep_normalize": (c_int, [c_void_p, c_void_p, _PPD, c_void_p, c_void_p, c_void_p]),
+    "dlka_prep_launch_count": (ctypes.c_long, []),
     "dlka_trace_start": (c_int, [c_int, c_void_p]),
     "dlka_trace_mark": (c_int, [c_void_p]),
     "dlka_trace_stop": (c_int, []),

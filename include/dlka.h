@@ -864,6 +864,60 @@ int dlka_augment_pointwise(const void *x, const void *noise, void *y, int dtype,
 long dlka_augment_launch_count(void);
 
 /* =======================================================================================
+ * Case preprocessing: nonzero mask with filled holes, crop, intensity normalisation — csrc/cl_preprocess.hip
+ * =======================================================================================
+ * What the reference runs on one host core per case before a trainer or predict_simple sees it: ImageCropper.crop
+ * (3D/d_lka_former/preprocessing/cropping.py:23-150) and the normalisation loop of GenericPreprocessor.resample_and_normalize
+ * (preprocessing/preprocessing.py:274-305).  Volumes are [C][d][h][w] float32, w contiguous; label maps int32; a description carries the
+ * spatial rank (2 or 3) and ext[3] = (d, h, w), left-padded with 1 for rank 2.
+ *
+ * dlka_prep_background   cropping.py:26-29 complemented: background[cell] uint8 = 1 where every channel is == 0 (a NaN is != 0, as in numpy).
+ *                        The caller labels this map with dlka_cc_components (mask_mode, connectivity 1: scipy's default structure).
+ * dlka_prep_fill_bbox    cropping.py:30 (scipy.ndimage.binary_fill_holes) and :35-42 (get_bbox_from_mask) in one pass over the volume:
+ *                        a background component is a hole iff none of its cells lies on one of the 2 * rank faces of the array, so
+ *                        mask = !background | !(component touches a face).  `labels` is dlka_cc_components' map of the background.
+ *                        box[8] int32 (device) = minimum index per axis (3), maximum index per axis (3), number of set cells, unused; an empty
+ *                        mask leaves (INT32_MAX x 3, -1 x 3, 0).  Integer atomicMin / atomicMax / atomicAdd only: bitwise reproducible.
+ *                        One memset and three launches.  workspace: one byte per cell plus one (dlka_prep_fill_workspace_bytes).
+ * dlka_prep_mask_bbox    :35-42 for a given uint8 map (set = value != 0): the same box.  Two launches.
+ * dlka_prep_crop         cropping.py:95-115: out[C][box] = data inside [lo, hi) per axis, NaN replaced by 0 when nan_to_zero != 0
+ *                        (preprocessing.py:250); seg_out (may be NULL) [max(seg_channels, 1)][box] = with seg_channels > 0 the cropped seg with
+ *                        nonzero_label where (seg == 0) & (mask == 0) (:110), otherwise nonzero_label where mask == 0 and 0 elsewhere (:112-115).
+ *                        One launch.
+ * dlka_prep_channel_stats   completes table[C][DLKA_PREP_REC] float64 (device) = (scheme, lower, upper, mean, sd, use_mask, count, unused): for
+ *                        a DLKA_PREP_CT2 channel mean, population sd and count of the cells with (float)lower < x < (float)upper (:292-295), for
+ *                        a DLKA_PREP_NONCT channel those of the cells with seg >= 0 (use_mask != 0) or of every cell (:300-304); a DLKA_PREP_CT
+ *                        channel keeps the mean and sd it came with.  float64, two passes, folded in a fixed order: bitwise reproducible.
+ *                        `seg` is ONE label map (the reference's seg[-1]).  Four launches.  workspace: dlka_prep_stats_workspace_bytes.
+ * dlka_prep_normalize    :276-305 for every channel in one launch, each step rounded to float32 and the division IEEE: CT / CT2
+ *                        x = min(max(x, (float)lower), (float)upper), (x - (float)mean) / (float)sd, then 0 where use_mask and seg < 0;
+ *                        NONCT (x - (float)mean) / ((float)sd + 1e-8f) on the selected cells, 0 elsewhere.  One launch.
+ * Return codes: DLKA_ERR_NULL, DLKA_ERR_SHAPE (rank other than 2 or 3, C or an extent < 1, a padded extent != 1, a box outside the array or
+ * empty), DLKA_ERR_UNSUPPORTED (C or seg_channels > DLKA_PREP_C_MAX, 2^31 cells or more, out == data for the crop), DLKA_ERR_WORKSPACE.
+ * Nothing is launched before the checks pass. */
+#define DLKA_PREP_C_MAX 32
+#define DLKA_PREP_REC 8
+enum { DLKA_PREP_CT = 0, DLKA_PREP_CT2 = 1, DLKA_PREP_NONCT = 2 };
+typedef struct dlka_prep_desc {
+    int32_t rank, C, seg_channels, nan_to_zero, nonzero_label;
+    int64_t ext[3];
+    int64_t lo[3], hi[3];                  /* dlka_prep_crop only */
+} dlka_prep_desc;
+int dlka_prep_background(const float *data, const dlka_prep_desc *d, uint8_t *background, void *stream);
+size_t dlka_prep_fill_workspace_bytes(const dlka_prep_desc *d);
+int dlka_prep_fill_bbox(const uint8_t *background, const int32_t *labels, const dlka_prep_desc *d, void *workspace, size_t workspace_bytes,
+                        uint8_t *mask, int32_t *box, void *stream);
+int dlka_prep_mask_bbox(const uint8_t *mask, const dlka_prep_desc *d, int32_t *box, void *stream);
+int dlka_prep_crop(const float *data, const int32_t *seg, const uint8_t *mask, const dlka_prep_desc *d, float *out, int32_t *seg_out,
+                   void *stream);
+size_t dlka_prep_stats_workspace_bytes(const dlka_prep_desc *d);
+int dlka_prep_channel_stats(const float *data, const int32_t *seg, const dlka_prep_desc *d, double *table, void *workspace,
+                            size_t workspace_bytes, void *stream);
+int dlka_prep_normalize(const float *data, const int32_t *seg, const dlka_prep_desc *d, const double *table, float *out, void *stream);
+/* Diagnostics: kernel launches so far (this process) of the entries above. */
+long dlka_prep_launch_count(void);
+
+/* =======================================================================================
  * Launch trace — measurement aid (no reference counterpart; the reference has no profiling hooks)
  * =======================================================================================
  * Between dlka_trace_start and dlka_trace_stop every kernel launch of the library is followed by a HIP timing event on the
