@@ -17,14 +17,14 @@ from .transformerblock import LKA3d_deform, LKA_Attention3d_deform, TransformerB
 from .tv_ops import DeformConv2d, deform_conv2d  # noqa: F401
 from .network import D_LKA_Former, D_LKA_Former_Encoder, D_LKA_FormerUpBlock, UnetOutBlock  # noqa: F401
 from .decoder2d import deformableLKABlock, MyDecoderLayer  # noqa: F401
-from . import inference, training, dp, losses, metrics, postprocessing, resampling, preprocessing  # noqa: F401
+from . import inference, training, dp, losses, metrics, postprocessing, resampling, preprocessing, inference2d  # noqa: F401
 from .losses import DC_and_CE_loss, DiceLoss, MultipleOutputLoss2, SoftDiceLoss, online_eval_counts  # noqa: F401
 
 __all__ = ["DeformConv", "DeformConvPack", "DeformConvPack_experimental", "DeformConvPack_Depth", "DeformConv_d",
            "DeformConvPack_d", "DeformConvFunction", "LKA3d_deform", "LKA_Attention3d_deform", "TransformerBlock_3D_single_deform_LKA", "UnetResBlock", "DeformConv2dPack",
            "deformable_LKA", "deformable_LKA_Attention", "DeformConv2d", "deform_conv2d", "install_reference_aliases", "D_LKA_Former",
            "D_LKA_Former_Encoder", "D_LKA_FormerUpBlock", "UnetOutBlock", "deformableLKABlock", "MyDecoderLayer", "inference", "training", "dp",
-           "losses", "metrics", "postprocessing", "resampling", "preprocessing", "SoftDiceLoss", "DC_and_CE_loss", "MultipleOutputLoss2", "DiceLoss", "online_eval_counts"]
+           "losses", "metrics", "postprocessing", "resampling", "preprocessing", "inference2d", "SoftDiceLoss", "DC_and_CE_loss", "MultipleOutputLoss2", "DiceLoss", "online_eval_counts"]
 
 
 _ALIAS_DEFAULT = ("D3D", "functions.deform_conv_func", "modules.deform_conv")

@@ -35,6 +35,7 @@ DLKA_AUG_CONSTANT, DLKA_AUG_NEAREST = 0, 1
 DLKA_AUG_RADIUS_MAX, DLKA_AUG_OPS_MAX = 32, 4
 DLKA_PREP_C_MAX, DLKA_PREP_REC = 32, 8                                  # include/dlka.h: dlka_prep_*
 DLKA_PREP_CT, DLKA_PREP_CT2, DLKA_PREP_NONCT = 0, 1, 2
+DLKA_ZOOM2D_I16, DLKA_ZOOM2D_K_MAX, DLKA_ZOOM2D_OUTSIDE = 3, 255, -2 ** 31   # include/dlka.h: dlka_zoom2d_*
 (DLKA_AUG_OP_NONE, DLKA_AUG_OP_NOISE, DLKA_AUG_OP_SCALE_ADD, DLKA_AUG_OP_CONTRAST, DLKA_AUG_OP_GAMMA, DLKA_AUG_OP_RETAIN,
  DLKA_AUG_OP_REPLACE) = range(7)
 
@@ -108,6 +109,12 @@ class PrepDesc(ctypes.Structure):
                 ("ext", c_int64 * 3), ("lo", c_int64 * 3), ("hi", c_int64 * 3)]
 
 
+class Zoom2dDesc(ctypes.Structure):
+    """``dlka_zoom2d_desc`` (include/dlka.h)."""
+    _fields_ = [("in_dtype", c_int32), ("out_dtype", c_int32), ("taps", c_int32), ("normalize", c_int32), ("N", c_int64),
+                ("in_", c_int64 * 2), ("out", c_int64 * 2), ("mean", ctypes.c_float), ("std", ctypes.c_float)]
+
+
 # name -> (restype, argtypes); every symbol include/dlka.h declares
 _G = POINTER(ConvGeom)
 _SD = POINTER(SegLossDesc)
@@ -116,6 +123,7 @@ _CCD = POINTER(ConnCompDesc)
 _RSD = POINTER(ResampleDesc)
 _AGD = POINTER(AugmentDesc)
 _PPD = POINTER(PrepDesc)
+_ZMD = POINTER(Zoom2dDesc)
 SIGNATURES = {
     "dlka_abi_version": (c_int, []),
     "dlka_status_string": (c_char_p, [c_int]),
@@ -279,6 +287,10 @@ SIGNATURES = {
     "dlka_prep_channel_stats": (c_int, [c_void_p, c_void_p, _PPD, c_void_p, c_void_p, c_size_t, c_void_p]),
     "dlka_prep_normalize": (c_int, [c_void_p, c_void_p, _PPD, c_void_p, c_void_p, c_void_p]),
     "dlka_prep_launch_count": (ctypes.c_long, []),
+    "dlka_zoom2d_spline": (c_int, [c_void_p, c_void_p, _ZMD, c_void_p, c_void_p, c_void_p]),
+    "dlka_zoom2d_nearest": (c_int, [c_void_p, c_void_p, _ZMD, c_int, c_void_p, c_void_p]),
+    "dlka_zoom2d_argmax": (c_int, [c_void_p, c_void_p, _ZMD, c_int, c_void_p, c_void_p]),
+    "dlka_zoom2d_launch_count": (ctypes.c_long, []),
     "dlka_trace_start": (c_int, [c_int, c_void_p]),
     "dlka_trace_mark": (c_int, [c_void_p]),
     "dlka_trace_stop": (c_int, []),

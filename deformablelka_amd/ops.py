@@ -1610,3 +1610,138 @@ def prep_normalize(data, seg_last, records):
 
 def prep_launch_count() -> int:
     return int(L.get_lib().dlka_prep_launch_count())
+
+
+# ---- the 2-D evaluator's slice resampling (include/dlka.h: dlka_zoom2d_*) -----------------------------------------------------------------------
+_ZM_DTYPES = {torch.float32: L.DLKA_F32, torch.bfloat16: L.DLKA_BF16, torch.float64: L.DLKA_F64, torch.int16: L.DLKA_ZOOM2D_I16}
+
+
+def _zm_stack(x, what="slices"):
+    L.require_device(x)
+    if x.ndim != 3 or x.numel() == 0:
+        raise RuntimeError(f"zoom2d: {what} are (n, h, w) with no empty axis, got {tuple(x.shape)}")
+    if x.numel() >= 2 ** 31:
+        raise RuntimeError("zoom2d: fewer than 2^31 cells per stack")
+    return x.contiguous()
+
+
+def _zm_desc(n, in_hw, out_hw):
+    out_hw = tuple(int(v) for v in out_hw)
+    if len(out_hw) != 2 or min(out_hw) < 1 or int(n) * out_hw[0] * out_hw[1] >= 2 ** 31:
+        raise RuntimeError(f"zoom2d: two positive output extents and fewer than 2^31 output cells, got {out_hw} for {int(n)} slices")
+    d = L.Zoom2dDesc()
+    d.N = int(n)
+    for ax in range(2):
+        d.in_[ax], d.out[ax] = int(in_hw[ax]), out_hw[ax]
+    return d, out_hw
+
+
+def zoom2d_spline_tables(starts, weights, in_hw, taps, device):
+    """Per-axis (rows, then columns) first taps and weights of the spline kernel as two device arrays.  ``starts[ax]``: int, -1 .. n - 1 (the
+    kernel mirrors the taps beyond the slice) or DLKA_ZOOM2D_OUTSIDE; ``weights[ax]``: float64 (m, taps)."""
+    s_all, w_all = [], []
+    for ax in range(2):
+        s, w = np.asarray(starts[ax], dtype=np.int64), np.asarray(weights[ax], dtype=np.float64)
+        inside = s != L.DLKA_ZOOM2D_OUTSIDE
+        if w.shape != (s.shape[0], taps) or (inside & ((s < (-1 if taps == 4 else 0)) | (s > int(in_hw[ax]) - 1))).any():
+            raise RuntimeError(f"zoom2d: the table of axis {ax} does not fit an extent of {int(in_hw[ax])} with {taps} taps")
+        s_all.append(s)
+        w_all.append(np.pad(w, ((0, 0), (0, 4 - taps))))
+    return (torch.from_numpy(np.concatenate(s_all).astype(np.int32)).to(device),
+            torch.from_numpy(np.ascontiguousarray(np.concatenate(w_all))).to(device))
+
+
+def zoom2d_index_tables(cells, in_hw, device):
+    """Per-axis (rows, then columns) source indices of the order-0 kernels as one int32 device array; -1: outside the slice."""
+    out = []
+    for ax in range(2):
+        c = np.asarray(cells[ax], dtype=np.int64)
+        if c.ndim != 1 or c.min() < -1 or c.max() > int(in_hw[ax]) - 1:
+            raise RuntimeError(f"zoom2d: the index table of axis {ax} does not fit an extent of {int(in_hw[ax])}")
+        out.append(c)
+    return torch.from_numpy(np.concatenate(out).astype(np.int32)).to(device)
+
+
+def _zm_table(t, n, dtype, like, what):
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.numel() != n or t.device != like.device or not t.is_contiguous():
+        raise RuntimeError(f"zoom2d: {what} is a contiguous {dtype} device array of {n} entries (zoom2d_*_tables)")
+    return t
+
+
+def zoom2d_coefficients(x):
+    """float64 cubic B-spline coefficients of every slice of ``x`` (n, h, w) as scipy.ndimage.zoom prepares them under mode 'constant': the
+    'mirror' prefilter of the slice itself, no padding.  The stack is filtered as ONE volume along axes 1 and 2: three launches whatever n."""
+    x = _zm_stack(x)
+    lib, st = L.get_lib(), L.stream_ptr(x)
+    i3 = ctypes.c_int64 * 3
+    if x.dtype in _RS_DTYPES:
+        coef = torch.empty(x.shape, dtype=torch.float64, device=x.device)
+        L.check(lib.dlka_resample_spline_pad(L.ptr(x), L.ptr(coef), _RS_DTYPES[x.dtype], i3(*x.shape), i3(0, 0, 0), st), "resample_spline_pad")
+    elif x.dtype in (torch.bfloat16, torch.int16):
+        coef = x.to(torch.float64)
+    else:
+        raise RuntimeError(f"zoom2d: float32, float64, bfloat16 or int16 slices, got {x.dtype}")
+    for ax in (1, 2):
+        L.check(lib.dlka_augment_spline_prefilter_mirror(L.ptr(coef), i3(*x.shape), ax, st), "augment_spline_prefilter_mirror")
+    return coef
+
+
+def zoom2d_spline(src, out_hw, start, w4, taps, out_dtype, mean=None, std=None):
+    """The spline kernel: ``src`` (n, h, w) float64 coefficients (taps 4) or raw float32 / bfloat16 / int16 values (taps 2) evaluated through
+    the device tables of ``zoom2d_spline_tables``; float32, bfloat16 or int16 result, float32 (v - mean) / std in between when given."""
+    src = _zm_stack(src, "coefficients" if taps == 4 else "slices")
+    if src.dtype not in _ZM_DTYPES or out_dtype not in _ZM_DTYPES or out_dtype == torch.float64:
+        raise RuntimeError(f"zoom2d: {src.dtype} -> {out_dtype} is not a pair the spline kernel has")
+    d, out_hw = _zm_desc(src.shape[0], src.shape[1:], out_hw)
+    d.in_dtype, d.out_dtype, d.taps = _ZM_DTYPES[src.dtype], _ZM_DTYPES[out_dtype], int(taps)
+    if (mean is None) != (std is None):
+        raise RuntimeError("zoom2d: mean and std come together")
+    if mean is not None:
+        d.normalize, d.mean, d.std = 1, float(mean), float(std)
+    rows = out_hw[0] + out_hw[1]
+    start, w4 = _zm_table(start, rows, torch.int32, src, "start"), _zm_table(w4, 4 * rows, torch.float64, src, "w4")
+    y = torch.empty((src.shape[0],) + out_hw, dtype=out_dtype, device=src.device)
+    L.check(L.get_lib().dlka_zoom2d_spline(L.ptr(src), L.ptr(y), ctypes.byref(d), L.ptr(start), L.ptr(w4), L.stream_ptr(src)), "zoom2d_spline")
+    return y
+
+
+def zoom2d_nearest(x, out_hw, idx):
+    """Order 0: ``x`` (n, h, w) of any 1, 2, 4 or 8 byte dtype gathered through the device table of ``zoom2d_index_tables``; outside: 0."""
+    x = _zm_stack(x)
+    if x.dtype == torch.bool or x.element_size() not in (1, 2, 4, 8) or x.is_complex():
+        raise RuntimeError(f"zoom2d: a real dtype of 1, 2, 4 or 8 bytes, got {x.dtype}")
+    d, out_hw = _zm_desc(x.shape[0], x.shape[1:], out_hw)
+    idx = _zm_table(idx, out_hw[0] + out_hw[1], torch.int32, x, "idx")
+    y = torch.empty((x.shape[0],) + out_hw, dtype=x.dtype, device=x.device)
+    L.check(L.get_lib().dlka_zoom2d_nearest(L.ptr(x), L.ptr(y), ctypes.byref(d), x.element_size(), L.ptr(idx), L.stream_ptr(x)), "zoom2d_nearest")
+    return y
+
+
+def zoom2d_argmax(logits, out_hw, idx, out=None):
+    """uint8 (n, x, y): the first maximum over the K planes of ``logits`` (n, K, h, w; float32 / bfloat16, finite) at the source pixel the
+    device table of ``zoom2d_index_tables`` names for each output pixel, 0 outside.  ``out``: a contiguous uint8 (n, x, y) to write into."""
+    L.require_device(logits)
+    if logits.ndim != 4 or logits.numel() == 0 or logits.dtype not in (torch.float32, torch.bfloat16):
+        raise RuntimeError(f"zoom2d: logits are float32 / bfloat16 (n, K, h, w) with no empty axis, got {logits.dtype} {tuple(logits.shape)}")
+    if logits.shape[1] > L.DLKA_ZOOM2D_K_MAX:
+        raise RuntimeError(f"zoom2d: at most {L.DLKA_ZOOM2D_K_MAX} classes for a uint8 label map, got {logits.shape[1]}")
+    if logits.numel() >= 2 ** 31 * 64:
+        raise RuntimeError("zoom2d: fewer than 2^37 logits per chunk")
+    logits = logits.contiguous()
+    d, out_hw = _zm_desc(logits.shape[0], logits.shape[2:], out_hw)
+    if logits[:, 0].numel() >= 2 ** 31:
+        raise RuntimeError("zoom2d: fewer than 2^31 cells per stack")
+    d.in_dtype = _ZM_DTYPES[logits.dtype]
+    idx = _zm_table(idx, out_hw[0] + out_hw[1], torch.int32, logits, "idx")
+    shape = (logits.shape[0],) + out_hw
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=logits.device)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != shape or out.device != logits.device or not out.is_contiguous():
+        raise RuntimeError(f"zoom2d: out is a contiguous uint8 {shape} on the logits' device")
+    L.check(L.get_lib().dlka_zoom2d_argmax(L.ptr(logits), L.ptr(out), ctypes.byref(d), int(logits.shape[1]), L.ptr(idx), L.stream_ptr(logits)),
+            "zoom2d_argmax")
+    return out
+
+
+def zoom2d_launch_count() -> int:
+    return int(L.get_lib().dlka_zoom2d_launch_count())

@@ -918,6 +918,43 @@ int dlka_prep_normalize(const float *data, const int32_t *seg, const dlka_prep_d
 long dlka_prep_launch_count(void);
 
 /* =======================================================================================
+ * The 2-D evaluator's slice resampling: scipy.ndimage.zoom of a stack of slices, argmax fused with the zoom back — csrc/cl_zoom2d.hip
+ * =======================================================================================
+ * test_single_volume (2D/utils.py:63-110) zooms every slice to the patch size at order 3, normalises it, runs the network and zooms the argmax
+ * of the logits back at order 0; the train-side __getitem__ (2D/datasets/dataset_synapse.py:109-112) zooms image and label the same way.
+ * scipy.ndimage.zoom with its defaults: output index k of an axis n -> m reads the coordinate k * ((n - 1) / (m - 1)); mode 'constant' gives
+ * cval = 0 wherever a coordinate is < 0 or > n - 1, at every order.  The caller forms the coordinates in float64 on the host and passes them
+ * as tables, rows (out[0] entries) first, then columns (out[1]); stacks are [N][h][w], w contiguous.
+ *
+ * dlka_zoom2d_spline    taps 4: src = float64 B-spline coefficients [N][in] (dlka_augment_spline_prefilter_mirror along axes 1 and 2 of the
+ *                       stack); taps 2: src = the raw values in in_dtype (order 1).  start[row] = the first tap (floor(coordinate) - 1, or
+ *                       floor(coordinate) for 2 taps) or DLKA_ZOOM2D_OUTSIDE; w4[4 * row + k] = the weights (2 taps: k < 2).  Taps beyond the
+ *                       slice are mirrored in the kernel.  The float64 sum t += (c * w_row) * w_col, rows outermost, is rounded once to float32;
+ *                       with normalize != 0 the float32 (v - mean) / std follows (one IEEE subtraction, one IEEE division); DLKA_BF16 then
+ *                       rounds once more.  DLKA_ZOOM2D_I16 rounds the float64 sum half away from zero and saturates (scipy's rule).
+ *                       (in_dtype, out_dtype): taps 4 (DLKA_F64, F32 | BF16 | I16); taps 2 (F32, F32 | BF16), (BF16, BF16), (I16, I16).
+ * dlka_zoom2d_nearest   order 0 for elements of elem_bytes (1, 2, 4, 8): y[n][i][j] = x[n][idx[i]][idx[out[0] + j]], 0 where either index is
+ *                       outside [0, extent) (the caller writes -1 for a coordinate outside the slice).
+ * dlka_zoom2d_argmax    logits [N][K][in] (in_dtype DLKA_F32 or DLKA_BF16, finite), labels [N][out] uint8 = the first maximum over the K planes at
+ *                       the source pixel (idx[i], idx[out[0] + j]), 0 where either index is outside.  The [N][in] label map is never written.
+ * One launch each, no atomics: results are bitwise reproducible.  Return codes: DLKA_ERR_NULL, DLKA_ERR_SHAPE (N, K or an extent < 1),
+ * DLKA_ERR_DTYPE, DLKA_ERR_UNSUPPORTED (taps other than 2 or 4, 2^31 cells or more, K > DLKA_ZOOM2D_K_MAX, normalize with I16 or std == 0,
+ * output == input).  Nothing is launched before the checks pass. */
+#define DLKA_ZOOM2D_I16 3
+#define DLKA_ZOOM2D_K_MAX 255
+#define DLKA_ZOOM2D_OUTSIDE (-2147483647 - 1)
+typedef struct dlka_zoom2d_desc {
+    int32_t in_dtype, out_dtype, taps, normalize;
+    int64_t N, in[2], out[2];
+    float mean, std;
+} dlka_zoom2d_desc;
+int dlka_zoom2d_spline(const void *src, void *y, const dlka_zoom2d_desc *d, const int32_t *start, const double *w4, void *stream);
+int dlka_zoom2d_nearest(const void *x, void *y, const dlka_zoom2d_desc *d, int elem_bytes, const int32_t *idx, void *stream);
+int dlka_zoom2d_argmax(const void *logits, uint8_t *labels, const dlka_zoom2d_desc *d, int K, const int32_t *idx, void *stream);
+/* Diagnostics: kernel launches so far (this process) of the entries above. */
+long dlka_zoom2d_launch_count(void);
+
+/* =======================================================================================
  * Launch trace — measurement aid (no reference counterpart; the reference has no profiling hooks)
  * =======================================================================================
  * Between dlka_trace_start and dlka_trace_stop every kernel launch of the library is followed by a HIP timing event on the
