@@ -91,12 +91,14 @@ int dlka_deform_conv3d_forward_cl(const void *x, const void *offset, const void 
     SameConv s;
     DLKA_TRY(make_same_conv(c, s));
     if (c->deformable_group != 1 || !deform_supported(s)) return DLKA_ERR_UNSUPPORTED;
-    s.act_bf16 = dtype == DLKA_BF16;   // x / out bf16 storage; offsets, weight and bias stay fp32
+    s.act_bf16 = dtype == DLKA_BF16;   // x / out bf16 storage; offsets, weight and bias stay fp32.  The arithmetic is the general operator's: fp32 samples, exact products on
+                                       // the fp32-input MFMA, fp32 accumulation, ONE rounding at the store (the bf16 matrix cores are the fused block's trade, not this entry's)
     Carver cv(workspace, workspace_bytes);
     float *wp = (float *)cv.take(dense_wp_floats(s) * 4);
     float *slab = (float *)cv.take(deform_fwd_slab_floats(s) * 4);
     if (!cv.ok()) return DLKA_ERR_WORKSPACE;
-    return deform_forward(s, (const float *)x, (const float *)offset, (const float *)weight, (const float *)bias, (float *)out, wp, (hipStream_t)stream, slab);
+    return deform_forward(s, (const float *)x, (const float *)offset, (const float *)weight, (const float *)bias, (float *)out, wp, (hipStream_t)stream, slab,
+                          /* b16_cores */ false);
 }
 
 int dlka_deform_conv3d_backward_cl(const void *x, const void *offset, const void *weight, const void *grad_out, void *grad_x, void *grad_offset,

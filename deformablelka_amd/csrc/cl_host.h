@@ -102,7 +102,7 @@ bool deform_b16();
 bool deform_supported(const SameConv &s);
 size_t deform_fwd_slab_floats(const SameConv &s);
 int deform_forward(const SameConv &s, const float *x, const float *off, const float *w, const float *bias, float *out, float *wp, hipStream_t st,
-                   float *slab = nullptr);
+                   float *slab = nullptr, bool b16_cores = true);
 void fill_deform_bwd(DeformBwdArgs &a, const SameConv &s);
 size_t deform_scratch_floats(const SameConv &s);
 int deform_backward(const SameConv &s, const float *x, const float *off, const float *w, const float *gout, float *gx, float *goff,

@@ -331,10 +331,13 @@ size_t deform_fwd_slab_floats(const SameConv &s)
     return sp > 1 ? (size_t)sp * s.M * s.Cout : 0;
 }
 int deform_forward(const SameConv &s, const float *x, const float *off, const float *w, const float *bias, float *out, float *wp, hipStream_t st,
-                   float *slab)
+                   float *slab, bool b16_cores)
 {
-    // DLKA_BF16: the contraction runs on the bf16 matrix cores — weights as two-term bf16 records (prep mode | 8; deform_b16() = 0 keeps the fp32-input MFMA)
-    const int b16 = (s.act_bf16 && deform_b16()) ? 1 : 0;
+    // DLKA_BF16: the contraction runs on the bf16 matrix cores — weights as two-term bf16 records (prep mode | 8; deform_b16() = 0 keeps the fp32-input MFMA).
+    // That rounds every trilinear sample to bf16 (an ABSOLUTE error of ~2^-9 |sample| |weight| sqrt(K Cin) per output, inside the fused block's 2e-2 contract):
+    // the block's choice.  b16_cores = false — the single-operator entry, "same semantics as dlka_deform_conv3d_*": bf16 STORAGE, fp32 products of the fp32
+    // samples, one rounding at the store — keeps the fp32-input MFMA, as that entry's backward does (no wp16 there).
+    const int b16 = (s.act_bf16 && b16_cores && deform_b16()) ? 1 : 0;
     if (w) DLKA_TRY(launch_cl_prep_weight(w, wp, s.Cout, s.Cin, s.K, s.Cin, s.Cout, b16 ? 8 : 0, st));
     IgemmArgs a;
     fill_igemm(a, s);

@@ -797,7 +797,8 @@ static WgradPlan wgrad_plan(int M, int K, int Cout, int Cin, int amode)
         static const int cot_cap = [] { const char *e = getenv("DLKA_WGRAD_COT"); return e ? atoi(e) : 0; }();   // (A/B knob, read once: fewer co-tiles per wave = fewer registers)
         if (cot_cap > 0 && pl.cot > cot_cap) pl.cot = cot_cap;
     }
-    const int groups = cdiv(OT, pl.cot) * CT * cdiv(K, pl.tpw);
+    const int groups_ = cdiv(OT, pl.cot) * CT * cdiv(K, pl.tpw);
+    const int groups = groups_ > 0 ? groups_ : 1;   // (Cin < 32: a width the launchers refuse, but the workspace queries come through here first)
     const int tiles = cdiv(M, 32);
     // register-heavy variants run one wave per SIMD (1024 slots): fill them once rather than 2.004 times
     const int slots = (amode == 0 && K > 1 && pl.cot * pl.tpw >= 6) ? 1024 : 2048;   // <=2 waves/SIMD for the rest

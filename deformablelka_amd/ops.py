@@ -517,15 +517,20 @@ def conv3d_forward_cl(x, weight, bias=None, padding=0, dilation=1, groups=1, out
     return out
 
 
-def conv3d_backward_cl(x, weight, grad_out, padding=0, dilation=1, groups=1, grad_out_planar=False):
+def conv3d_backward_cl(x, weight, grad_out, padding=0, dilation=1, groups=1, grad_out_planar=False, need=(True, True, True)):
+    """-> (grad_x, grad_weight, grad_bias); a gradient ``need`` does not ask for is passed to the library as null and returned as None (no gradient asked
+    for: no library call)."""
     L.require_device(x, weight, grad_out)
     p, d = _triple(padding), _triple(dilation)
     x, weight, grad_out = x.contiguous(), weight.contiguous(), grad_out.contiguous()
     g = _geom_cl(x.shape, weight.shape[0], tuple(weight.shape[2:5]), p, d, groups)
     lib = L.get_lib()
     dt = L.dtype_code(x)
-    gi, gw = torch.empty_like(x), torch.empty_like(weight)
-    gb = torch.empty((g.Cout,), dtype=x.dtype, device=x.device)
+    if not any(need):
+        return None, None, None
+    gi = torch.empty_like(x) if need[0] else None
+    gw = torch.empty_like(weight) if need[1] else None
+    gb = torch.empty((g.Cout,), dtype=x.dtype, device=x.device) if need[2] else None
     wsb = lib.dlka_conv3d_cl_workspace(byref(g), dt, 1)
     ws = L.scratch(wsb, x)
     rc = lib.dlka_conv3d_backward_cl(L.ptr(x), L.ptr(weight), L.ptr(grad_out), int(grad_out_planar), L.ptr(gi), L.ptr(gw), L.ptr(gb),
@@ -534,9 +539,24 @@ def conv3d_backward_cl(x, weight, grad_out, padding=0, dilation=1, groups=1, gra
     return gi, gw, gb
 
 
+def deform_cl_grad_dtype(x):
+    """Element type of the four gradients ``dlka_deform_conv3d_backward_cl`` writes: x's for float32; float32 for bfloat16 activations too (DLKA_BF16 there
+    is mixed storage — x / out / grad_out bf16; offsets, weight, bias and ALL FOUR gradients fp32: grad_x is the fp32 accumulation target of the window
+    scatter, cl_deform_bwd2.hip, grad_offset one fp32 store per element, the parameter gradients come out of ``launch_cl_wgrad<float>``, cl_wgrad.hip)."""
+    return torch.float32 if x.dtype == torch.bfloat16 else x.dtype
+
+
+def _deform_cl_fp32_operands(x, **named):
+    """DLKA_BF16 on the channels-last deformable conv is an ACTIVATION dtype: the library reads offsets, weight and bias as fp32 whatever x is."""
+    for name, t in named.items():
+        if t is not None and t.dtype != (torch.float32 if x.dtype == torch.bfloat16 else x.dtype):
+            raise RuntimeError(f"channels-last deformable conv: {name} must be float32 (bfloat16 is the storage of x / out / grad_out only); got {t.dtype}")
+
+
 def deform_conv3d_forward_cl(x, offset, weight, bias, padding=1, dilation=1):
-    """x [B,D,H,W,C] channels-last, offset [B,3K,D,H,W] planar -> out [B,D,H,W,Cout]."""
+    """x [B,D,H,W,C] channels-last, offset [B,3K,D,H,W] planar -> out [B,D,H,W,Cout] (x's dtype; with bfloat16 x the offsets, weight and bias stay float32)."""
     L.require_device(x, offset, weight, bias)
+    _deform_cl_fp32_operands(x, offset=offset, weight=weight, bias=bias)
     p, d = _triple(padding), _triple(dilation)
     x, offset, weight, bias = x.contiguous(), offset.contiguous(), weight.contiguous(), bias.contiguous()
     g = _geom_cl(x.shape, weight.shape[0], tuple(weight.shape[2:5]), p, d, 1)
@@ -552,15 +572,25 @@ def deform_conv3d_forward_cl(x, offset, weight, bias, padding=1, dilation=1):
     return out
 
 
-def deform_conv3d_backward_cl(x, offset, weight, grad_out, padding=1, dilation=1):
+def deform_conv3d_backward_cl(x, offset, weight, grad_out, padding=1, dilation=1, need=(True, True, True, True)):
+    """-> (grad_x [B,D,H,W,C], grad_offset, grad_weight, grad_bias), each of ``deform_cl_grad_dtype(x)``; a gradient ``need`` does not ask for is passed to
+    the library as null and returned as None (no gradient asked for: no library call).  With bfloat16 x the library refuses grad_bias without grad_weight."""
     L.require_device(x, offset, weight, grad_out)
+    _deform_cl_fp32_operands(x, offset=offset, weight=weight)
+    if grad_out.dtype != x.dtype:
+        raise RuntimeError(f"channels-last deformable conv: grad_out must have x's dtype ({x.dtype}), got {grad_out.dtype}")
     p, d = _triple(padding), _triple(dilation)
     x, offset, weight, grad_out = x.contiguous(), offset.contiguous(), weight.contiguous(), grad_out.contiguous()
     g = _geom_cl(x.shape, weight.shape[0], tuple(weight.shape[2:5]), p, d, 1)
     lib = L.get_lib()
     dt = L.dtype_code(x)
-    gi, go, gw = torch.empty_like(x), torch.empty_like(offset), torch.empty_like(weight)
-    gb = torch.empty((g.Cout,), dtype=x.dtype, device=x.device)
+    if not any(need):
+        return None, None, None, None
+    gdt = deform_cl_grad_dtype(x)
+    gi = torch.empty(x.shape, dtype=gdt, device=x.device) if need[0] else None
+    go = torch.empty(offset.shape, dtype=gdt, device=x.device) if need[1] else None
+    gw = torch.empty(weight.shape, dtype=gdt, device=x.device) if need[2] else None
+    gb = torch.empty((g.Cout,), dtype=gdt, device=x.device) if need[3] else None
     wsb = lib.dlka_deform_conv3d_cl_workspace(byref(g), dt, 1)
     ws = L.scratch(wsb, x)
     rc = lib.dlka_deform_conv3d_backward_cl(L.ptr(x), L.ptr(offset), L.ptr(weight), L.ptr(grad_out), L.ptr(gi), L.ptr(go), L.ptr(gw),

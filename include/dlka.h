@@ -274,7 +274,9 @@ int dlka_conv3d_backward_cl(const void *x, const void *weight, const void *grad_
                             void *workspace, size_t workspace_bytes, const dlka_conv_geom *g, int dtype, void *stream);
 
 /* Deformable conv with x / out / grad_x channels-last and offset / grad_offset planar (reference layout).
- * group == deformable_group == 1, C and Cout in {32, 64, 96, 128, 256}.  Same semantics as dlka_deform_conv3d_*. */
+ * group == deformable_group == 1, C and Cout in {32, 64, 96, 128, 256}.  Same semantics as dlka_deform_conv3d_*.
+ * dtype DLKA_F32, or DLKA_BF16 = MIXED storage: x / out / grad_out bf16; offset, weight, bias and ALL FOUR gradients fp32.  The arithmetic is fp32 (exact
+ * products of the fp32 samples, fp32 accumulation, `out` rounded once at the store); backward refuses grad_bias without grad_weight for DLKA_BF16. */
 size_t dlka_deform_conv3d_cl_workspace(const dlka_conv_geom *g, int dtype, int backward);
 int dlka_deform_conv3d_forward_cl(const void *x, const void *offset, const void *weight, const void *bias, void *out,
                                   void *workspace, size_t workspace_bytes, const dlka_conv_geom *g, int dtype, void *stream);
