@@ -30,6 +30,7 @@ DLKA_SD_U8, DLKA_SD_I16, DLKA_SD_I32, DLKA_SD_I64 = 0, 1, 2, 3
 DLKA_CC_K_MAX, DLKA_CC_IDS_MAX = 32, 64                                # include/dlka.h: dlka_cc_*
 DLKA_CC_SUMMARY = 1 + 2 * DLKA_CC_K_MAX
 DLKA_RESAMPLE_SPLINE_PAD = 12                                          # scipy.ndimage: edge samples in front of the prefilter for mode 'nearest'
+DLKA_SPLINE_REFLECT, DLKA_SPLINE_MIRROR = 0, 1                         # include/dlka.h: dlka_spline_prefilter
 DLKA_AUG_I16 = 3                                                       # include/dlka.h: dlka_augment_*
 DLKA_AUG_CONSTANT, DLKA_AUG_NEAREST = 0, 1
 DLKA_AUG_RADIUS_MAX, DLKA_AUG_OPS_MAX = 32, 4
@@ -266,13 +267,12 @@ SIGNATURES = {
     "dlka_resample_argmax": (c_int, [c_void_p, c_void_p, _RSD, c_void_p, c_void_p, c_void_p, c_void_p]),
     "dlka_resample_linear": (c_int, [c_void_p, c_void_p, _RSD, c_void_p, c_void_p, c_void_p]),
     "dlka_resample_labels": (c_int, [c_void_p, c_void_p, _RSD, c_void_p, c_void_p, c_int, c_void_p]),
-    "dlka_resample_spline_pad": (c_int, [c_void_p, c_void_p, c_int, POINTER(c_int64), POINTER(c_int64), c_void_p]),
-    "dlka_resample_spline_prefilter": (c_int, [c_void_p, POINTER(c_int64), c_int, c_void_p]),
     "dlka_resample_spline_eval": (c_int, [c_void_p, c_void_p, _RSD, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "dlka_resample_launch_count": (ctypes.c_long, []),
+    "dlka_spline_pad": (c_int, [c_void_p, c_void_p, c_int, POINTER(c_int64), POINTER(c_int64), c_void_p]),
+    "dlka_spline_prefilter": (c_int, [c_void_p, POINTER(c_int64), c_int, c_int, c_void_p]),
     "dlka_augment_spatial": (c_int, [c_void_p, c_void_p, c_void_p, _AGD, c_void_p, c_void_p, c_void_p]),
     "dlka_augment_spatial_labels": (c_int, [c_void_p, c_void_p, _AGD, c_void_p, c_void_p, c_void_p]),
-    "dlka_augment_spline_prefilter_mirror": (c_int, [c_void_p, POINTER(c_int64), c_int, c_void_p]),
     "dlka_augment_gaussian": (c_int, [c_void_p, c_void_p, c_int, c_int64, POINTER(c_int64), c_int, c_void_p, c_void_p, c_void_p]),
     "dlka_augment_stats_workspace_bytes": (c_size_t, [c_int64, c_int64]),
     "dlka_augment_channel_stats": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int64, c_int64, c_void_p]),

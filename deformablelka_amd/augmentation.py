@@ -24,6 +24,7 @@ import torch
 from . import _lib as L
 from . import ops
 from . import resampling
+from ._containers import to_working_device
 
 __all__ = ["draw_spatial", "augment_spatial", "draw_gaussian_noise", "augment_gaussian_noise", "draw_gaussian_blur", "augment_gaussian_blur",
            "draw_brightness_multiplicative", "augment_brightness_multiplicative", "draw_brightness_additive", "augment_brightness_additive",
@@ -42,17 +43,9 @@ def launch_count() -> int:
 # ---- containers ------------------------------------------------------------------------------------------------------------------------------
 def _device(x, what):
     """A detached tensor on the working device; never the caller's own storage when it is going to be returned."""
-    if isinstance(x, torch.Tensor):
-        t = x.detach()
-    else:
-        a = np.asarray(x)
-        if a.dtype.kind not in "biuf":
-            raise RuntimeError(f"augmentation: {what} is an integer, bool or floating array, got {a.dtype}")
-        t = torch.from_numpy(np.ascontiguousarray(a.astype(np.int64) if a.dtype.kind == "u" and a.dtype.itemsize > 1 else a))
+    t = to_working_device(x, "augmentation", what)
     if t.ndim != 5:
         raise RuntimeError(f"augmentation: {what} is (b, c, x, y, z), got {tuple(t.shape)}")
-    if not L._test_backend and not t.is_cuda and torch.cuda.is_available():
-        t = t.cuda()
     return t
 
 

@@ -248,37 +248,6 @@ __global__ void __launch_bounds__(AUG_THREADS) dlka_augment_labels_kernel(AugArg
     }
 }
 
-// Cubic B-spline prefilter along `axis` with scipy's 'mirror' start values (what spline_filter1d uses for mode 'constant'); in place, one lane
-// per line.  cl_resample.hip's prefilter is the 'reflect' one (modes 'nearest' and 'reflect').
-__global__ void __launch_bounds__(AUG_THREADS) dlka_augment_prefilter_mirror_kernel(double *p, int e0, int e1, int e2, int axis)
-{
-#pragma clang fp contract(off)
-    const int ext[3] = {e0, e1, e2};
-    const long stride[3] = {(long)e1 * e2, (long)e2, 1L};
-    const int n = ext[axis];
-    const int ua = axis == 0 ? 1 : 0, ub = axis == 2 ? 1 : 2;
-    const long lines = (long)ext[ua] * ext[ub];
-    const long q = (long)blockIdx.x * AUG_THREADS + threadIdx.x;
-    if (q >= lines || n < 2) return;
-    double *c = p + (q / ext[ub]) * stride[ua] + (q % ext[ub]) * stride[ub];
-    const long s = stride[axis];
-    const double z = -0.26794919243112270647;   // sqrt(3) - 2
-    const double gain = (1.0 - z) * (1.0 - 1.0 / z);
-    for (int i = 0; i < n; ++i) c[i * s] *= gain;
-    double z_n_1 = 1.0;
-    for (int i = 0; i < n - 1; ++i) z_n_1 *= z;
-    double z_i = z;
-    double acc = c[0] + z_n_1 * c[(long)(n - 1) * s];
-    for (int i = 1; i < n - 1; ++i) {
-        acc += z_i * (c[i * s] + z_n_1 * c[(long)(n - 1 - i) * s]);
-        z_i *= z;
-    }
-    c[0] = acc / (1.0 - z_n_1 * z_n_1);
-    for (int i = 1; i < n; ++i) c[i * s] += z * c[(long)(i - 1) * s];
-    c[(long)(n - 1) * s] = (z * c[(long)(n - 2) * s] + c[(long)(n - 1) * s]) * z / (z * z - 1.0);
-    for (int i = n - 2; i >= 0; --i) c[i * s] = z * (c[(long)(i + 1) * s] - c[i * s]);
-}
-
 // (c)
 __device__ __forceinline__ int aug_reflect(int i, int n)
 {
@@ -534,24 +503,6 @@ extern "C" int dlka_augment_spatial_labels(const int32_t *seg, int32_t *out, con
         DLKA_LAUNCH(dlka_augment_labels_kernel<0>, grid, block, 0, (hipStream_t)stream, a, seg, out, maps, plain);
     else
         DLKA_LAUNCH(dlka_augment_labels_kernel<1>, grid, block, 0, (hipStream_t)stream, a, seg, out, maps, plain);
-    DLKA_CHECK_LAUNCH();
-    return DLKA_OK;
-}
-
-extern "C" int dlka_augment_spline_prefilter_mirror(double *coef, const int64_t *ext, int axis, void *stream)
-{
-    if (!coef || !ext) return DLKA_ERR_NULL;
-    if (axis < 0 || axis > 2) return DLKA_ERR_SHAPE;
-    long cells = 1;
-    for (int ax = 0; ax < 3; ++ax) {
-        if (ext[ax] < 1) return DLKA_ERR_SHAPE;
-        if (ext[ax] > 0x7fffffffL) return DLKA_ERR_UNSUPPORTED;
-        cells *= ext[ax];
-        if (cells > 0x7fffffffL) return DLKA_ERR_UNSUPPORTED;
-    }
-    g_aug_launches.fetch_add(1, std::memory_order_relaxed);
-    DLKA_LAUNCH(dlka_augment_prefilter_mirror_kernel, dim3((unsigned)cdivl(cells / ext[axis], AUG_THREADS)), dim3(AUG_THREADS), 0,
-                (hipStream_t)stream, coef, (int)ext[0], (int)ext[1], (int)ext[2], axis);
     DLKA_CHECK_LAUNCH();
     return DLKA_OK;
 }

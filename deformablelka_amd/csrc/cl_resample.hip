@@ -15,24 +15,22 @@
 //             grid is refined every source cell is read by several lanes of the same workgroup.
 //   linear    (b) the same arithmetic (rs_lerp3, the same instruction sequence: the fused label map equals the argmax of this kernel's output bit
 //             for bit), every channel written.
-//   spline    (c) order 3, float64 throughout: pad by edge samples, recursive prefilter along each filtered axis (one lane per line, causal and
-//             anti-causal pass), separable 4-tap evaluation, clip to the input's range; only the caller rounds to the output dtype.
+//   spline    (c) order 3, float64 throughout: separable 4-tap evaluation on the B-spline coefficients of the padded channel (cl_spline.hip
+//             prepares them), clip to the input's range; only the caller rounds to the output dtype.
 //   labels    (d) is_seg: the per-label passes of resize_segmentation (one resize of the indicator per label, ascending, later labels overwrite)
 //             collapse into one visit of the up to 8 source cells: the weight of a label is the sum of the weights of the cells that hold it,
 //             and the largest label whose weight passes the threshold wins; none: 0.
 //
 // No atomics, no reduction across lanes: every output cell is computed by one lane from the inputs alone, so two runs give the same bits.
-#include <atomic>
-
+#include "cl_resample.h"
 #include "dlka_common.h"
 
 namespace dlka {
 
-static std::atomic<long> g_rs_launches{0};   // dlka_resample_launch_count (include/dlka.h): diagnostics
+std::atomic<long> g_rs_launches{0};   // dlka_resample_launch_count (include/dlka.h): diagnostics; cl_spline.hip's launches count here too
 
 #define RS_THREADS 256
 #define RS_VPT 4                          // output voxels per lane along the contiguous axis in the argmax / linear kernels
-#define RS_PAD_MAX 64
 
 struct RsArgs {
     int C;
@@ -192,58 +190,6 @@ __global__ void __launch_bounds__(RS_THREADS) dlka_resample_labels_kernel(RsArgs
 }
 
 // ---- (c) order 3 ---------------------------------------------------------------------------------------------------------------------------
-struct RsPad {
-    int in[3], pad[3], ext[3];
-    long cells;
-};
-
-template <typename T>
-__global__ void __launch_bounds__(RS_THREADS) dlka_resample_spline_pad_kernel(RsPad a, const T *x, double *p)
-{
-    const long q = (long)blockIdx.x * RS_THREADS + threadIdx.x;
-    if (q >= a.cells) return;
-    const int pw = (int)(q % a.ext[2]);
-    const int ph = (int)((q / a.ext[2]) % a.ext[1]);
-    const int pd = (int)(q / ((long)a.ext[2] * a.ext[1]));
-    const int sw = min(max(pw - a.pad[2], 0), a.in[2] - 1);
-    const int sh = min(max(ph - a.pad[1], 0), a.in[1] - 1);
-    const int sd = min(max(pd - a.pad[0], 0), a.in[0] - 1);
-    p[q] = (double)x[((long)sd * a.in[1] + sh) * a.in[2] + sw];
-}
-
-// Cubic B-spline prefilter of every line along `axis`, in place: gain, causal pass from the 'reflect' start value, anti-causal pass
-// (scipy.ndimage.spline_filter1d, which treats 'nearest' as 'reflect' on the padded array).  One lane per line.
-__global__ void __launch_bounds__(RS_THREADS) dlka_resample_spline_prefilter_kernel(double *p, int e0, int e1, int e2, int axis)
-{
-#pragma clang fp contract(off)
-    const int ext[3] = {e0, e1, e2};
-    const long stride[3] = {(long)e1 * e2, (long)e2, 1L};
-    const int n = ext[axis];
-    const int ua = axis == 0 ? 1 : 0, ub = axis == 2 ? 1 : 2;   // the two other axes
-    const long lines = (long)ext[ua] * ext[ub];
-    const long q = (long)blockIdx.x * RS_THREADS + threadIdx.x;
-    if (q >= lines || n < 2) return;
-    double *c = p + (q / ext[ub]) * stride[ua] + (q % ext[ub]) * stride[ub];
-    const long s = stride[axis];
-    const double z = -0.26794919243112270647;   // sqrt(3) - 2
-    const double gain = (1.0 - z) * (1.0 - 1.0 / z);
-    for (int i = 0; i < n; ++i) c[i * s] *= gain;
-    double z_n = 1.0;
-    for (int i = 0; i < n; ++i) z_n *= z;
-    double z_i = z;
-    const double c0 = c[0];
-    double acc = c0 + z_n * c[(long)(n - 1) * s];
-    for (int i = 1; i < n; ++i) {
-        acc += z_i * (c[i * s] + z_n * c[(long)(n - 1 - i) * s]);
-        z_i *= z;
-    }
-    acc *= z / (1.0 - z_n * z_n);
-    c[0] = acc + c0;
-    for (int i = 1; i < n; ++i) c[i * s] += z * c[(long)(i - 1) * s];
-    c[(long)(n - 1) * s] *= z / (z - 1.0);
-    for (int i = n - 2; i >= 0; --i) c[i * s] = z * (c[(long)(i + 1) * s] - c[i * s]);
-}
-
 // Separable evaluation on the coefficients: per axis taps[ax] (1 or 4) cells from start[] with the weights w4[], then the clip to [lo, hi] of
 // the volume (clip_axis < 0) or of the slice along clip_axis.
 __global__ void __launch_bounds__(RS_THREADS) dlka_resample_spline_eval_kernel(RsArgs a, const double *coef, double *y, const int *start,
@@ -366,49 +312,6 @@ extern "C" int dlka_resample_labels(const int32_t *seg, int32_t *out, const dlka
     g_rs_launches.fetch_add(1, std::memory_order_relaxed);
     DLKA_LAUNCH(dlka_resample_labels_kernel, dim3((unsigned)cdivl((long)a.C * a.out_cells, RS_THREADS)), dim3(RS_THREADS), 0,
                 (hipStream_t)stream, a, seg, out, idx, w, strict);
-    DLKA_CHECK_LAUNCH();
-    return DLKA_OK;
-}
-
-extern "C" int dlka_resample_spline_pad(const void *x, double *padded, int dtype, const int64_t *in, const int64_t *pad, void *stream)
-{
-    if (!x || !padded || !in || !pad) return DLKA_ERR_NULL;
-    if (dtype != DLKA_F32 && dtype != DLKA_F64) return DLKA_ERR_DTYPE;
-    RsPad a;
-    a.cells = 1;
-    for (int ax = 0; ax < 3; ++ax) {
-        if (in[ax] < 1 || pad[ax] < 0) return DLKA_ERR_SHAPE;
-        if (pad[ax] > RS_PAD_MAX || in[ax] > 0x7fffffffL - 2 * RS_PAD_MAX) return DLKA_ERR_UNSUPPORTED;
-        a.in[ax] = (int)in[ax];
-        a.pad[ax] = (int)pad[ax];
-        a.ext[ax] = (int)(in[ax] + 2 * pad[ax]);
-        a.cells *= a.ext[ax];
-        if (a.cells > 0x7fffffffL) return DLKA_ERR_UNSUPPORTED;
-    }
-    g_rs_launches.fetch_add(1, std::memory_order_relaxed);
-    const dim3 grid((unsigned)cdivl(a.cells, RS_THREADS)), block(RS_THREADS);
-    if (dtype == DLKA_F32)
-        DLKA_LAUNCH(dlka_resample_spline_pad_kernel<float>, grid, block, 0, (hipStream_t)stream, a, (const float *)x, padded);
-    else
-        DLKA_LAUNCH(dlka_resample_spline_pad_kernel<double>, grid, block, 0, (hipStream_t)stream, a, (const double *)x, padded);
-    DLKA_CHECK_LAUNCH();
-    return DLKA_OK;
-}
-
-extern "C" int dlka_resample_spline_prefilter(double *coef, const int64_t *ext, int axis, void *stream)
-{
-    if (!coef || !ext) return DLKA_ERR_NULL;
-    if (axis < 0 || axis > 2) return DLKA_ERR_SHAPE;
-    long cells = 1;
-    for (int ax = 0; ax < 3; ++ax) {
-        if (ext[ax] < 1) return DLKA_ERR_SHAPE;
-        if (ext[ax] > 0x7fffffffL) return DLKA_ERR_UNSUPPORTED;
-        cells *= ext[ax];
-        if (cells > 0x7fffffffL) return DLKA_ERR_UNSUPPORTED;
-    }
-    g_rs_launches.fetch_add(1, std::memory_order_relaxed);
-    DLKA_LAUNCH(dlka_resample_spline_prefilter_kernel, dim3((unsigned)cdivl(cells / ext[axis], RS_THREADS)), dim3(RS_THREADS), 0,
-                (hipStream_t)stream, coef, (int)ext[0], (int)ext[1], (int)ext[2], axis);
     DLKA_CHECK_LAUNCH();
     return DLKA_OK;
 }

@@ -8,7 +8,7 @@
 // host (deformablelka_amd/inference2d.py), so the rounding of that product, including the pairs for which the last coordinate exceeds n - 1 by
 // one ulp and the whole last row or column is 0 (512 -> 224), is scipy's and the kernels never form a coordinate.
 //
-//   spline    (a) a stack of slices through 4 x 4 taps on float64 B-spline coefficients (prefiltered by dlka_augment_spline_prefilter_mirror along
+//   spline    (a) a stack of slices through 4 x 4 taps on float64 B-spline coefficients (cl_spline.hip's 'mirror' prefilter along
 //             axes 1 and 2 of the stack), or 2 x 2 taps on the raw values (order 1).  A lane owns ZM_VPT output pixels that are neighbours along
 //             W, holds their column tables (mirrored tap indices and weights) in registers and walks ZM_ROWS output rows with them; the sum is
 //             scipy's, t += (c * w_row) * w_col with the rows outermost, rounded once to float32, then optionally (v - mean) / std in float32 (one

@@ -31,6 +31,7 @@ import torch
 from . import _lib as L
 from . import metrics as M
 from . import ops
+from ._containers import cubic_bspline_weights, to_working_device
 
 __all__ = ["zoom", "zoom_slices", "resize_sample", "predict_volume", "test_single_volume", "inference"]
 
@@ -39,25 +40,19 @@ _SPLINE_DTYPES = (torch.float32, torch.bfloat16, torch.int16)
 
 # ---- containers ------------------------------------------------------------------------------------------------------------------------------
 def _load(x, what):
-    """(tensor on the working device, function that gives a result tensor the container and device the caller expects)."""
+    """(tensor on the working device, function that gives a result tensor the container and device the caller expects).  Not the shared
+    ``load``: a result whose dtype the call changed keeps it, and bfloat16 has no way back to numpy."""
+    t = to_working_device(x, "inference2d", what, "iuf")
     if isinstance(x, torch.Tensor):
-        t = x.detach()
-
         def back(r):
             return r.to(device=x.device)
     else:
-        a = np.asarray(x)
-        if a.dtype.kind not in "iuf":
-            raise RuntimeError(f"inference2d: {what} is an integer or floating array, got {a.dtype}")
-        src = a.astype(np.int64) if a.dtype.kind == "u" and a.dtype.itemsize > 1 else a
-        t = torch.from_numpy(np.ascontiguousarray(src))
+        a_dtype = np.asarray(x).dtype
 
         def back(r):
             if r.dtype == torch.bfloat16:
                 raise RuntimeError("inference2d: numpy has no bfloat16; pass a tensor")
-            return r.cpu().numpy().astype(a.dtype, copy=False) if r.dtype == t.dtype else r.cpu().numpy()
-    if not L._test_backend and not t.is_cuda and torch.cuda.is_available():
-        t = t.cuda()
+            return r.cpu().numpy().astype(a_dtype, copy=False) if r.dtype == t.dtype else r.cpu().numpy()
     return t, back
 
 
@@ -78,11 +73,7 @@ def _axis_table(n, m, order):
         w = np.stack([1.0 - y, y], 1)
         first = lo.astype(np.int64)
     else:
-        z = 1.0 - y
-        w1 = (y * y * (y - 2.0) * 3.0 + 4.0) / 6.0
-        w2 = (z * z * (z - 2.0) * 3.0 + 4.0) / 6.0
-        w0 = z * z * z / 6.0
-        w = np.stack([w0, w1, w2, 1.0 - w0 - w1 - w2], 1)
+        w = cubic_bspline_weights(y)
         first = lo.astype(np.int64) - 1
     return np.where(outside, L.DLKA_ZOOM2D_OUTSIDE, first), w
 

@@ -20,21 +20,13 @@ import torch
 
 from . import _lib as L
 from . import ops
+from ._containers import to_working_device
 
 __all__ = ["dc", "hd", "hd95", "asd", "assd", "surface_metrics", "surface_distances", "calculate_metric_percase", "evaluate_label_maps"]
 
 
 def _as_tensor(x):
-    if isinstance(x, torch.Tensor):
-        t = x.detach()
-    else:
-        a = np.asarray(x)
-        if a.dtype.kind == "u" and a.dtype.itemsize > 1:
-            a = a.astype(np.int64)
-        t = torch.from_numpy(np.ascontiguousarray(a))
-    if not L._test_backend and not t.is_cuda and torch.cuda.is_available():
-        t = t.cuda()
-    return t
+    return to_working_device(x, "metrics", "input", kinds=None)   # medpy takes whatever numpy.asarray takes: no dtype refusal here
 
 
 def _as_mask(x):
@@ -44,8 +36,10 @@ def _as_mask(x):
 
 
 def _as_labels(x):
+    """Rule of this module: a floating value that is no integer becomes -1, which is no class (postprocessing maps it to 0, resampling
+    raises): keep the three apart."""
     t = _as_tensor(x)
-    if t.is_floating_point():   # a value that is no integer is no class
+    if t.is_floating_point():
         t = torch.where(t == t.round(), t, torch.full_like(t, -1)).to(torch.int64)
     elif t.dtype == torch.int8:
         t = t.to(torch.int16)

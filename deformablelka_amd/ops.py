@@ -1227,6 +1227,7 @@ def cc_launch_count() -> int:
 
 # ---- resampling of probabilities, images and label maps (include/dlka.h: dlka_resample_*) ---------------------------------------------------
 _RS_DTYPES = {torch.float32: L.DLKA_F32, torch.float64: L.DLKA_F64}
+_I3 = ctypes.c_int64 * 3   # three extents, as the entries below take them
 
 
 def _rs_desc(x, out, taps, tap_hi, dtype=None):
@@ -1315,6 +1316,28 @@ def resample_labels(seg, out, tables, strict=False):
     return y
 
 
+def spline_coefficients(x, pad, boundary, axes, out=None):
+    """float64 cubic B-spline coefficients of ONE volume ``x`` (x, y, z; float32 / float64) as scipy.ndimage.spline_filter prepares them:
+    ``pad[ax]`` edge samples on both sides (all 0: the cast alone) in one launch, then ``spline_prefilter``.  ``out``: where to write."""
+    L.require_device(x, out)
+    x, ext = x.contiguous(), [int(n) + 2 * int(p) for n, p in zip(x.shape, pad)]
+    out = torch.empty(ext, dtype=torch.float64, device=x.device) if out is None else out
+    if x.ndim != 3 or x.dtype not in _RS_DTYPES or list(out.shape) != ext or out.device != x.device:
+        raise RuntimeError(f"spline: one float32 / float64 volume (x, y, z) and room for {ext}, got {tuple(x.shape)} {x.dtype}, {tuple(out.shape)}")
+    L.check(L.get_lib().dlka_spline_pad(L.ptr(x), L.ptr(out), _RS_DTYPES[x.dtype], _I3(*x.shape), _I3(*pad), L.stream_ptr(x)), "spline_pad")
+    return spline_prefilter(out, boundary, axes)
+
+
+def spline_prefilter(coef, boundary, axes):
+    """In place: one launch per axis in ``axes`` with the start values of ``boundary`` (DLKA_SPLINE_REFLECT / DLKA_SPLINE_MIRROR)."""
+    L.require_device(coef)
+    if coef.ndim != 3 or coef.dtype != torch.float64 or not coef.is_contiguous():
+        raise RuntimeError(f"spline: a contiguous float64 volume (x, y, z), got {tuple(coef.shape)} {coef.dtype}")
+    for ax in axes:
+        L.check(L.get_lib().dlka_spline_prefilter(L.ptr(coef), _I3(*coef.shape), int(ax), int(boundary), L.stream_ptr(coef)), "spline_prefilter")
+    return coef
+
+
 def resample_spline(x, out, tables, pad, lo, hi, clip_axis=-1):
     """One channel ``x`` (x, y, z; float32 / float64) through the cubic B-spline: ``pad[ax]`` edge samples on both sides and the prefilter on
     every axis with pad[ax] > 0, then the evaluation by the per-axis tables (first cell in the padded array, 4 weights; or 1 weight on an
@@ -1323,18 +1346,11 @@ def resample_spline(x, out, tables, pad, lo, hi, clip_axis=-1):
     L.require_device(x, lo, hi)
     if x.ndim != 3 or x.dtype not in _RS_DTYPES:
         raise RuntimeError(f"resample: one float32 / float64 channel (x, y, z), got {tuple(x.shape)} {x.dtype}")
-    x = x.contiguous()
     pad = [int(p) for p in pad]
     ext = [int(n) + 2 * p for n, p in zip(x.shape, pad)]
     if ext[0] * ext[1] * ext[2] >= 2 ** 31:
         raise RuntimeError("resample: fewer than 2^31 cells per padded channel")
-    lib, st = L.get_lib(), L.stream_ptr(x)
-    coef = torch.empty(ext, dtype=torch.float64, device=x.device)
-    i3 = ctypes.c_int64 * 3
-    L.check(lib.dlka_resample_spline_pad(L.ptr(x), L.ptr(coef), _RS_DTYPES[x.dtype], i3(*x.shape), i3(*pad), st), "resample_spline_pad")
-    for ax in range(3):
-        if pad[ax] > 0:
-            L.check(lib.dlka_resample_spline_prefilter(L.ptr(coef), i3(*ext), ax, st), "resample_spline_prefilter")
+    coef = spline_coefficients(x, pad, L.DLKA_SPLINE_REFLECT, [ax for ax in range(3) if pad[ax] > 0])
     taps = [np.asarray(w).shape[1] for _, w in tables]
     d, out = _rs_desc(coef[None], out, taps, 4)
     n_clip = 1 if clip_axis < 0 else out[clip_axis]
@@ -1342,8 +1358,8 @@ def resample_spline(x, out, tables, pad, lo, hi, clip_axis=-1):
         raise RuntimeError(f"resample: {n_clip} float64 clip bounds expected")
     ci, wi = _rs_tables(coef[None], tables, out, 4, True)
     y = torch.empty(out, dtype=torch.float64, device=x.device)
-    L.check(lib.dlka_resample_spline_eval(L.ptr(coef), L.ptr(y), ctypes.byref(d), L.ptr(ci), L.ptr(wi), L.ptr(lo.contiguous()),
-                                          L.ptr(hi.contiguous()), int(clip_axis), st), "resample_spline_eval")
+    L.check(L.get_lib().dlka_resample_spline_eval(L.ptr(coef), L.ptr(y), ctypes.byref(d), L.ptr(ci), L.ptr(wi), L.ptr(lo.contiguous()),
+                                                  L.ptr(hi.contiguous()), int(clip_axis), L.stream_ptr(x)), "resample_spline_eval")
     return y
 
 
@@ -1393,22 +1409,14 @@ def augment_spline_coefficients(x, mode):
     with the 'mirror' ones.  Returns (coefficients (b, c, x + 2 pad, ...), pad)."""
     x = _aug_volume(x, "data")
     src = x if x.dtype in _RS_DTYPES else x.to(torch.float64 if x.dtype == torch.int16 else torch.float32)
-    pad = L.DLKA_RESAMPLE_SPLINE_PAD if mode == L.DLKA_AUG_NEAREST else 0
+    pad, boundary = (L.DLKA_RESAMPLE_SPLINE_PAD, L.DLKA_SPLINE_REFLECT) if mode == L.DLKA_AUG_NEAREST else (0, L.DLKA_SPLINE_MIRROR)
     ext = [int(n) + 2 * pad for n in x.shape[2:]]
     if ext[0] * ext[1] * ext[2] >= 2 ** 31:
         raise RuntimeError("augment: fewer than 2^31 cells per padded channel")
-    lib, st = L.get_lib(), L.stream_ptr(x)
     coef = torch.empty([x.shape[0], x.shape[1]] + ext, dtype=torch.float64, device=x.device)
-    i3 = ctypes.c_int64 * 3
     for b in range(x.shape[0]):
         for c in range(x.shape[1]):
-            L.check(lib.dlka_resample_spline_pad(L.ptr(src[b, c]), L.ptr(coef[b, c]), _RS_DTYPES[src.dtype], i3(*x.shape[2:]), i3(pad, pad, pad), st),
-                    "resample_spline_pad")
-            for ax in range(3):
-                if mode == L.DLKA_AUG_NEAREST:
-                    L.check(lib.dlka_resample_spline_prefilter(L.ptr(coef[b, c]), i3(*ext), ax, st), "resample_spline_prefilter")
-                else:
-                    L.check(lib.dlka_augment_spline_prefilter_mirror(L.ptr(coef[b, c]), i3(*ext), ax, st), "augment_spline_prefilter_mirror")
+            spline_coefficients(src[b, c], (pad, pad, pad), boundary, range(3), out=coef[b, c])
     return coef, pad
 
 
@@ -1456,10 +1464,9 @@ def augment_gaussian(x, radius, weights):
     if radius.shape != (n,) or weights.shape != (n, L.DLKA_AUG_RADIUS_MAX + 1) or radius.max() > L.DLKA_AUG_RADIUS_MAX:
         raise RuntimeError(f"augment: {n} radii of at most {L.DLKA_AUG_RADIUS_MAX} and their weight rows expected")
     r, w = torch.from_numpy(radius).to(x.device), torch.from_numpy(weights).to(x.device)
-    i3 = ctypes.c_int64 * 3
     for ax in range(3):
         y = torch.empty_like(x)
-        L.check(L.get_lib().dlka_augment_gaussian(L.ptr(x), L.ptr(y), _AUG_DTYPES[x.dtype], n, i3(*x.shape[2:]), ax, L.ptr(r), L.ptr(w),
+        L.check(L.get_lib().dlka_augment_gaussian(L.ptr(x), L.ptr(y), _AUG_DTYPES[x.dtype], n, _I3(*x.shape[2:]), ax, L.ptr(r), L.ptr(w),
                                                   L.stream_ptr(x)), "augment_gaussian")
         x = y
     return x
@@ -1513,8 +1520,7 @@ def augment_pointwise(x, steps, noise=None, stats0=None, stats1=None, flip=None)
         f = torch.from_numpy(flip).to(x.device)
     t = torch.from_numpy(table).to(x.device)
     y = torch.empty_like(x)
-    i3 = ctypes.c_int64 * 3
-    L.check(L.get_lib().dlka_augment_pointwise(L.ptr(x), L.ptr(noise), L.ptr(y), _AUG_DTYPES[x.dtype], x.shape[0], x.shape[1], i3(*x.shape[2:]),
+    L.check(L.get_lib().dlka_augment_pointwise(L.ptr(x), L.ptr(noise), L.ptr(y), _AUG_DTYPES[x.dtype], x.shape[0], x.shape[1], _I3(*x.shape[2:]),
                                                L.ptr(t), L.ptr(stats0), L.ptr(stats1), L.ptr(f), L.stream_ptr(x)), "augment_pointwise")
     return y
 
@@ -1702,18 +1708,11 @@ def zoom2d_coefficients(x):
     """float64 cubic B-spline coefficients of every slice of ``x`` (n, h, w) as scipy.ndimage.zoom prepares them under mode 'constant': the
     'mirror' prefilter of the slice itself, no padding.  The stack is filtered as ONE volume along axes 1 and 2: three launches whatever n."""
     x = _zm_stack(x)
-    lib, st = L.get_lib(), L.stream_ptr(x)
-    i3 = ctypes.c_int64 * 3
     if x.dtype in _RS_DTYPES:
-        coef = torch.empty(x.shape, dtype=torch.float64, device=x.device)
-        L.check(lib.dlka_resample_spline_pad(L.ptr(x), L.ptr(coef), _RS_DTYPES[x.dtype], i3(*x.shape), i3(0, 0, 0), st), "resample_spline_pad")
-    elif x.dtype in (torch.bfloat16, torch.int16):
-        coef = x.to(torch.float64)
-    else:
-        raise RuntimeError(f"zoom2d: float32, float64, bfloat16 or int16 slices, got {x.dtype}")
-    for ax in (1, 2):
-        L.check(lib.dlka_augment_spline_prefilter_mirror(L.ptr(coef), i3(*x.shape), ax, st), "augment_spline_prefilter_mirror")
-    return coef
+        return spline_coefficients(x, (0, 0, 0), L.DLKA_SPLINE_MIRROR, (1, 2))
+    if x.dtype in (torch.bfloat16, torch.int16):             # torch's cast: the pad kernel reads float32 / float64 only
+        return spline_prefilter(x.to(torch.float64), L.DLKA_SPLINE_MIRROR, (1, 2))
+    raise RuntimeError(f"zoom2d: float32, float64, bfloat16 or int16 slices, got {x.dtype}")
 
 
 def zoom2d_spline(src, out_hw, start, w4, taps, out_dtype, mean=None, std=None):

@@ -21,36 +21,16 @@ import torch
 
 from . import _lib as L
 from . import ops
+from ._containers import load
 
 __all__ = ["label", "component_sizes", "remove_all_but_the_largest_connected_component"]
 
 _MAX_COUNT = 2 ** 31 - 1     # a map has fewer than 2^31 cells
 
 
-def _load(x):
-    """(tensor on the working device, function that gives a result tensor the container, device and ``dtype`` the caller expects)."""
-    if isinstance(x, torch.Tensor):
-        t = x.detach()
-
-        def back(r, dtype=None):
-            return r.to(device=x.device, dtype=x.dtype if dtype is None else dtype)
-    else:
-        a = np.asarray(x)
-        if a.dtype.kind not in "biuf":
-            raise RuntimeError(f"postprocessing: label maps are integer, bool or floating arrays, got {a.dtype}")
-        src = a.astype(np.int64) if a.dtype.kind == "u" and a.dtype.itemsize > 1 else a
-        t = torch.from_numpy(np.ascontiguousarray(src))
-
-        def back(r, dtype=None):
-            out = r.cpu().numpy()
-            return out.astype(a.dtype if dtype is None else dtype, copy=False)
-    if not L._test_backend and not t.is_cuda and torch.cuda.is_available():
-        t = t.cuda()
-    return t, back
-
-
 def _as_classes(t):
-    """The map in a dtype the kernels read.  A floating value that is no integer is no class: background."""
+    """The map in a dtype the kernels read.  Rule of this module: a floating value that is no integer is no class and becomes 0, background
+    (metrics maps it to -1, resampling raises): keep the three apart."""
     if t.dtype in ops._SD_DTYPES:
         return t
     if t.dtype == torch.int8:
@@ -70,7 +50,7 @@ def _as_object(t):
 
 
 def _label(input, connectivity):
-    t, back = _load(input)
+    t, back = load(input, "postprocessing", "label maps", plural=True)
     labels, _, summary, state = ops.cc_components(_as_object(t), None, connectivity, want_filtered=False)
     return labels, int(summary[0].item()), state, back
 
@@ -79,15 +59,14 @@ def label(input, connectivity=1):
     """scipy.ndimage.label(input, generate_binary_structure(input.ndim, connectivity)): (labels int32, num_features int).  Objects are numbered in
     raster order of their first cell, as scipy numbers them."""
     labels, n, _, back = _label(input, connectivity)
-    return back(labels, torch.int32 if isinstance(input, torch.Tensor) else np.int32), n
+    return back(labels, torch.int32), n
 
 
 def component_sizes(input, connectivity=1):
     """(labels int32, sizes int64 (num_features,)): sizes[k] is the cell count of object k + 1."""
     labels, n, state, back = _label(input, connectivity)
     sizes, _ = ops.cc_component_table(state, n)
-    tensor = isinstance(input, torch.Tensor)
-    return back(labels, torch.int32 if tensor else np.int32), back(sizes, torch.int64 if tensor else np.int64)
+    return back(labels, torch.int32), back(sizes, torch.int64)
 
 
 def _min_count(min_size, volume_per_voxel):
@@ -132,7 +111,7 @@ def remove_all_but_the_largest_connected_component(image, for_which_classes, vol
     vpv = float(volume_per_voxel)
     if not (vpv > 0.0 and math.isfinite(vpv)):
         raise ValueError(f"postprocessing: volume_per_voxel must be positive and finite, got {volume_per_voxel}")
-    t, back = _load(image)
+    t, back = load(image, "postprocessing", "label maps", plural=True)
     work = _as_classes(t)
     if for_which_classes is None:
         for_which_classes = [int(v) for v in torch.unique(work).cpu().tolist() if v > 0]

@@ -22,35 +22,11 @@ import copy
 import numpy as np
 import torch
 
-from . import _lib as L
 from . import ops
+from ._containers import load
 from .resampling import RESAMPLING_SEPARATE_Z_ANISO_THRESHOLD, resample_patient
 
 __all__ = ["create_nonzero_mask", "get_bbox_from_mask", "crop_to_bbox", "crop_to_nonzero", "ImageCropper", "GenericPreprocessor"]
-
-
-# ---- containers ------------------------------------------------------------------------------------------------------------------------------
-def _load(x, what):
-    """(tensor on the working device, function that gives a result tensor the container, device and ``dtype`` the caller expects)."""
-    if isinstance(x, torch.Tensor):
-        t = x.detach()
-
-        def back(r, dtype=None):
-            return r.to(device=x.device, dtype=x.dtype if dtype is None else dtype)
-    else:
-        a = np.asarray(x)
-        if a.dtype.kind not in "biuf":
-            raise RuntimeError(f"preprocessing: {what} is an integer, bool or floating array, got {a.dtype}")
-        src = a.astype(np.int64) if a.dtype.kind == "u" and a.dtype.itemsize > 1 else a
-        t = torch.from_numpy(np.ascontiguousarray(src))
-
-        def back(r, dtype=None):
-            if dtype is None:
-                return r.cpu().numpy().astype(a.dtype, copy=False)
-            return r.to(dtype).cpu().numpy()
-    if not L._test_backend and not t.is_cuda and torch.cuda.is_available():
-        t = t.cuda()
-    return t, back
 
 
 def _spatial_rank(shape, what):
@@ -68,7 +44,7 @@ def _box_list(box, rank):
 
 
 def _seg_to_device(seg, data_t):
-    t, back = _load(seg, "seg")
+    t, back = load(seg, "preprocessing", "seg")
     if tuple(t.shape[1:]) != tuple(data_t.shape[1:]) or t.ndim != data_t.ndim:
         raise ValueError(f"preprocessing: seg {tuple(t.shape)} does not have the extents of data {tuple(data_t.shape)}")
     return t.to(device=data_t.device, dtype=torch.int32), back
@@ -78,7 +54,7 @@ def _seg_to_device(seg, data_t):
 def create_nonzero_mask(data):
     """cropping.py:23-31: the cells that are nonzero in any channel, holes filled (scipy.ndimage.binary_fill_holes, default structure): bool."""
     _spatial_rank(data.shape, "data")
-    t, back = _load(data, "data")
+    t, back = load(data, "preprocessing", "data")
     if t.dtype != torch.float32:          # only "!= 0" matters, and a cast could round a small value to 0
         t = (t != 0).to(torch.float32)
     mask, _ = ops.prep_nonzero_mask(t)
@@ -89,7 +65,7 @@ def get_bbox_from_mask(mask, outside_value=0):
     """cropping.py:34-42: [[lo, hi], ...] per axis of the cells that differ from ``outside_value``, as Python ints."""
     if len(mask.shape) not in (2, 3):
         raise NotImplementedError(f"preprocessing: a mask of rank 2 or 3, got {tuple(mask.shape)}")
-    t, _ = _load(mask, "mask")
+    t, _ = load(mask, "preprocessing", "mask")
     return _box_list(ops.prep_mask_bbox((t != outside_value).to(torch.uint8)), t.ndim)
 
 
@@ -112,7 +88,7 @@ def crop_to_nonzero(data, seg=None, nonzero_label=-1):
     """cropping.py:84-116: (data, seg, bbox).  Outside the nonzero mask the label map gets ``nonzero_label`` wherever it is 0; without a seg it is
     ``nonzero_label`` there and 0 inside (int64).  Data with nothing nonzero raises ValueError, as numpy's min of an empty array does."""
     _spatial_rank(data.shape, "data")
-    t, back = _load(data, "data")
+    t, back = load(data, "preprocessing", "data")
     seg_t, seg_back = (None, None) if seg is None else _seg_to_device(seg, t)
     out, seg_out, bbox = _crop(t.to(torch.float32), seg_t, nonzero_label, False)
     if seg is None:
@@ -139,7 +115,7 @@ class ImageCropper(object):
     def _crop(data, properties, seg, nan_to_zero):
         """``crop`` that also hands on the device tensors (float32, int32) for the next stage."""
         _spatial_rank(data.shape, "data")
-        t, back = _load(data, "data")
+        t, back = load(data, "preprocessing", "data")
         seg_t, seg_back = (None, None) if seg is None else _seg_to_device(seg, t)
         out, seg_out, bbox = _crop(t.to(torch.float32), seg_t, -1, nan_to_zero)
         classes = torch.unique(seg_out).cpu().numpy()
@@ -204,7 +180,7 @@ class GenericPreprocessor(object):
         computed in float64 and used (rounded to float32) for the CT2 and nonCT channels; a CT channel has (0, given mean, given sd)."""
         if len(data.shape) != 4:
             raise NotImplementedError(f"preprocessing: normalize takes (C, X, Y, Z) data, got {tuple(data.shape)}")
-        t, back = _load(data, "data")
+        t, back = load(data, "preprocessing", "data")
         seg_t = None if seg is None else _seg_to_device(seg, t)[0]
         out, table = self._normalize(t.to(torch.float32), seg_t)
         return back(out), back(table[:, [6, 3, 4]], torch.float64)
@@ -229,7 +205,7 @@ class GenericPreprocessor(object):
         values.  Returns (data, seg, properties); ``properties`` is a copy with ``size_after_resampling`` and ``spacing_after_resampling``."""
         if len(data.shape) != 4:
             raise NotImplementedError(f"preprocessing: resample_and_normalize takes (C, X, Y, Z) data, got {tuple(data.shape)}")
-        t, back = _load(data, "data")
+        t, back = load(data, "preprocessing", "data")
         seg_t, seg_back = (None, None) if seg is None else _seg_to_device(seg, t)
         out, seg_out, properties = self._resample_and_normalize(t.to(torch.float32), seg_t, target_spacing, properties, force_separate_z, False)
         return back(out), None if seg is None else seg_back(seg_out), properties
@@ -244,10 +220,10 @@ class GenericPreprocessor(object):
         perm = (0, *[i + 1 for i in self.transpose_forward])
         t, seg_t = t.permute(perm).contiguous(), seg_t.permute(perm).contiguous()
         out, seg_out, properties = self._resample_and_normalize(t, seg_t, target_spacing, properties, force_separate_z, True)
-        _, back = _load(data, "data")
+        _, back = load(data, "preprocessing", "data")
         if seg is None:
             return back(out, torch.float32), back(seg_out, torch.int64), properties
-        return back(out, torch.float32), _load(seg, "seg")[1](seg_out), properties
+        return back(out, torch.float32), load(seg, "preprocessing", "seg")[1](seg_out), properties
 
     def preprocess_test_case(self, data_files, target_spacing, seg_file=None, force_separate_z=None):
         """preprocessing.py:308-316 with cropping.py:61-81: reads the files with SimpleITK, then ``preprocess_arrays``."""

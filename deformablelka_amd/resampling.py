@@ -23,6 +23,7 @@ import torch
 
 from . import _lib as L
 from . import ops
+from ._containers import cubic_bspline_weights, load
 
 __all__ = ["RESAMPLING_SEPARATE_Z_ANISO_THRESHOLD", "get_do_separate_z", "get_lowres_axis", "resample_patient", "resample_data_or_seg",
            "resample_and_argmax", "segmentation_from_softmax"]
@@ -38,30 +39,6 @@ def get_do_separate_z(spacing, anisotropy_threshold=RESAMPLING_SEPARATE_Z_ANISO_
 def get_lowres_axis(new_spacing):
     """preprocessing.py:33-35: the axes whose spacing is the largest."""
     return np.where(max(new_spacing) / np.array(new_spacing) == 1)[0]
-
-
-# ---- containers ------------------------------------------------------------------------------------------------------------------------------
-def _load(x, what):
-    """(tensor on the working device, function that gives a result tensor the container and device the caller expects)."""
-    if isinstance(x, torch.Tensor):
-        t = x.detach()
-
-        def back(r, dtype=None):
-            return r.to(device=x.device, dtype=x.dtype if dtype is None else dtype)
-    else:
-        a = np.asarray(x)
-        if a.dtype.kind not in "biuf":
-            raise RuntimeError(f"resampling: {what} is an integer, bool or floating array, got {a.dtype}")
-        src = a.astype(np.int64) if a.dtype.kind == "u" and a.dtype.itemsize > 1 else a
-        t = torch.from_numpy(np.ascontiguousarray(src))
-
-        def back(r, dtype=None):
-            if dtype is None:
-                return r.cpu().numpy().astype(a.dtype, copy=False)
-            return r.to(dtype).cpu().numpy()
-    if not L._test_backend and not t.is_cuda and torch.cuda.is_available():
-        t = t.cuda()
-    return t, back
 
 
 # ---- tables: float64 on the host, as scipy.ndimage computes them ----------------------------------------------------------------------------
@@ -85,12 +62,7 @@ def _cubic_table(n_in, n_out):
     """First of the four cells in the array padded by DLKA_RESAMPLE_SPLINE_PAD, and the cubic B-spline weights."""
     c = _coordinates(n_in, n_out) + float(L.DLKA_RESAMPLE_SPLINE_PAD)
     lo = np.floor(c)
-    y = c - lo
-    z = 1.0 - y
-    w1 = (y * y * (y - 2.0) * 3.0 + 4.0) / 6.0
-    w2 = (z * z * (z - 2.0) * 3.0 + 4.0) / 6.0
-    w0 = z * z * z / 6.0
-    return lo.astype(np.int64) - 1, np.stack([w0, w1, w2, 1.0 - w0 - w1 - w2], 1)
+    return lo.astype(np.int64) - 1, cubic_bspline_weights(c - lo)
 
 
 def _identity_table(n, width):
@@ -164,6 +136,7 @@ def _resample_values(t, new_shape, orders, sep_axis):
 
 
 def _as_labels(t):
+    # rule of this module: a floating value that is no integer is an error (metrics maps it to -1, postprocessing to 0): keep the three apart
     if t.is_floating_point():
         if not bool((t == t.round()).all()):
             raise NotImplementedError("resampling: is_seg=True takes integer-valued label maps")
@@ -203,7 +176,7 @@ def resample_data_or_seg(data, new_shape, is_seg, axis=None, order=3, do_separat
     assert len(data.shape) == 4, "data must be (c, x, y, z)"
     _check_orders(order, order_z, is_seg, do_separate_z)
     new_shape = _new_shape(new_shape)
-    t, back = _load(data, "data")
+    t, back = load(data, "resampling", "data")
     if tuple(t.shape[1:]) == new_shape:
         return back(t)
     orders, sep_axis = _axis_orders(order, order_z, do_separate_z, axis)
@@ -261,7 +234,7 @@ def resample_and_argmax(probabilities, new_shape, axis=None, order=1, do_separat
     channel is > 0.5) — as ONE kernel that keeps the running maximum in registers: uint8 (x', y', z').  Ties go to the first maximum, as in
     numpy.  order and order_z: 0 or 1."""
     assert len(probabilities.shape) == 4, "data must be (c, x, y, z)"
-    t, _ = _load(probabilities, "probabilities")
+    t, _ = load(probabilities, "resampling", "probabilities")
     seg = _argmax(t, _new_shape(new_shape), axis, order, do_separate_z, order_z, regions_class_order)
     return seg.to(probabilities.device) if isinstance(probabilities, torch.Tensor) else seg.cpu().numpy()
 
@@ -273,7 +246,7 @@ def segmentation_from_softmax(segmentation_softmax, properties_dict, order=1, re
     ``size_after_cropping``, and the placement into ``crop_bbox`` (upper bounds clamped to the volume as the reference clamps them).
     ``properties_dict`` is not modified."""
     assert len(segmentation_softmax.shape) == 4, "data must be (c, x, y, z)"
-    t, _ = _load(segmentation_softmax, "segmentation_softmax")
+    t, _ = load(segmentation_softmax, "resampling", "segmentation_softmax")
     tensor = isinstance(segmentation_softmax, torch.Tensor)
     shape_after_cropping = tuple(int(v) for v in properties_dict.get('size_after_cropping'))
     do_separate_z, lowres_axis = False, None

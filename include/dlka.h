@@ -780,12 +780,12 @@ long dlka_cc_launch_count(void);
  * arithmetic in the same order, so the argmax of its output is dlka_resample_argmax's map bit for bit.  dtype: DLKA_F32 or DLKA_F64.
  * dlka_resample_labels (resize_segmentation as :127, :153-158, :196 bind it; strict != 0: the z step of :180-187): int32 maps; per output cell
  * the largest label whose summed weight is >= 0.5 (strict: > 0.5) among the source cells, 0 when there is none.
- * dlka_resample_spline_pad / _prefilter / _eval (order 3, :130-131 with :153-158 or :196): float64; pad[ax] edge samples on both sides, the
- * cubic B-spline prefilter in place along one axis of ext[3], the 4-tap evaluation of one channel clipped to [lo[s], hi[s]], s = the output
- * index along clip_axis, or 0 when clip_axis < 0.
- * One launch each, no atomics: results are bitwise reproducible.  Return codes: DLKA_ERR_NULL, DLKA_ERR_SHAPE (C or an extent < 1, a negative
- * pad, an axis outside 0..2), DLKA_ERR_DTYPE, DLKA_ERR_UNSUPPORTED (taps other than 1 or 2 (spline: 4), 2^31 cells or more, C > 256 for the
- * argmax, C != 1 for the spline, output == input).  Nothing is launched before the checks pass. */
+ * dlka_resample_spline_eval (order 3, :130-131 with :153-158 or :196): float64; the 4-tap evaluation of one channel of B-spline coefficients
+ * (dlka_spline_pad with DLKA_RESAMPLE_SPLINE_PAD edge samples on every filtered axis, dlka_spline_prefilter with DLKA_SPLINE_REFLECT along
+ * it) clipped to [lo[s], hi[s]], s = the output index along clip_axis, or 0 when clip_axis < 0.
+ * One launch each, no atomics: results are bitwise reproducible.  Return codes: DLKA_ERR_NULL, DLKA_ERR_SHAPE (C or an extent < 1, a clip
+ * axis above 2), DLKA_ERR_DTYPE, DLKA_ERR_UNSUPPORTED (taps other than 1 or 2 (spline: 4), 2^31 cells or more, C > 256 for the argmax,
+ * C != 1 for the spline, output == input).  Nothing is launched before the checks pass. */
 typedef struct dlka_resample_desc {
     int32_t C, dtype;
     int32_t taps[3];
@@ -796,12 +796,33 @@ int dlka_resample_argmax(const void *x, uint8_t *labels, const dlka_resample_des
 int dlka_resample_linear(const void *x, void *y, const dlka_resample_desc *d, const int32_t *idx, const double *w, void *stream);
 int dlka_resample_labels(const int32_t *seg, int32_t *out, const dlka_resample_desc *d, const int32_t *idx, const double *w, int strict,
                          void *stream);
-int dlka_resample_spline_pad(const void *x, double *padded, int dtype, const int64_t *in, const int64_t *pad, void *stream);
-int dlka_resample_spline_prefilter(double *coef, const int64_t *ext, int axis, void *stream);
 int dlka_resample_spline_eval(const double *coef, double *y, const dlka_resample_desc *d, const int32_t *start, const double *w4,
                               const double *lo, const double *hi, int clip_axis, void *stream);
-/* Diagnostics: kernel launches so far (this process) of the entries above. */
+/* Diagnostics: kernel launches so far (this process) of the entries above and of dlka_spline_pad / dlka_spline_prefilter below. */
 long dlka_resample_launch_count(void);
+
+/* =======================================================================================
+ * Cubic B-spline coefficients of a volume — csrc/cl_spline.hip
+ * =======================================================================================
+ * What scipy.ndimage.spline_filter (scipy/ndimage/_interpolation.py, spline_filter1d; src/ni_splines.c: apply_filter with
+ * _init_causal_reflect / _init_causal_mirror and their anti-causal counterparts) runs in front of every order-3 interpolation: of
+ * map_coordinates as skimage's resize calls it for resample_data_or_seg (3D/d_lka_former/preprocessing/preprocessing.py:130-131), of
+ * batchgenerators' interpolate_img in SpatialTransform (data_augmentation_moreDA.py:60-147) and of scipy.ndimage.zoom in test_single_volume
+ * (2D/utils.py:63-110).  float64; volumes are ext[3] cells, the last axis contiguous.
+ *
+ * dlka_spline_pad         padded[in + 2 pad] = x[in] (dtype DLKA_F32 or DLKA_F64) with pad[ax] edge samples on both sides of axis ax; pad 0
+ *                         is the cast to float64.
+ * dlka_spline_prefilter   in place along one axis of coef[ext]; a line of one cell is left as it is.  boundary: DLKA_SPLINE_REFLECT (scipy's
+ *                         'reflect', and its 'nearest' once the array is padded by DLKA_RESAMPLE_SPLINE_PAD edge samples) or
+ *                         DLKA_SPLINE_MIRROR ('mirror': what scipy filters with under 'constant', no padding).
+ * One launch each, one lane per line, no atomics: results are bitwise reproducible.  Return codes: DLKA_ERR_NULL, DLKA_ERR_SHAPE (an extent
+ * < 1, a negative pad, an axis outside 0..2), DLKA_ERR_DTYPE, DLKA_ERR_UNSUPPORTED (a boundary outside the two, a pad above 64, 2^31 cells or
+ * more).  Nothing is launched before the checks pass.  The launches count in dlka_resample_launch_count. */
+#define DLKA_RESAMPLE_SPLINE_PAD 12
+#define DLKA_SPLINE_REFLECT 0
+#define DLKA_SPLINE_MIRROR 1
+int dlka_spline_pad(const void *x, double *padded, int dtype, const int64_t *in, const int64_t *pad, void *stream);
+int dlka_spline_prefilter(double *coef, const int64_t *ext, int axis, int boundary, void *stream);
 
 /* =======================================================================================
  * Train-time augmentation of a batch of patches — csrc/cl_augment.hip
@@ -814,9 +835,9 @@ long dlka_resample_launch_count(void);
  * dlka_augment_spatial   per sample b a float64 map maps[12 b ..] (rows of 4: src[d] = m[4d] g0 + m[4d+1] g1 + m[4d+2] g2 + m[4d+3] with
  *              g[e] = index[e] - (out[e] - 1) / 2, formed in the lane: no coordinate grid is stored) and plain[4 b ..] = (flag, lb0, lb1, lb2):
  *              flag != 0 copies the box at lb bit for bit (batchgenerators does not interpolate an unmodified sample).  order 0 / 1 read x;
- *              order 3 reads coef, float64 B-spline coefficients [B*C][src + 2 pad], prepared by dlka_resample_spline_pad and
- *              dlka_resample_spline_prefilter (mode DLKA_AUG_NEAREST, pad 12: scipy's rule) or dlka_augment_spline_prefilter_mirror
- *              (DLKA_AUG_CONSTANT, pad 0).  The border rule is scipy.ndimage.map_coordinates': 'constant' gives cval wherever a coordinate
+ *              order 3 reads coef, float64 B-spline coefficients [B*C][src + 2 pad], prepared by dlka_spline_pad and
+ *              dlka_spline_prefilter: mode DLKA_AUG_NEAREST with pad 12 and DLKA_SPLINE_REFLECT (scipy's rule), DLKA_AUG_CONSTANT with
+ *              pad 0 and DLKA_SPLINE_MIRROR.  The border rule is scipy.ndimage.map_coordinates': 'constant' gives cval wherever a coordinate
  *              is < 0 or > n - 1, 'nearest' clamps the coordinate; taps and weights are scipy's, summed in its order in float64.
  * dlka_augment_spatial_labels   int32 maps.  order 0: the nearest cell (cval outside).  order 1: batchgenerators' per-label rule in one
  *              visit of the 8 neighbours: the largest label whose summed trilinear weight is >= 0.5, else 0; outside under 'constant'
@@ -854,7 +875,6 @@ int dlka_augment_spatial(const void *x, const double *coef, void *y, const dlka_
                          void *stream);
 int dlka_augment_spatial_labels(const int32_t *seg, int32_t *out, const dlka_augment_desc *d, const double *maps, const int32_t *plain,
                                 void *stream);
-int dlka_augment_spline_prefilter_mirror(double *coef, const int64_t *ext, int axis, void *stream);
 int dlka_augment_gaussian(const void *x, void *y, int dtype, int64_t channels, const int64_t *ext, int axis, const int32_t *radius,
                           const double *weights, void *stream);
 size_t dlka_augment_stats_workspace_bytes(int64_t channels, int64_t cells);
@@ -928,7 +948,7 @@ long dlka_prep_launch_count(void);
  * cval = 0 wherever a coordinate is < 0 or > n - 1, at every order.  The caller forms the coordinates in float64 on the host and passes them
  * as tables, rows (out[0] entries) first, then columns (out[1]); stacks are [N][h][w], w contiguous.
  *
- * dlka_zoom2d_spline    taps 4: src = float64 B-spline coefficients [N][in] (dlka_augment_spline_prefilter_mirror along axes 1 and 2 of the
+ * dlka_zoom2d_spline    taps 4: src = float64 B-spline coefficients [N][in] (dlka_spline_prefilter, DLKA_SPLINE_MIRROR, along axes 1 and 2 of the
  *                       stack); taps 2: src = the raw values in in_dtype (order 1).  start[row] = the first tap (floor(coordinate) - 1, or
  *                       floor(coordinate) for 2 taps) or DLKA_ZOOM2D_OUTSIDE; w4[4 * row + k] = the weights (2 taps: k < 2).  Taps beyond the
  *                       slice are mirrored in the kernel.  The float64 sum t += (c * w_row) * w_col, rows outermost, is rounded once to float32;
