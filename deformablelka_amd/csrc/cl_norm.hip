@@ -47,6 +47,8 @@ __device__ __forceinline__ void st_lo(float *p, long i, float v, int lo)
 
 // One wave per token row: x (planar [B][C][N] — the NCDHW tensor the block receives — or channels-last [M][C]) (+ pos[N][C])
 // -> xt[M][C]; xn = (xt - mean) * rstd * w + b; stats[m] = {mean, rstd}.   Biased variance, eps inside the sqrt (nn.LayerNorm).
+// The variance is TWO-PASS: mean first, then the sum of (xt - mean)^2 over the values the lanes still hold.  The one-pass E[x^2] - mean^2 form cancels
+// (mean / std)^2 ulps of the variance (fp32: rstd 5e-4 off at mean / std = 100, the variance gone at 500 — see cl_bn_stats_kernel); nn.LayerNorm is not one-pass.
 __global__ __launch_bounds__(NT) void cl_layernorm_fwd_kernel(const float *__restrict__ x, int x_planar, const float *__restrict__ pos,
                                                               const float *__restrict__ w, const float *__restrict__ b, float *__restrict__ xt,
                                                               float *__restrict__ xn, float *__restrict__ stats, int B, int N, int C, float eps, int lo,
@@ -67,10 +69,10 @@ __global__ __launch_bounds__(NT) void cl_layernorm_fwd_kernel(const float *__res
                 xt[m * C + c] = val;
             }
             const float mean = half_sum(val) / C;
-            const float var = fmaxf(half_sum(val * val) / C - mean * mean, 0.f);
-            const float rstd = 1.f / sqrtf(var + eps);
+            const float d = ok ? val - mean : 0.f;   // two-pass variance on the row the lanes hold (see the note above the kernel)
+            const float rstd = 1.f / sqrtf(half_sum(d * d) / C + eps);
             if (ok) {
-                const float o = (val - mean) * rstd * w[c] + b[c];
+                const float o = d * rstd * w[c] + b[c];
                 st_lo(xn, m * C + c, o, lo);
                 if (xn32) xn32[m * C + c] = o;
                 if (c == 0) { stats[2 * m] = mean; stats[2 * m + 1] = rstd; }
@@ -80,23 +82,34 @@ __global__ __launch_bounds__(NT) void cl_layernorm_fwd_kernel(const float *__res
     }
     for (long m = (long)blockIdx.x * (NT / 64) + wave; m < M; m += (long)gridDim.x * (NT / 64)) {
         const int bb = (int)(m / N), v = (int)(m - (long)bb * N);
-        float s = 0.f, s2 = 0.f;
-        for (int c = lane; c < C; c += 64) {
-            float val = x_planar ? x[((long)bb * C + c) * N + v] : x[m * C + c];
-            if (pos) val += pos[(long)v * C + c];
-            xt[m * C + c] = val;
-            s += val;
-            s2 = fmaf(val, val, s2);
+        float s = 0.f, s2 = 0.f, d[KMAX];   // this lane's channels lane + 64k stay in registers between the passes
+#pragma unroll
+        for (int k = 0; k < KMAX; ++k) {
+            const int c = lane + 64 * k;
+            d[k] = 0.f;
+            if (c < C) {
+                float val = x_planar ? x[((long)bb * C + c) * N + v] : x[m * C + c];
+                if (pos) val += pos[(long)v * C + c];
+                xt[m * C + c] = val;
+                d[k] = val;
+                s += val;
+            }
         }
-        s = wave_sum(s);
-        s2 = wave_sum(s2);
-        const float mean = s / C;
-        const float var = fmaxf(s2 / C - mean * mean, 0.f);
-        const float rstd = 1.f / sqrtf(var + eps);
-        for (int c = lane; c < C; c += 64) {
-            const float o = (xt[m * C + c] - mean) * rstd * w[c] + b[c];
-            st_lo(xn, m * C + c, o, lo);
-            if (xn32) xn32[m * C + c] = o;
+        const float mean = wave_sum(s) / C;
+#pragma unroll
+        for (int k = 0; k < KMAX; ++k) {
+            d[k] = lane + 64 * k < C ? d[k] - mean : 0.f;
+            s2 = fmaf(d[k], d[k], s2);
+        }
+        const float rstd = 1.f / sqrtf(wave_sum(s2) / C + eps);
+#pragma unroll
+        for (int k = 0; k < KMAX; ++k) {
+            const int c = lane + 64 * k;
+            if (c < C) {
+                const float o = d[k] * rstd * w[c] + b[c];
+                st_lo(xn, m * C + c, o, lo);
+                if (xn32) xn32[m * C + c] = o;
+            }
         }
         if (lane == 0) { stats[2 * m] = mean; stats[2 * m + 1] = rstd; }
     }
@@ -230,9 +243,22 @@ __global__ __launch_bounds__(NT) void cl_scale_residual_bwd_kernel(const float *
 }
 
 // sums[c] += sum_m (x[m][c] - p_c), sums[C + c] += sum_m (x[m][c] - p_c)^2     (zero-initialised)
-// p_c = x[0][c], the first row, is a per-channel pivot: the one-pass E[x^2] - mean^2 form loses all its digits when |mean| >> std
+// p_c is a per-channel pivot taken from the data (x[0][c] in the quad kernels, bn_pivot below here): the one-pass E[x^2] - mean^2 form loses all its digits when |mean| >> std
 // (fp32: 24 % variance error at mean/std = 500); around a pivot that is itself a sample the two sums stay O(std), so the
 // subtraction in cl_bn_finish_stats_kernel cancels nothing that matters (matches torch's Welford BatchNorm to ~1e-6 rel).
+// The general kernel's pivot is the mean of the first BN_PIVOT_ROWS rows (added in row order, here and in cl_bn_finish_stats_kernel: the same value in both).  A single
+// sample sits |mean - p| ~ 2-3 std away for some channel of a wide tensor, the sum of squares is then (1 + (mean - p)^2 / var) ~ 10 times what the variance needs, and
+// the rounding of ~1000 workgroups' fp32 atomics into it is amplified by that factor: variance 8e-6 off at (M, C) = (30011, 96), y 3.6e-5 off.  Eight rows: factor 1.1.
+constexpr int BN_PIVOT_ROWS = 8;
+__device__ __forceinline__ float bn_pivot(const float *__restrict__ x, long M, int C, int c, int rows)
+{
+    if (rows <= 1) return x[c];
+    const int n = M < rows ? (int)M : rows;
+    float p = 0.f;
+    for (int r = 0; r < n; ++r) p += x[(long)r * C + c];
+    return p / n;
+}
+
 __global__ __launch_bounds__(NT) void cl_bn_stats_kernel(const float *__restrict__ x, float *__restrict__ sums, long M, int C)
 {
     DLKA_DYN_SMEM(float, red);   // [2][C]
@@ -244,7 +270,7 @@ __global__ __launch_bounds__(NT) void cl_bn_stats_kernel(const float *__restrict
         const int c = cb + c_in;
         if (r_in < rpb && c < C) {
             float s = 0.f, s2 = 0.f;
-            const float pv = x[c];
+            const float pv = bn_pivot(x, M, C, c, BN_PIVOT_ROWS);
             const long step = (long)gridDim.x * rpb;
             long m = (long)blockIdx.x * rpb + r_in;
             for (; m + 3 * step < M; m += 4 * step) {   // four rows in flight per work-item (the loop is pure load latency otherwise)
@@ -266,13 +292,14 @@ __global__ __launch_bounds__(NT) void cl_bn_stats_kernel(const float *__restrict
 }
 
 // stats[c] = mean, stats[C + c] = rstd, stats[2C + c] = unbiased variance (for the running estimate)
-__global__ void cl_bn_finish_stats_kernel(const float *__restrict__ x, const float *__restrict__ sums, float *__restrict__ stats, long M, int C, float eps)
+// pivot_rows: 1 after the quad kernel (p_c = x[0][c]), BN_PIVOT_ROWS after the general one
+__global__ void cl_bn_finish_stats_kernel(const float *__restrict__ x, const float *__restrict__ sums, float *__restrict__ stats, long M, int C, float eps, int pivot_rows)
 {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= C) return;
     const float dm = sums[c] / (float)M;               // mean - pivot
     const float var = fmaxf(sums[C + c] / (float)M - dm * dm, 0.f);
-    const float mean = x[c] + dm;
+    const float mean = bn_pivot(x, M, C, c, pivot_rows) + dm;
     stats[c] = mean;
     stats[C + c] = 1.f / sqrtf(var + eps);
     stats[2 * C + c] = M > 1 ? var * ((float)M / (float)(M - 1)) : var;
@@ -434,15 +461,13 @@ __global__ __launch_bounds__(NT) void cl_layernorm_fwd_q_kernel(const float *__r
             if (pos) { const f32x4 pv = act_load4(pos, (long)(m % N) * C + 4 * q); v[0] += pv[0]; v[1] += pv[1]; v[2] += pv[2]; v[3] += pv[3]; }
             act_store4(xt, i, v);
         }
-        const float s = row_sum<LPR>((v[0] + v[1]) + (v[2] + v[3]));
-        const float s2 = row_sum<LPR>(fmaf(v[0], v[0], fmaf(v[1], v[1], fmaf(v[2], v[2], v[3] * v[3]))));
-        const float mean = s / C;
-        const float var = fmaxf(s2 / C - mean * mean, 0.f);
-        const float rstd = 1.f / sqrtf(var + eps);
+        const float mean = row_sum<LPR>((v[0] + v[1]) + (v[2] + v[3])) / C;
+        const f32x4 d = {v[0] - mean, v[1] - mean, v[2] - mean, v[3] - mean};   // (a row past M holds zeros and has mean 0)
+        const float rstd = 1.f / sqrtf(row_sum<LPR>(fmaf(d[0], d[0], fmaf(d[1], d[1], fmaf(d[2], d[2], d[3] * d[3])))) / C + eps);
         if (!ok) continue;
         f32x4 o;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = (v[e] - mean) * rstd * wq[e] + bq[e];
+        for (int e = 0; e < 4; ++e) o[e] = d[e] * rstd * wq[e] + bq[e];
         stq_lo(xn, i, o, lo);
         if (xn32) act_store4(xn32, i, o);
         if (q == 0) { stats[2 * m] = mean; stats[2 * m + 1] = rstd; }
@@ -819,12 +844,13 @@ int launch_cl_bn_stats(const float *x, float *sums, float *stats, long M, int C,
     }
     if (!zeroed) DLKA_TRY_LAUNCH(launch_zero(sums, (size_t)2 * C * 4, st));
     const int rpb = NT / (C < NT ? C : NT);
-    if (quad_shape_ok(C, M) && quad_aligned(x)) {
+    const bool quad = quad_shape_ok(C, M) && quad_aligned(x);
+    if (quad) {
         DLKA_QUAD_DISPATCH(C, cl_bn_stats_q_kernel, quad_grid(M, C, 8, 1024), x, sums, M)
     } else
         DLKA_LAUNCH(cl_bn_stats_kernel, dim3(grid_for(M, rpb * 16, 1024)), dim3(NT), 2 * C * sizeof(float), st, x, sums, M, C);
     DLKA_CHECK_LAUNCH();
-    DLKA_LAUNCH(cl_bn_finish_stats_kernel, dim3(cdiv(C, 256)), dim3(256), 0, st, x, (const float *)sums, stats, M, C, eps);
+    DLKA_LAUNCH(cl_bn_finish_stats_kernel, dim3(cdiv(C, 256)), dim3(256), 0, st, x, (const float *)sums, stats, M, C, eps, quad ? 1 : BN_PIVOT_ROWS);
     DLKA_CHECK_LAUNCH();
     return DLKA_OK;
 }

@@ -856,34 +856,156 @@ def check_lka3d_tokens_bf16(dev, B, C, dims, seed=0, offset_std=0.38, rtol=BF16_
 
 
 # ---- the wrapper block (TransformerBlock_3D_single_deform_LKA) and its pieces ------------------------------------------------
-def check_layernorm_tokens(dev, B, C, N, planar, pos, seed=0):
-    from deformablelka_amd import ops
+def offset_view(t, elems=1):
+    """A contiguous copy of ``t`` that starts ``elems`` elements into a fresh allocation: same values, a data pointer that is NOT 16-byte aligned.  ops.py only calls
+    .contiguous(), so such a view reaches the C API with its own pointer and the launchers must fall back from their 16-byte (quad) kernels."""
+    buf = torch.empty(t.numel() + elems, dtype=t.dtype, device=t.device)
+    v = buf[elems:].view(t.shape)
+    v.copy_(t.detach())
+    assert v.is_contiguous() and v.data_ptr() % 16 != 0
+    return v
+
+
+def _put(t, dev, name, unaligned):
+    """``t`` on ``dev``; as an offset_view when ``unaligned`` is "all" or names this operand."""
+    if t is None:
+        return None
+    t = t.to(dev)
+    return offset_view(t) if unaligned == "all" or name in unaligned else t
+
+
+LN_SCALE = 2.0   # std of the LayerNorm test rows
+LN_MEAN_ULPS = {20.0: 4.14, 100.0: 4.34, 500.0: 3.96}   # bound of the row mean in fp32 ulps of |mean|: twice torch's own fp32 error (check_layernorm_tokens)
+
+
+def layernorm_inputs(B, C, N, planar, pos, seed=0, mean_over_std=None):
+    """(x, w, b, pos_embed or None, g_xn, g_res) of check_layernorm_tokens."""
     g = torch.Generator().manual_seed(seed)
-    x = torch.randn(B, C, N, generator=g) * 2 + 0.5 if planar else torch.randn(B, N, C, generator=g) * 2 + 0.5
+    x = torch.randn(B, C, N, generator=g) * LN_SCALE if planar else torch.randn(B, N, C, generator=g) * LN_SCALE
     w, b = torch.randn(C, generator=g), torch.randn(C, generator=g)
     pe = torch.randn(1, N, C, generator=g) if pos else None
     gxn, gres = torch.randn(B, N, C, generator=g), torch.randn(B, N, C, generator=g)
-    xr, wr, br = x.clone().requires_grad_(True), w.clone().requires_grad_(True), b.clone().requires_grad_(True)
-    per = pe.clone().requires_grad_(True) if pos else None
-    t = xr.permute(0, 2, 1) if planar else xr
+    if mean_over_std is None:
+        x = x + 0.5
+    else:
+        sign = (torch.rand(B, N, 1, generator=g) < 0.5).float() * 2 - 1
+        off = LN_SCALE * mean_over_std * sign * (0.8 + 0.4 * torch.rand(B, N, 1, generator=g))
+        x = x + (off.permute(0, 2, 1) if planar else off)
+    return x, w, b, pe, gxn, gres
+
+
+def check_layernorm_tokens(dev, B, C, N, planar, pos, seed=0, mean_over_std=None, unaligned=()):
+    """LayerNorm over tokens (+ pos_embed), forward and backward.  Returns the forward results (xt, xn, stats) on the CPU.
+
+    unaligned: "all" or a collection of operand names ("x", "pos", "w", "b", "gxn", "gres", "xt", "stats") passed as offset_view()s — same reference, same tolerances.
+
+    mean_over_std=None: the rows of x are N(0.5, 2) and the reference is torch's fp32 F.layer_norm (the cases this check has always had).
+
+    mean_over_std=r: every token row is N(m, 2) with m = +-2 r (1 +- 0.2), sign and jitter drawn per row.  The reference is FLOAT64 F.layer_norm and its autograd gradients
+    evaluated on the fp32 xt the kernel returned (xt = x + pos is one correctly rounded fp32 add and is first held to the fp32 sum), so the comparison sees the kernels'
+    arithmetic and not the representation error of x.  Bounds:
+      stats mean   LN_MEAN_ULPS fp32 ulps of the row's |mean| (see below: one ulp is tighter than fp32 summation of C values delivers)
+      stats rstd   rtol 1e-4
+      xn           atol max(2e-5, 4e-7 * r * 2): ulp(|mean|) carried into (x - mean) * rstd (check_batchnorm_cl's form for the same fp32 floor)
+      gradients    rtol 1e-4, unscaled: an error d of the mean moves xhat by d * rstd ~ 1.5e-7 r per ulp, i.e. 7e-5 at r = 500, and the gradients by less
+    torch's OWN fp32 CPU kernels (torch.native_layer_norm and its autograd) against the same float64 reference on these inputs, worst over the five emulator and the
+    five GPU shapes of test_layernorm_tokens_large_mean:
+      r      xn abs    (bound)   mean, ulps   rstd rel   gxt rel    gw rel     gb rel     gpos rel
+      20     1.14e-5   (2e-5)    2.07         6.76e-7    5.16e-7    2.27e-6    5.04e-7    3.79e-7
+      100    5.11e-5   (8e-5)    2.17         2.43e-6    3.37e-6    6.51e-6    5.04e-7    2.71e-6
+      500    3.43e-4   (4e-4)    1.98         3.46e-5    2.03e-5    3.57e-5    5.04e-7    1.62e-5
+    torch is inside every bound but "one ulp of |mean|": summing C fp32 values of one sign rounds at every level of the tree, and its own row mean is about 2 ulps off
+    at each ratio.  The mean's bound is therefore TWICE torch's measured error at that ratio (LN_MEAN_ULPS = 4.14 / 4.34 / 3.96 ulps); every other bound stands as the
+    fp32 floor gives it.  None of them was set from the HIP kernels' output.
+    The one-pass variance E[x^2] - mean^2 these kernels computed before missed the bounds at every ratio and shape; worst over the five emulator shapes:
+      r      xn abs     rstd rel   gxt rel    gw rel
+      20     3.35e-4    4.49e-5    2.55e-5    2.35e-5      (xn alone outside its bound)
+      100    6.18e-3    1.34e-3    6.24e-4    6.25e-4
+      500    1.42e-1    3.48e-2    1.76e-2    2.17e-2"""
+    from deformablelka_amd import ops
+    x, w, b, pe, gxn, gres = layernorm_inputs(B, C, N, planar, pos, seed, mean_over_std)
+    t32 = x.permute(0, 2, 1) if planar else x
     if pos:
-        t = t + per
-    n = F.layer_norm(t, (C,), wr, br, 1e-5)
-    (n * gxn).sum().backward(retain_graph=True)
-    (t * gres).sum().backward()
-    xt, xn, stats = ops.layernorm_tokens_forward(x.to(dev), planar, None if pe is None else pe.to(dev), w.to(dev), b.to(dev))
-    assert_close("ln xt", xt, t.detach(), atol=1e-6)
-    assert_close("ln xn", xn, n.detach(), atol=2e-5)
-    gxt, gw, gb, gpos = ops.layernorm_tokens_backward(gxn.to(dev), gres.to(dev), xt, stats, w.to(dev), with_pos=pos)
-    ref_gx = xr.grad.permute(0, 2, 1) if planar else xr.grad
+        t32 = t32 + pe
+    u = unaligned
+    wd_, bd_ = _put(w, dev, "w", u), _put(b, dev, "b", u)
+    xt, xn, stats = ops.layernorm_tokens_forward(_put(x, dev, "x", u), planar, _put(pe, dev, "pos", u), wd_, bd_)
+    fwd = (xt.cpu().clone(), xn.cpu().clone(), stats.cpu().clone())
+    gxt, gw, gb, gpos = ops.layernorm_tokens_backward(_put(gxn, dev, "gxn", u), _put(gres, dev, "gres", u), _put(xt, dev, "xt", u), _put(stats, dev, "stats", u), wd_,
+                                                      with_pos=pos)
+    assert_close("ln xt", xt, t32, atol=1e-6)
+    if mean_over_std is None:
+        xr, wr, br = x.clone().requires_grad_(True), w.clone().requires_grad_(True), b.clone().requires_grad_(True)
+        per = pe.clone().requires_grad_(True) if pos else None
+        t = xr.permute(0, 2, 1) if planar else xr
+        if pos:
+            t = t + per
+        n = F.layer_norm(t, (C,), wr, br, 1e-5)
+        (n * gxn).sum().backward(retain_graph=True)
+        (t * gres).sum().backward()
+        assert_close("ln xn", xn, n.detach(), atol=2e-5)
+        ref_gx = xr.grad.permute(0, 2, 1) if planar else xr.grad
+        ref_gpos = per.grad if pos else None
+    else:
+        r = float(mean_over_std)
+        td, wr, br = xt.cpu().double().requires_grad_(True), w.double().requires_grad_(True), b.double().requires_grad_(True)
+        n = F.layer_norm(td, (C,), wr, br, 1e-5)
+        ((n * gxn.double()).sum() + (td * gres.double()).sum()).backward()
+        mean64 = td.detach().mean(-1).reshape(-1)
+        rstd64 = torch.rsqrt(td.detach().var(-1, unbiased=False) + 1e-5).reshape(-1)
+        e_mean = ((stats[:, 0].cpu().double() - mean64).abs() / 2.0 ** (torch.floor(torch.log2(mean64.abs())) - 23)).max().item()   # in fp32 ulps of the row's |mean|
+        e_rstd, e_xn = rel_err(stats[:, 1], rstd64), (xn.cpu().double() - n.detach()).abs().max().item()
+        print(f"[ln r={r:g} B={B} C={C} N={N} planar={planar} pos={pos}] mean err {e_mean:.2f} ulp; rstd rel {e_rstd:.3e}; xn abs {e_xn:.3e}; "
+              f"gxt rel {rel_err(gxt, td.grad):.3e}; gw rel {rel_err(gw, wr.grad):.3e}; gb rel {rel_err(gb, br.grad):.3e}")
+        assert e_mean <= LN_MEAN_ULPS[r], f"ln mean: {e_mean:.2f} fp32 ulps of |mean| off, more than {LN_MEAN_ULPS[r]}"
+        assert_close("ln rstd", stats[:, 1], rstd64, rtol=1e-4)
+        assert_close("ln xn", xn, n.detach(), atol=max(2e-5, 4e-7 * r * LN_SCALE))
+        ref_gx, ref_gpos = td.grad, td.grad.sum(0, keepdim=True)
     assert_close("ln gx", gxt, ref_gx, rtol=1e-4)
     assert_close("ln gw", gw, wr.grad, rtol=1e-4)
     assert_close("ln gb", gb, br.grad, rtol=1e-4)
     if pos:
-        assert_close("ln gpos", gpos, per.grad, rtol=1e-4)
+        assert_close("ln gpos", gpos, ref_gpos, rtol=1e-4)
+    return fwd
 
 
-def check_batchnorm_cl(dev, M, C, training, with_res, seed=0, mean_over_std=0.2):
+def check_layernorm_unsupported_width(dev, C=257):
+    """LayerNorm keeps at most 4 channels per lane (C <= 256): a wider row is refused with DLKA_ERR_UNSUPPORTED by both directions, and nothing is written."""
+    from deformablelka_amd import _lib as L, ops
+    B, N = 1, 5
+    x, w, b = torch.randn(B, N, C).to(dev), torch.randn(C).to(dev), torch.randn(C).to(dev)
+    with raises_status(-8):
+        ops.layernorm_tokens_forward(x, False, None, w, b)
+    mark = 1234.5
+    outs = [torch.full((B, N, C), mark).to(dev), torch.full((B, N, C), mark).to(dev), torch.full((B * N, 2), mark).to(dev)]
+    lib = L.get_lib()
+    rc = lib.dlka_layernorm_tokens_forward(L.ptr(x), 0, L.ptr(None), L.ptr(w), L.ptr(b), *(L.ptr(o) for o in outs), B, N, C, 1e-5, L.dtype_code(x), L.stream_ptr(x))
+    assert rc == -8, rc
+    gouts = [torch.full((B, N, C), mark).to(dev), torch.full((C,), mark).to(dev), torch.full((C,), mark).to(dev), torch.full((1, N, C), mark).to(dev)]
+    rc = lib.dlka_layernorm_tokens_backward(L.ptr(x), L.ptr(x), L.ptr(x), L.ptr(outs[2]), L.ptr(w), *(L.ptr(o) for o in gouts), B, N, C, L.dtype_code(x), L.stream_ptr(x))
+    assert rc == -8, rc
+    for o in outs + gouts:
+        assert bool((o.cpu() == mark).all())
+
+
+class raises_status:
+    """The library's error for a dlka_status code, as ops.py raises it (RuntimeError "...(dlka status <code>)")."""
+
+    def __init__(self, code):
+        self.code = code
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, et, ev, tb):
+        assert et is not None, f"expected dlka status {self.code}, the call succeeded"
+        assert issubclass(et, RuntimeError) and f"(dlka status {self.code})" in str(ev), (et, ev)
+        return True
+
+
+def check_batchnorm_cl(dev, M, C, training, with_res, seed=0, mean_over_std=0.2, unaligned=()):
+    """BatchNorm (+ residual) + LeakyReLU over channels-last rows, forward and backward.  Returns y on the CPU.
+    unaligned: "all" or a collection of operand names ("x", "res", "w", "b", "stats" (eval mode: caller-supplied), "gy", "y") passed as offset_view()s."""
     from deformablelka_amd import ops
     g = torch.Generator().manual_seed(seed)
     x = torch.randn(M, C, generator=g) * 1.5 + 1.5 * mean_over_std
@@ -897,11 +1019,15 @@ def check_batchnorm_cl(dev, M, C, training, with_res, seed=0, mean_over_std=0.2)
     if with_res:
         v = v + rr
     y_ref = F.leaky_relu(v, 0.01)
+    u = unaligned
     if training:
         stats = torch.empty(3 * C).to(dev)
     else:
-        stats = torch.cat([rm, torch.rsqrt(rv + 1e-5), rv]).to(dev)
-    y = ops.batchnorm_cl_forward(x.to(dev), None if res is None else res.to(dev), w.to(dev), b.to(dev), stats, training)
+        stats = _put(torch.cat([rm, torch.rsqrt(rv + 1e-5), rv]), dev, "stats", u)
+    xd_, wd_ = _put(x, dev, "x", u), _put(w, dev, "w", u)
+    y = ops.batchnorm_cl_forward(xd_, _put(res, dev, "res", u), wd_, _put(b, dev, "b", u), stats, training)
+    if os.environ.get("DLKA_PARITY_VERBOSE"):
+        print(f"[bn M={M} C={C} training={training}] y abs {(y.cpu().double() - y_ref.detach().double()).abs().max().item():.3e}")
     # fp32 floor: x carries ulp(|mean|) of representation error into (x - mean) * rstd, e.g. 6e-5 at mean 750
     assert_close("bn y", y, y_ref.detach(), atol=max(2e-5, 4e-7 * 1.5 * mean_over_std))
     if training:
@@ -912,26 +1038,59 @@ def check_batchnorm_cl(dev, M, C, training, with_res, seed=0, mean_over_std=0.2)
     # forward under test (sign of ITS y), which is what a backward pass consistent with that forward has to use.
     gpre = gy * torch.where(y.detach().cpu() > 0, torch.ones(()), torch.full((), 0.01))
     v.backward(gpre)
-    gx, gres, gw, gb = ops.batchnorm_cl_backward(gy.to(dev), x.to(dev), y, w.to(dev), stats, training, with_res=with_res)
+    gx, gres, gw, gb = ops.batchnorm_cl_backward(_put(gy, dev, "gy", u), xd_, _put(y, dev, "y", u), wd_, stats, training, with_res=with_res)
     assert_close("bn gx", gx, xr.grad, rtol=max(2e-4, 2e-6 * mean_over_std))
     assert_close("bn gw", gw, wr.grad, rtol=max(2e-4, 2e-6 * mean_over_std))
     assert_close("bn gb", gb, br.grad, rtol=2e-4)
     if with_res:
         assert_close("bn gres", gres, rr.grad, rtol=1e-5)
+    return y.detach().cpu().clone()
 
 
-def check_scale_residual(dev, M, C, seed=0):
+def check_scale_residual(dev, M, C, seed=0, unaligned=()):
+    """out = xt + gamma * e and its backward, then the Dropout3d channel scale.  Returns out on the CPU.  The backward takes C % 32 == 0 only: at any other width it must
+    refuse with DLKA_ERR_SHAPE.  unaligned: "all" or a collection of operand names ("xt", "e", "gamma", "gy") passed as offset_view()s."""
     from deformablelka_amd import ops
     g = torch.Generator().manual_seed(seed)
     xt, e, gm, gy = torch.randn(M, C, generator=g), torch.randn(M, C, generator=g), torch.randn(C, generator=g), torch.randn(M, C, generator=g)
-    out = ops.scale_residual_forward(xt.to(dev), e.to(dev), gm.to(dev))
+    u = unaligned
+    ed_, gmd_ = _put(e, dev, "e", u), _put(gm, dev, "gamma", u)
+    out = ops.scale_residual_forward(_put(xt, dev, "xt", u), ed_, gmd_)
     assert_close("sr out", out, xt + gm * e, atol=1e-6)
-    ge, gg = ops.scale_residual_backward(gy.to(dev), e.to(dev), gm.to(dev))
-    assert_close("sr ge", ge, gy * gm, atol=1e-6)
-    assert_close("sr ggamma", gg, (gy * e).sum(0), rtol=1e-4)
+    if C % 32:
+        with raises_status(-4):
+            ops.scale_residual_backward(_put(gy, dev, "gy", u), ed_, gmd_)
+    else:
+        ge, gg = ops.scale_residual_backward(_put(gy, dev, "gy", u), ed_, gmd_)
+        assert_close("sr ge", ge, gy * gm, atol=1e-6)
+        assert_close("sr ggamma", gg, (gy * e).sum(0), rtol=1e-4)
     B = 3
     x3, mask = torch.randn(B, 7, C, generator=g), torch.rand(B, C, generator=g)
-    assert_close("channel scale", ops.channel_scale(x3.to(dev), mask.to(dev)), x3 * mask[:, None, :], atol=1e-6)
+    assert_close("channel scale", ops.channel_scale(_put(x3, dev, "x3", u), _put(mask, dev, "mask", u)), x3 * mask[:, None, :], atol=1e-6)
+    return out.cpu().clone()
+
+
+def check_norm_ops_unaligned(dev, op, M, C):
+    """A quad width (C in {32, 64, 128, 256}) takes the 16-byte kernels only while EVERY pointer they load or store 16 bytes through is aligned (the quad_aligned
+    terms of the launchers in csrc/cl_norm.hip).  Three ways through the same check, same reference, same tolerances: (c) aligned — the quad kernels; (a) every
+    caller-supplied operand an offset_view — the general kernels; (b) one operand at a time offset — the launcher must notice that operand alone (an incomplete guard
+    list shows as a misaligned 16-byte load: a crash on the emulator, a wrong result or fault on the GPU).  The forward results (no atomics in those kernels; the
+    training-mode BatchNorm statistics, which have, sit inside their own tolerance) of every variant agree with (c) within the check's tolerances.
+    op: "ln" (LayerNorm with pos_embed, M = N tokens of one sample), "bn_eval" / "bn_train" (BatchNorm + residual + LeakyReLU), "sr" (scale-residual)."""
+    if op == "ln":
+        run = lambda u: check_layernorm_tokens(dev, 1, C, M, False, True, unaligned=u)
+        names, tols = ("x", "pos", "w", "b", "gxn", "gres", "xt", "stats"), (dict(atol=1e-6), dict(atol=2e-5), dict(rtol=1e-4))
+    elif op in ("bn_eval", "bn_train"):
+        run = lambda u: (check_batchnorm_cl(dev, M, C, op == "bn_train", True, unaligned=u),)
+        names, tols = ("x", "res", "w", "b", "gy", "y") + (("stats",) if op == "bn_eval" else ()), (dict(atol=2e-5),)
+    else:
+        run = lambda u: (check_scale_residual(dev, M, C, unaligned=u),)
+        names, tols = ("xt", "e", "gamma", "gy"), (dict(atol=1e-6),)
+    aligned = run(())
+    for u in ["all"] + [(n,) for n in names]:
+        got = run(u)
+        for i, (a, r, t) in enumerate(zip(got, aligned, tols)):
+            assert_close(f"{op} forward result {i}, unaligned={u}, against the aligned run", a, r, **t)
 
 
 # The LeakyReLU-kink protocol (wrapper block, assembled net).  LeakyReLU's slope jumps from 0.01 to 1 at 0: a pre-activation within fp32 rounding of 0 can sit on
@@ -964,11 +1123,14 @@ def kink_report(pre_out):
     return n_dis, worst, total
 
 
-def check_tblock3d(dev, B, C, dims, training, pos, seed=0, offset_std=0.02, atol=FWD_ATOL, rtol=BWD_RTOL, chain=False, report=False, acdc=False):
+def check_tblock3d(dev, B, C, dims, training, pos, seed=0, offset_std=0.02, atol=FWD_ATOL, rtol=BWD_RTOL, chain=False, report=False, acdc=False,
+                   token_mean_over_std=0.0):
     """The fused wrapper block vs the oracle composition (oracle/blocks.py transformer_block_3d): forward 1e-4 abs (north_star), EVERY gradient 1e-3 rel
     (SURVEY §8c), every element of it — on identical sampling cells (the oracle fed the kernels' predicted offsets, as check_lka3d_tokens does) and on the
     kernels' activation pattern at UnetResBlock's two LeakyReLUs (kink protocol above: disagreements counted and capped).  chain=True: two applications of the
-    block, each with its own offsets / patterns.  The plain comparison (oracle on its own cells and pattern) is reported and sanity-bounded."""
+    block, each with its own offsets / patterns.  The plain comparison (oracle on its own cells and pattern) is reported and sanity-bounded.
+    token_mean_over_std=r: every token (voxel) of the N(0, 1) input is shifted by +-r (1 +- 0.2), sign and jitter drawn per token — the rows the block's LayerNorm
+    sees then have |mean| >> std (check_layernorm_tokens, mean_over_std)."""
     import deformablelka_amd as dk
     from deformablelka_amd import ops as _ops
     from oracle import blocks
@@ -994,6 +1156,9 @@ def check_tblock3d(dev, B, C, dims, training, pos, seed=0, offset_std=0.02, atol
     x = torch.randn(B, C, H, W, D)
     gy = torch.randn(B, C, H, W, D)
     mask = torch.nn.functional.dropout3d(torch.ones(B, C, 1, 1, 1), 0.1, True).view(B, C) if training else None
+    if token_mean_over_std:
+        sign = (torch.rand(B, 1, H, W, D) < 0.5).float() * 2 - 1
+        x = x + token_mean_over_std * sign * (0.8 + 0.4 * torch.rand(B, 1, H, W, D))
     napp = 2 if chain else 1
 
     def run_oracle(overrides=None):

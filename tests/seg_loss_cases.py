@@ -86,3 +86,36 @@ def check_counts(case, device, label_dtype=torch.float32):
         got = torch.stack([tp, fp, fn]).cpu()
         assert got.dtype == torch.int64
         assert torch.equal(got, ref), (got, ref)
+
+
+def check_unaligned_vector_shape(device, label_dtype=torch.float32):
+    """K = 4, N = 3 * 4 * 4 = 48 (a multiple of 4): aligned, the launchers' seg_vec takes the 16-byte kernels; with logits and labels that start one element into
+    their allocation (tests/parity.py offset_view: contiguous, data pointer not 16-byte aligned) the same shape has to take the scalar ones.  Both runs against
+    tests/seg_loss_ref.py in float64 under the tolerances above, forward, Dice coefficients, online-evaluation counts and every element of the gradient."""
+    from deformablelka_amd import losses
+    from tests import seg_loss_ref as R
+    from tests.parity import offset_view
+    tol_abs, tol_grad = TOL[torch.float32]
+    gen = torch.Generator().manual_seed(4)
+    B, K, spatial = 2, 4, (3, 4, 4)
+    x = torch.randn((B, K) + spatial, generator=gen) * 2.0
+    y = torch.randint(0, K, (B, 1) + spatial, generator=gen)
+    kw = {"batch_dice": True, "smooth": 1e-5, "do_bg": False}
+    xr = x.double().requires_grad_(True)
+    ref, dcr = R.dc_and_ce(xr, y, **kw)
+    ref.backward()
+    for aligned in (True, False):
+        xd, yd = x.clone().to(device), y.to(device=device, dtype=label_dtype)
+        if not aligned:
+            xd, yd = offset_view(xd), offset_view(yd)
+        xd.requires_grad_(True)
+        loss = losses.DC_and_CE_loss(dict(kw), {})(xd, yd)
+        loss.backward()
+        dc = losses.dc_and_ce(xd.detach(), yd, **kw)[1][0]
+        e_loss = abs(float(loss) - float(ref))
+        e_grad = float((xd.grad.cpu().double() - xr.grad).abs().max() / xr.grad.abs().max())
+        e_dc = float((dc.cpu().double()[1:] - dcr.detach()[1:]).abs().max())
+        print(f"K=4 N=48 {'aligned' if aligned else 'offset by one element'}: loss err {e_loss:.3e}, grad rel {e_grad:.3e}, dc err {e_dc:.3e}")
+        assert e_loss <= tol_abs and e_grad <= tol_grad and e_dc <= tol_abs
+        tp, fp, fn = losses.online_eval_counts(xd.detach(), yd)
+        assert torch.equal(torch.stack([tp, fp, fn]).cpu(), R.eval_counts(x, y))

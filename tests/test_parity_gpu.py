@@ -465,6 +465,71 @@ def test_scale_residual_and_channel_scale():
     parity.check_scale_residual(DEV, 20003, 64)
 
 
+# ---- LayerNorm on rows with |mean| >> std; the general-width kernels; quad widths at unaligned pointers (csrc/cl_norm.hip) ------------------------
+LN_LARGE_MEAN = [   # B, C, N, planar, pos — and the launcher branch the case reaches (launch_cl_layernorm_fwd / _bwd)
+    (2, 32, 4099, False, True),     # quad forward and backward (LPR = 8), gpos summed over the batch by the owning work-item
+    (1, 64, 1031, True, False),     # planar input: the general forward, C > 32 loop (one channel per lane); quad backward
+    (2, 24, 999, False, True),      # C <= 32, no quad width: the two-rows-per-wave branch of both general kernels, lanes 24..31 of a half idle
+    (1, 96, 2100, False, False),    # general, C % 64 != 0: lane + 64 k with the second round half empty
+    (1, 256, 515, False, True),     # quad, widest (LPR = 64: a row is a whole wave)
+]
+
+
+@pytest.mark.parametrize("ratio", [20.0, 100.0, 500.0])
+@pytest.mark.parametrize("case", LN_LARGE_MEAN)
+def test_layernorm_tokens_large_mean(case, ratio):
+    """Rows with |mean| / std = ratio against float64 LayerNorm of the kernel's own xt (parity.check_layernorm_tokens, mean_over_std): the variance must not be the
+    one-pass E[x^2] - mean^2, which loses (mean / std)^2 ulps of it."""
+    B, C, N, planar, pos = case
+    parity.check_layernorm_tokens(DEV, B, C, N, planar, pos, mean_over_std=ratio)
+
+
+def test_tblock3d_large_token_mean():
+    """The fused entry point dlka_tblock3d_* on an input whose tokens have |mean| / std ~ 100: forward and every gradient at the block's tolerances — the block's
+    LayerNorm is launch_cl_layernorm_fwd (general kernel: the block reads planar NCDHW), its backward the quad kernel on the saved {mean, rstd}."""
+    parity.check_tblock3d(DEV, 2, 32, (6, 5, 7), True, True, token_mean_over_std=100.0)
+
+
+@pytest.mark.parametrize("case", [(2, 16, 3001, False, True), (1, 48, 2050, False, False), (3, 96, 999, False, True), (1, 160, 1033, True, True),
+                                  (1, 192, 517, False, False)])
+def test_layernorm_tokens_general_widths(case):
+    """Widths outside {32, 64, 128, 256}: cl_layernorm_fwd_kernel / cl_layernorm_bwd_kernel in both directions.  C = 16: two rows per wave, half of each half idle, an
+    odd M leaves the last wave one row; 48, 96, 160, 192: lane + 64 k with 1, 2, 3, 3 rounds, the last one partial; with pos the backward adds gpos by atomics."""
+    B, C, N, planar, pos = case
+    parity.check_layernorm_tokens(DEV, B, C, N, planar, pos)
+
+
+def test_layernorm_tokens_refuses_257_channels():
+    parity.check_layernorm_unsupported_width(DEV)
+
+
+@pytest.mark.parametrize("case", [(30011, 96, True, True), (7777, 192, True, False), (4099, 384, False, True), (1031, 512, True, True)])
+def test_batchnorm_cl_general_widths(case):
+    """C % 32 == 0 outside the quad set: cl_bn_stats_kernel, cl_bn_apply_kernel, cl_bn_bwd_reduce_kernel, cl_bn_bwd_apply_kernel.  C = 96, 192: rpb = 256 / C = 2, 1 rows
+    per pass with 64 threads idle; C = 384, 512: the cb loop runs twice (384: its second round half empty); M is no multiple of the rows in flight, so the four-row
+    (statistics) and two-row (backward reduction) loops end in their single-row tails."""
+    parity.check_batchnorm_cl(DEV, *case)
+
+
+def test_batchnorm_cl_general_width_large_mean():
+    """mean / std = 500 at C = 96: the pivoted sums of the GENERAL statistics kernel (cl_bn_stats_kernel).  M = 1031 (33 workgroups, four-row loop and tail): the
+    check's reference is torch's fp32 batch_norm, which is itself 1.4e-4 from float64 here and leaves the bound (3e-4) from M ~ 4000 on (3.2e-4 at 4099, 6.1e-4 at 30011)."""
+    parity.check_batchnorm_cl(DEV, 1031, 96, True, True, mean_over_std=500.0)
+
+
+@pytest.mark.parametrize("M,C", [(20003, 96), (1031, 512), (1031, 20)])
+def test_scale_residual_general_widths(M, C):
+    """cl_scale_residual_fwd_kernel / _bwd_kernel (C = 96: two rows per pass, 64 threads idle; C = 512: the cb loop runs twice); C = 20: forward only (i % C on a
+    width that is no multiple of anything), the backward must refuse it with the shape error."""
+    parity.check_scale_residual(DEV, M, C)
+
+
+@pytest.mark.parametrize("op,C", [("ln", 64), ("ln", 32), ("bn_eval", 64), ("bn_train", 64), ("sr", 64)])
+def test_norm_ops_quad_width_at_unaligned_pointers(op, C):
+    """parity.check_norm_ops_unaligned: aligned (quad kernels), everything offset by one element (general kernels at a quad width), one operand at a time offset."""
+    parity.check_norm_ops_unaligned(DEV, op, 2050, C)
+
+
 @pytest.mark.parametrize("C,dims,training,pos", [(32, (16, 16, 16), True, True), (64, (8, 8, 8), False, False), (128, (6, 5, 7), True, False),
                                                   (256, (4, 4, 4), True, True)])
 def test_tblock3d_vs_oracle(C, dims, training, pos):

@@ -31,6 +31,12 @@ def test_fixture_case(name, dtype, label_dtype):
     C.check_case(name, FX["cases"][name], "cpu", dtype, label_dtype)
 
 
+@pytest.mark.parametrize("label_dtype", [torch.float32, torch.int64], ids=["labels_f32", "labels_i64"])
+def test_vector_shape_at_unaligned_pointers(label_dtype):
+    """A shape whose aligned twin takes the 16-byte kernels (K = 4, N % 4 == 0), logits and labels one element off 16-byte alignment: the scalar kernels."""
+    C.check_unaligned_vector_shape("cpu", label_dtype)
+
+
 @pytest.mark.parametrize("name", NAMES)
 def test_online_eval_counts(name):
     C.check_counts(FX["cases"][name], "cpu")
