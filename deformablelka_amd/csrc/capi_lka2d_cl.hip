@@ -85,6 +85,50 @@ int carve_prep2d(const Lka2dCl &G, float *base, Prep2d &t, const dlka_lka2d_para
     return launch_cl_prep_batch(pb, st);
 }
 
+// ---- the block's buffer layouts: one record and ONE carve function per buffer and direction (Carver, cl_host.h) ---------------------------------
+// `saved`: activation-typed tensors, the two offset fields (fp32 on both paths), the prepared weights
+struct Lka2dSaved { float *xt, *h, *a, *t1, *t2, *g1, *m, *spare, *o5, *o7, *prep; };
+Lka2dSaved carve_lka2d_saved(Carver &sv, const Lka2dCl &G)
+{
+    Lka2dSaved S;
+    float **act[8] = {&S.xt, &S.h, &S.a, &S.t1, &S.t2, &S.g1, &S.m, &S.spare};
+    for (float **t : act) *t = (float *)sv.take(G.E * G.SB);
+    S.o5 = (float *)sv.take(G.O5 * 4); S.o7 = (float *)sv.take(G.O7 * 4);
+    S.prep = (float *)sv.take(G.prep_floats() * 4);
+    return S;
+}
+// `workspace`, forward call: forward-only tensors where the backward call's first gradient buffers will be
+struct Lka2dFwdWs { float *yt, *a32, *t1_32; };   // a32, t1_32: bf16 path, the fp32 offset-determining chain
+Lka2dFwdWs carve_lka2d_fwd_ws(Carver &cv, const Lka2dCl &G)
+{
+    Lka2dFwdWs W;
+    W.yt = (float *)cv.take(G.E * 4); W.a32 = (float *)cv.take(G.E * 4); W.t1_32 = (float *)cv.take(G.E * 4);
+    return W;
+}
+// `workspace`, backward call.  The nine gradient buffers keep their fp32 size on the bf16 path: the two grad_input accumulators ARE fp32, others serve as
+// landing zones of tap-split sums.
+struct Lka2dBwdWs {
+    float *gyt, *gg1, *ga1, *gt2, *gta, *gt1, *gaa, *gab, *gh;
+    float *goff;     // the 7x7 conv's grad_offset
+    float *goff5;    // the 5x5 conv's, in a buffer of its own: the 7x7 offset net's weight gradient may still be reading `goff`
+    float *part;
+    void *reserve;   // 4096 bytes nothing uses (the size query has always counted them)
+    float *pad7, *pad5;   // the zero-padded copies the offset nets' weight gradients read (own buffers: both may be in flight on the internal stream at once)
+};
+Lka2dBwdWs carve_lka2d_bwd_ws(Carver &cv, const Lka2dCl &G)
+{
+    Lka2dBwdWs W;
+    float **grad[9] = {&W.gyt, &W.gg1, &W.ga1, &W.gt2, &W.gta, &W.gt1, &W.gaa, &W.gab, &W.gh};
+    for (float **g : grad) *g = (float *)cv.take(G.E * 4);
+    W.goff = (float *)cv.take(G.O7 * 4);
+    W.goff5 = (float *)cv.take(G.O5 * 4);
+    W.part = (float *)cv.take(G.part_floats() * 4);
+    W.reserve = cv.take(4096);
+    W.pad7 = (float *)cv.take_opt(dense_wgrad_pad_bytes(G.off7), dense_wgrad_pad_bytes(G.off7) != 0);
+    W.pad5 = (float *)cv.take_opt(dense_wgrad_pad_bytes(G.off5), dense_wgrad_pad_bytes(G.off5) != 0);
+    return W;
+}
+
 void fill_ddw(DwArgs2d &d, const Lka2dCl &G, int k, int pad, int dil)
 {
     memset(&d, 0, sizeof(d));
@@ -101,47 +145,41 @@ int lka2d_cl_supported(int B, int C, int H, int W, int dtype)
     return dense_fwd_supported(block_conv2d(B, C, 50, H, W, 5, 2, 1)) ? 1 : 0;
 }
 
-// saved: xt, h, a, t1, t2, g1, m, (spare) — activation-typed —, o5, o7 (fp32), prepared weights
 size_t lka2d_cl_saved_bytes(int B, int C, int H, int W, int dtype)
 {
-    Lka2dCl G(B, C, H, W, dtype);
-    return 8 * align256(G.E * G.SB) + align256(G.O5 * 4) + align256(G.O7 * 4) + align256(G.prep_floats() * 4);
+    const Lka2dCl G(B, C, H, W, dtype);
+    return carved_bytes([&](Carver &m) { carve_lka2d_saved(m, G); });
 }
 
-// (the nine gradient buffers keep their fp32 size on the bf16 path: the two grad_input accumulators ARE fp32, two more serve as the forward
-//  pass's fp32 chain tensors and as landing zones of tap-split sums)
-// (diagnostics) the offset tensors inside `saved`: lka2d_cl_forward carves xt, h, a, t1, t2, g1, m, spare, then o5, o7 (fp32 on both paths)
+// (diagnostics) the offset tensors inside `saved`
 int lka2d_cl_saved_offsets(int B, int C, int H, int W, int dtype, size_t byte_offsets[2], int *elem_bytes)
 {
-    Lka2dCl G(B, C, H, W, dtype);
-    byte_offsets[0] = 8 * align256(G.E * G.SB);
-    byte_offsets[1] = byte_offsets[0] + align256(G.O5 * 4);
+    Carver sv = Carver::probing();
+    const Lka2dSaved S = carve_lka2d_saved(sv, Lka2dCl(B, C, H, W, dtype));
+    byte_offsets[0] = sv.offset_of(S.o5);
+    byte_offsets[1] = sv.offset_of(S.o7);
     *elem_bytes = 4;
     return DLKA_OK;
 }
 
 size_t lka2d_cl_workspace_bytes(int B, int C, int H, int W, int dtype)
 {
-    Lka2dCl G(B, C, H, W, dtype);
-    return 9 * align256(G.E * 4) + align256(G.O7 * 4) + align256(G.O5 * 4) + align256(G.part_floats() * 4) + align256(4096) +   // (O5: the second conv's grad_offset, see lka2d_cl_backward)
-           dense_wgrad_pad_bytes(G.off7) + dense_wgrad_pad_bytes(G.off5);   // the zero-padded copies the offset nets' weight gradients read (round 5)
+    const Lka2dCl G(B, C, H, W, dtype);
+    const size_t f = carved_bytes([&](Carver &m) { carve_lka2d_fwd_ws(m, G); }), b = carved_bytes([&](Carver &m) { carve_lka2d_bwd_ws(m, G); });
+    return f > b ? f : b;
 }
 
 int lka2d_cl_forward(const void *x_, const dlka_lka2d_params *p, void *y_, void *saved, size_t saved_bytes, void *workspace, size_t workspace_bytes, int B,
                      int C, int H, int W, int dtype, hipStream_t st)
 {
     Lka2dCl G(B, C, H, W, dtype);
-    const size_t SB = G.SB;
     const int bf = G.bf;
     Carver sv(saved, saved_bytes), cv(workspace, workspace_bytes);
-    float *xt = (float *)sv.take(G.E * SB), *h = (float *)sv.take(G.E * SB), *a = (float *)sv.take(G.E * SB), *t1 = (float *)sv.take(G.E * SB);
-    float *t2 = (float *)sv.take(G.E * SB), *g1 = (float *)sv.take(G.E * SB), *m = (float *)sv.take(G.E * SB), *spare = (float *)sv.take(G.E * SB);
-    float *o5 = (float *)sv.take(G.O5 * 4), *o7 = (float *)sv.take(G.O7 * 4);
-    float *prep = (float *)sv.take(G.prep_floats() * 4);
-    float *yt = (float *)cv.take(G.E * 4);
-    float *a32 = (float *)cv.take(G.E * 4), *t1_32 = (float *)cv.take(G.E * 4);   // bf16 path: the fp32 offset-determining chain
-    (void)spare;
+    const Lka2dSaved S = carve_lka2d_saved(sv, G);
+    const Lka2dFwdWs Wf = carve_lka2d_fwd_ws(cv, G);
     if (!sv.ok() || !cv.ok()) return DLKA_ERR_WORKSPACE;
+    float *xt = S.xt, *h = S.h, *a = S.a, *t1 = S.t1, *t2 = S.t2, *g1 = S.g1, *m = S.m, *o5 = S.o5, *o7 = S.o7, *prep = S.prep;
+    float *yt = Wf.yt, *a32 = Wf.a32, *t1_32 = Wf.t1_32;
     const float *N0 = nullptr;
     Prep2d PW;
     DLKA_TRY(carve_prep2d(G, prep, PW, p, st, true));
@@ -168,24 +206,15 @@ int lka2d_cl_backward(const void *x_, const dlka_lka2d_params *p, const void *gy
 {
     (void)x_;
     Lka2dCl G(B, C, H, W, dtype);
-    const size_t SB = G.SB;
     const int bf = G.bf;
-    Carver sv((void *)saved, saved_bytes), cv(workspace, workspace_bytes);
-    const float *xt = (float *)sv.take(G.E * SB), *h = (float *)sv.take(G.E * SB), *a = (float *)sv.take(G.E * SB), *t1 = (float *)sv.take(G.E * SB);
-    const float *t2 = (float *)sv.take(G.E * SB), *g1 = (float *)sv.take(G.E * SB), *m = (float *)sv.take(G.E * SB);
-    (void)sv.take(G.E * SB);
-    const float *o5 = (float *)sv.take(G.O5 * 4), *o7 = (float *)sv.take(G.O7 * 4);
-    float *prep = (float *)sv.take(G.prep_floats() * 4);
-    float *gyt = (float *)cv.take(G.E * 4), *gg1 = (float *)cv.take(G.E * 4), *ga1 = (float *)cv.take(G.E * 4), *gt2 = (float *)cv.take(G.E * 4);
-    float *gta = (float *)cv.take(G.E * 4), *gt1 = (float *)cv.take(G.E * 4), *gaa = (float *)cv.take(G.E * 4), *gab = (float *)cv.take(G.E * 4);
-    float *gh = (float *)cv.take(G.E * 4);
-    float *goff = (float *)cv.take(G.O7 * 4);
-    float *goff5 = (float *)cv.take(G.O5 * 4);   // the 5x5 conv's grad_offset in a buffer of its own: the 7x7 offset net's weight gradient may still be reading `goff`
-    float *part = (float *)cv.take(G.part_floats() * 4);
-    (void)cv.take(4096);
-    float *pad7 = (float *)cv.take_opt(dense_wgrad_pad_bytes(G.off7), dense_wgrad_pad_bytes(G.off7) != 0);   // (own buffers: both weight gradients may be in flight on the
-    float *pad5 = (float *)cv.take_opt(dense_wgrad_pad_bytes(G.off5), dense_wgrad_pad_bytes(G.off5) != 0);   //  internal stream at once)
+    Carver sv(saved, saved_bytes), cv(workspace, workspace_bytes);
+    const Lka2dSaved S = carve_lka2d_saved(sv, G);
+    const Lka2dBwdWs Wb = carve_lka2d_bwd_ws(cv, G);
     if (!sv.ok() || !cv.ok()) return DLKA_ERR_WORKSPACE;
+    const float *xt = S.xt, *h = S.h, *a = S.a, *t1 = S.t1, *t2 = S.t2, *g1 = S.g1, *m = S.m, *o5 = S.o5, *o7 = S.o7;
+    float *prep = S.prep;
+    float *gyt = Wb.gyt, *gg1 = Wb.gg1, *ga1 = Wb.ga1, *gt2 = Wb.gt2, *gta = Wb.gta, *gt1 = Wb.gt1, *gaa = Wb.gaa, *gab = Wb.gab, *gh = Wb.gh;
+    float *goff = Wb.goff, *goff5 = Wb.goff5, *part = Wb.part, *pad7 = Wb.pad7, *pad5 = Wb.pad5;
     const float *N0 = nullptr;
     Prep2d PW;
     DLKA_TRY(carve_prep2d(G, prep, PW, p, st, false));

@@ -52,11 +52,15 @@ inline SameConv dw_conv(int B, int C, int D, int H, int W, const int *k, const i
     return s;
 }
 
+// weight-gradient partial sums: in the backward workspace, or the caller's block-private area when the fold is deferred (dlka_lka3d_tokens_partials_bytes_v)
+struct TokPartials { float *p2, *c1, *p1, *off, *dcn, *stage5, *stage7; };
+
 struct TokGeoms {
     SameConv pw, dw5, dw7, offc, dcn;   // (dw5 / dw7: conv0 / conv_spatial, whatever their kernels are in the variant)
     SameConv dw5_f, dw7_f, offc_f, pw_f;   // the forward chain's geometries: == dw5 / dw7 / offc / pw on the fp32 path, their fp32-storage twins on DLKA_BF16
     size_t E, Off, GOff;   // GOff: the backward's internal grad_offset buffer, 96 channel planes per batch (packed layout, DeformBwdArgs::goff_cpad)
     size_t SB;             // bytes per activation element (4, or 2 on the DLKA_BF16 path)
+    size_t part_bytes;     // size of the TokPartials layout (carve_partials, measured once here: both workspace layouts hold it)
     TokGeoms(int B, int C, int D, int H, int W, int dtype = DLKA_F32, int variant = DLKA_LKA3D_SYNAPSE)
     {
         const int bf = dtype == DLKA_BF16 ? 1 : 0;
@@ -75,6 +79,7 @@ struct TokGeoms {
         E = (size_t)B * C * D * H * W;
         Off = (size_t)B * 81 * D * H * W;
         GOff = (size_t)B * 96 * D * H * W;
+        part_bytes = carved_bytes([&](Carver &m) { carve_partials(m); });
     }
     size_t wp_floats() const
     {
@@ -111,7 +116,16 @@ struct TokGeoms {
     size_t part_off() const { return (cl_wgrad_part_floats_mode(pw.M, 27, 81, pw.Cin, 0) + 63) & ~(size_t)63; }
     size_t part_dcn() const { return (cl_wgrad_part_floats_mode(pw.M, 27, pw.Cin, pw.Cin, 1) + 63) & ~(size_t)63; }
     size_t stage_dw() const { return (size_t)(dw5.K + 1 + dw7.K + 1) * pw.Cin; }   // conv0 [K0 + 1][C] then conv_spatial [K1 + 1][C]
-    size_t part_floats() const { return 3 * part_pw() + part_off() + part_dcn() + ((stage_dw() + 63) & ~(size_t)63); }
+    TokPartials carve_partials(Carver &pc) const
+    {
+        TokPartials P;
+        P.p2 = (float *)pc.take(part_pw() * 4); P.c1 = (float *)pc.take(part_pw() * 4); P.p1 = (float *)pc.take(part_pw() * 4);
+        P.off = (float *)pc.take(part_off() * 4);
+        P.dcn = (float *)pc.take(part_dcn() * 4);
+        P.stage5 = (float *)pc.take(stage_dw() * 4);   // the depthwise staging is ONE area (one zero fill): conv_spatial's rows follow conv0's
+        P.stage7 = P.stage5 ? P.stage5 + (size_t)(dw5.K + 1) * pw.Cin : nullptr;
+        return P;
+    }
 };
 
 // carve + (forward only) fill the prepared-weight area
@@ -120,6 +134,100 @@ struct TokPrep {
     float *off_f, *off_b, *dcn_f, *dcn_b, *dw5_f, *dw5_b, *dw7_f, *dw7_b;
     float *dcn_b16;   // bf16 path: the deformable conv's column-matrix weights as two-term bf16 records (grad_offset / grad_input on the bf16 matrix cores)
 };
+
+// ---- the block's buffer layouts: one record and ONE carve function per buffer and direction (Carver, cl_host.h) ---------------------------------
+// `saved`, forward to backward call.  Activation-typed (bf16 on DLKA_BF16) except the fp32 offsets and prepared weights.  Sized without slack.
+struct TokSaved {
+    float *h, *a, *t1, *t, *off, *f, *g1;
+    float *prep;   // the prepared weights (carve_prep)
+    float *m;      // gate output, kept: proj_2's weight gradient needs it
+};
+inline TokSaved carve_tok_saved(Carver &sv, const TokGeoms &G)
+{
+    const size_t act = G.E * G.SB;
+    TokSaved S;
+    S.h = (float *)sv.take(act); S.a = (float *)sv.take(act); S.t1 = (float *)sv.take(act); S.t = (float *)sv.take(act);
+    S.off = (float *)sv.take(G.Off * 4);
+    S.f = (float *)sv.take(act); S.g1 = (float *)sv.take(act);
+    S.prep = (float *)sv.take(G.prep_floats() * 4);
+    S.m = (float *)sv.take(act);
+    return S;
+}
+inline size_t tok_saved_bytes(const TokGeoms &G) { return carved_bytes([&](Carver &m) { carve_tok_saved(m, G); }); }
+
+// blocked inputs of the opt-in LDS-brick depthwise convs (DLKA_DW_LDS), both directions: sized and carved only when that mode is on — and only when both fit,
+// so a mode switched on between the size query and the call keeps the register-row kernels instead of overrunning the workspace
+inline void carve_tok_blk(Carver &cv, const TokGeoms &G, float *&blkA, float *&blkB)
+{
+    const bool want_blk = cl_dwconv_lds_mode() != 0;
+    blkA = (float *)cv.take_opt(G.blk_floats() * 4, want_blk);
+    blkB = (float *)cv.take_opt(G.blk_floats() * 4, want_blk && cv.got(blkA));
+    if (!blkB) blkA = nullptr;
+}
+
+// `workspace`, backward call (the front of the buffer; the tail is TokWsTail)
+struct TokBwdWs {
+    float *wp_reserve;   // (unused since the prepared weights moved into `saved`; the sizes it contributes to are kept)
+    float *part;         // TokPartials, unless the caller brings a block-private area
+    // every intermediate gradient has its own buffer: the weight-gradient stream reads them while the data-gradient chain moves on.  fp32-sized on both
+    // dtypes: gta and the split scratch ARE fp32
+    float *gg1, *ga1, *gf, *gta, *gt, *gt1, *ga2, *gh;
+    float *goff, *scratch;
+    float *samp;         // ALWAYS carved at its capacity: the layout behind it does not depend on the gather switch
+    float *blkA, *blkB;
+    float *padt;         // the zero-padded copy of t the offset conv's weight gradient reads (null when the workspace was sized without it: the unpadded kernels)
+};
+inline TokBwdWs carve_tok_bwd_ws(Carver &cv, const TokGeoms &G)
+{
+    TokBwdWs W;
+    W.wp_reserve = (float *)cv.take(G.wp_floats() * 4);
+    W.part = (float *)cv.take(G.part_bytes);
+    float **grad[8] = {&W.gg1, &W.ga1, &W.gf, &W.gta, &W.gt, &W.gt1, &W.ga2, &W.gh};
+    for (float **g : grad) *g = (float *)cv.take(G.E * 4);
+    W.goff = (float *)cv.take(G.GOff * 4);
+    W.scratch = (float *)cv.take(G.scratch_floats() * 4);
+    W.samp = G.samp_capacity_floats() ? (float *)cv.take(G.samp_capacity_floats() * 4) : nullptr;
+    carve_tok_blk(cv, G, W.blkA, W.blkB);
+    const size_t pad = dense_wgrad_pad_bytes(G.offc);
+    W.padt = (float *)cv.take_opt(pad, pad != 0);
+    return W;
+}
+
+// `workspace`, forward call (front).  Forward-only tensors, dead when the call returns; they sit where the backward call's gradient buffers gg1 .. gt will be,
+// so that the forward pass never needs more than the backward pass does.
+struct TokFwdWs {
+    float *wp_reserve, *part_reserve, *gg1_reserve;   // (nothing of the forward pass lives here)
+    float *a32, *t1_32, *t_32;                        // bf16 path: the fp32 offset-determining chain (TokGeoms)
+    float *blkA, *blkB;
+};
+inline TokFwdWs carve_tok_fwd_ws(Carver &cv, const TokGeoms &G)
+{
+    TokFwdWs W;
+    W.wp_reserve = (float *)cv.take(G.wp_floats() * 4);
+    W.part_reserve = (float *)cv.take(G.part_bytes);
+    W.gg1_reserve = (float *)cv.take(G.E * 4);
+    W.a32 = (float *)cv.take(G.E * 4); W.t1_32 = (float *)cv.take(G.E * 4); W.t_32 = (float *)cv.take(G.E * 4);
+    carve_tok_blk(cv, G, W.blkA, W.blkB);
+    return W;
+}
+
+// `workspace`, the tail: behind everything either direction carves from the front.  Continues a forward carve (cv stands at the forward call's end)
+struct TokWsTail {
+    void *reserve;   // 4096 bytes nothing uses (the size queries have always counted them; memory use is behaviour)
+    float *slab;     // forward pass, small stages: the deformable conv's tap-range slabs (null: none needed)
+};
+inline TokWsTail carve_tok_ws_tail(Carver &cv, const TokGeoms &G)
+{
+    cv.skip_to(carved_bytes([&](Carver &m) { carve_tok_bwd_ws(m, G); }));
+    TokWsTail T;
+    T.reserve = cv.take(4096);
+    T.slab = deform_fwd_slab_floats(G.dcn) ? (float *)cv.take(deform_fwd_slab_floats(G.dcn) * 4) : nullptr;
+    return T;
+}
+inline size_t tok_workspace_bytes(const TokGeoms &G)
+{
+    return carved_bytes([&](Carver &m) { carve_tok_fwd_ws(m, G); carve_tok_ws_tail(m, G); });
+}
 
 // (capi_lka3d_tokens.hip)
 bool tokens_supported(int B, int C, int D, int H, int W, int variant = DLKA_LKA3D_SYNAPSE);

@@ -74,8 +74,7 @@ int dlka_lka3d_tokens_supported(int B, int C, int D, int H, int W, int dtype) { 
 size_t dlka_lka3d_tokens_saved_bytes_v(int B, int C, int D, int H, int W, int dtype, int variant)
 {
     if (!dlka_lka3d_tokens_supported_v(B, C, D, H, W, dtype, variant)) return 0;
-    TokGeoms G(B, C, D, H, W, dtype, variant);
-    return 7 * align256(G.E * G.SB) + align256(G.Off * 4) + align256(G.prep_floats() * 4);
+    return tok_saved_bytes(TokGeoms(B, C, D, H, W, dtype, variant));
 }
 size_t dlka_lka3d_tokens_saved_bytes(int B, int C, int D, int H, int W, int dtype) { return dlka_lka3d_tokens_saved_bytes_v(B, C, D, H, W, dtype, DLKA_LKA3D_SYNAPSE); }
 
@@ -83,11 +82,7 @@ size_t dlka_lka3d_tokens_workspace_bytes(int B, int C, int D, int H, int W, int 
 size_t dlka_lka3d_tokens_workspace_bytes_v(int B, int C, int D, int H, int W, int dtype, int variant)
 {
     if (!dlka_lka3d_tokens_supported_v(B, C, D, H, W, dtype, variant)) return 0;
-    TokGeoms G(B, C, D, H, W, dtype, variant);   // (the eight gradient buffers keep their fp32 size on the bf16 path: gta and the split scratch ARE fp32)
-    return align256(G.wp_floats() * 4) + align256(G.part_floats() * 4) + 8 * align256(G.E * 4) + align256(G.GOff * 4) +
-           align256(G.scratch_floats() * 4) + align256(G.samp_capacity_floats() * 4) + (cl_dwconv_lds_mode() ? 2 * align256(G.blk_floats() * 4) : 0) + align256(4096) +
-           dense_wgrad_pad_bytes(G.offc) +   // the zero-padded copy of t the offset conv's weight gradient reads (round 5)
-           align256(deform_fwd_slab_floats(G.dcn) * 4);   // forward pass, small stages: the deformable conv's tap-range slabs, at the END of the workspace (round 6)
+    return tok_workspace_bytes(TokGeoms(B, C, D, H, W, dtype, variant));
 }
 
 // x_f32 (DLKA_BF16 only, optional): the caller's UNROUNDED fp32 twin of the bf16 input x.  The chain that decides where the deformable conv samples then starts
@@ -107,27 +102,15 @@ int dlka::tokens_forward_impl(const void *x_, const dlka_lka3d_params *p, void *
     // DLKA_BF16: x, y and every saved activation are bf16 storage (`float *` below is then just an address: the kernels reinterpret it);
     // offsets, prepared weights, parameters and all accumulators are fp32
     TokGeoms G(B, C, D, H, W, dtype, variant);
-    const size_t SB = G.SB;
     Carver sv(saved, saved_bytes), cv(workspace, workspace_bytes);
-    float *h = (float *)sv.take(G.E * SB), *a = (float *)sv.take(G.E * SB), *t1 = (float *)sv.take(G.E * SB), *t = (float *)sv.take(G.E * SB);
-    float *off = (float *)sv.take(G.Off * 4), *f = (float *)sv.take(G.E * SB), *g1 = (float *)sv.take(G.E * SB);
-    float *prep = (float *)sv.take(G.prep_floats() * 4);
-    float *m = (float *)sv.take(G.E * SB);   // gate output, kept: proj_2's weight gradient needs it
-    (void)cv.take(G.wp_floats() * 4);
-    (void)cv.take(G.part_floats() * 4);
-    (void)cv.take(G.E * 4);   // (layout kept: the first of the backward pass's eight gradient buffers)
-    // bf16 path: the fp32 offset-determining chain (TokGeoms): a32, t1_32, t_32 — the next three of the backward pass's gradient buffers
-    float *a32 = (float *)cv.take(G.E * 4), *t1_32 = (float *)cv.take(G.E * 4), *t_32 = (float *)cv.take(G.E * 4);
-    // blocked inputs of the opt-in LDS-brick depthwise convs (DLKA_DW_LDS): sized and carved only when that mode is on — and only when both fit, so a mode
-    // switched on between the size query and this call keeps the register-row kernels instead of overrunning the workspace
-    const bool want_blk = cl_dwconv_lds_mode() != 0;
-    float *blkA = (float *)cv.take_opt(G.blk_floats() * 4, want_blk), *blkB = (float *)cv.take_opt(G.blk_floats() * 4, want_blk && blkA);
-    if (!blkB) blkA = nullptr;
+    const TokSaved S = carve_tok_saved(sv, G);
+    const TokFwdWs Wf = carve_tok_fwd_ws(cv, G);
     if (!sv.ok() || !cv.ok()) return DLKA_ERR_WORKSPACE;
-    // the deformable conv's slabs (small stages) live at the END of the workspace: behind everything either pass carves from the front
-    const size_t slab_bytes = align256(deform_fwd_slab_floats(G.dcn) * 4);
-    if (slab_bytes && workspace_bytes < dlka_lka3d_tokens_workspace_bytes_v(B, C, D, H, W, dtype, variant)) return DLKA_ERR_WORKSPACE;
-    float *slab = slab_bytes ? (float *)((char *)workspace + dlka_lka3d_tokens_workspace_bytes_v(B, C, D, H, W, dtype, variant) - slab_bytes) : nullptr;
+    TokWsTail Wt = {nullptr, nullptr};
+    if (deform_fwd_slab_floats(G.dcn)) Wt = carve_tok_ws_tail(cv, G);   // (a workspace without the tail serves every stage that needs no slabs)
+    if (!cv.ok()) return DLKA_ERR_WORKSPACE;
+    float *h = S.h, *a = S.a, *t1 = S.t1, *t = S.t, *off = S.off, *f = S.f, *g1 = S.g1, *prep = S.prep, *m = S.m;
+    float *a32 = Wf.a32, *t1_32 = Wf.t1_32, *t_32 = Wf.t_32, *blkA = Wf.blkA, *blkB = Wf.blkB, *slab = Wt.slab;
     const bool bf = dtype == DLKA_BF16;
     const float *x = (const float *)x_;
     float *y = (float *)y_;
@@ -233,14 +216,11 @@ int dlka_lka3d_tokens_prepare_plan(int nblocks, const dlka_lka3d_params *params,
         if (!dlka_lka3d_tokens_supported(B, C, D, H, W, dtype)) return DLKA_ERR_UNSUPPORTED;
         TokGeoms G(B, C, D, H, W, dtype);
         Carver sv(saved[k], saved_bytes[k]);
-        for (int e = 0; e < 4; ++e) (void)sv.take(G.E * G.SB);   // h, a, t1, t
-        (void)sv.take(G.Off * 4);
-        (void)sv.take(G.E * G.SB); (void)sv.take(G.E * G.SB);     // f, g1
-        float *prep = (float *)sv.take(G.prep_floats() * 4);
-        if (!sv.ok()) return DLKA_ERR_WORKSPACE;
+        const TokSaved S = carve_tok_saved(sv, G);
+        if (!S.prep) return DLKA_ERR_WORKSPACE;   // (the plan writes the prepared weights only: a buffer that ends behind them will do)
         TokPrep PW;
         PrepBatch pb;
-        DLKA_TRY(carve_prep(G, prep, PW, &params[k], nullptr, true, nullptr, &pb));
+        DLKA_TRY(carve_prep(G, S.prep, PW, &params[k], nullptr, true, nullptr, &pb));
         if (pb.njobs > PLAN_JOBS_PER_BLOCK) return DLKA_ERR_UNSUPPORTED;
         for (int j = 0; j < pb.njobs; ++j) {
             first[nj] = nb;
@@ -291,8 +271,7 @@ size_t fin_jobs_off(int nb) { return align256(sizeof(FinPlanHeader) + (size_t)(n
 size_t dlka_lka3d_tokens_partials_bytes_v(int B, int C, int D, int H, int W, int dtype, int variant)
 {
     if (!dlka_lka3d_tokens_supported_v(B, C, D, H, W, dtype, variant)) return 0;
-    TokGeoms G(B, C, D, H, W, dtype, variant);
-    return align256(G.part_floats() * 4);
+    return TokGeoms(B, C, D, H, W, dtype, variant).part_bytes;
 }
 
 size_t dlka_wgrad_finalize_plan_bytes(int nblocks)
@@ -438,40 +417,26 @@ int dlka::tokens_backward_impl(const void *x_, const dlka_lka3d_params *p, const
     // DLKA_BF16: x, gy, gx, the saved activations and the intermediate gradients gg1, ga1, gf, gt, gt1, gh are bf16 storage; grad_offset, the
     // deformable conv's grad_input accumulator gta (atomics), the weight-gradient partials and the parameter gradients are fp32
     TokGeoms G(B, C, D, H, W, dtype, variant);
-    const size_t SB = G.SB;
     const bool bf = dtype == DLKA_BF16;
-    Carver sv((void *)saved, saved_bytes), cv(workspace, workspace_bytes);
-    const float *h = (float *)sv.take(G.E * SB), *a = (float *)sv.take(G.E * SB), *t1 = (float *)sv.take(G.E * SB), *t = (float *)sv.take(G.E * SB);
-    const float *off = (float *)sv.take(G.Off * 4), *f = (float *)sv.take(G.E * SB), *g1 = (float *)sv.take(G.E * SB);
-    float *prep = (float *)sv.take(G.prep_floats() * 4);   // written by the matching forward call
-    const float *m = (const float *)sv.take(G.E * SB);
-    (void)cv.take(G.wp_floats() * 4);
-    float *part = (float *)cv.take(G.part_floats() * 4);
-    if (partials) {
-        if (partials_bytes < G.part_floats() * 4) return DLKA_ERR_WORKSPACE;
-        part = (float *)partials;
-    }
-    // every intermediate gradient has its own buffer: the weight-gradient stream reads them while the data-gradient chain moves on
-    float *gg1 = (float *)cv.take(G.E * 4), *ga1 = (float *)cv.take(G.E * 4), *gf = (float *)cv.take(G.E * 4), *gta = (float *)cv.take(G.E * 4);
-    float *gt = (float *)cv.take(G.E * 4), *gt1 = (float *)cv.take(G.E * 4), *ga2 = (float *)cv.take(G.E * 4), *gh = (float *)cv.take(G.E * 4);
-    float *goff = (float *)cv.take(G.GOff * 4);
-    float *scratch = (float *)cv.take(G.scratch_floats() * 4);
-    // the sample area is ALWAYS carved at its capacity (the layout behind it does not depend on the gather switch, which is read once here)
-    float *samp = G.samp_capacity_floats() ? (float *)cv.take(G.samp_capacity_floats() * 4) : nullptr;
-    if (wgrad_gather()) samp = nullptr;
-    const bool want_blk = cl_dwconv_lds_mode() != 0;   // (see the forward pass)
-    float *blkA = (float *)cv.take_opt(G.blk_floats() * 4, want_blk), *blkB = (float *)cv.take_opt(G.blk_floats() * 4, want_blk && blkA);
-    if (!blkB) blkA = nullptr;
-    float *padt = (float *)cv.take_opt(dense_wgrad_pad_bytes(G.offc), dense_wgrad_pad_bytes(G.offc) != 0);   // (null when the workspace was sized without it: the unpadded kernels)
+    Carver sv(saved, saved_bytes), cv(workspace, workspace_bytes);
+    const TokSaved S = carve_tok_saved(sv, G);   // (written by the matching forward call)
+    const TokBwdWs Wb = carve_tok_bwd_ws(cv, G);
     if (!sv.ok() || !cv.ok()) return DLKA_ERR_WORKSPACE;
+    Carver pc(partials ? partials : Wb.part, partials ? partials_bytes : G.part_bytes);
+    const TokPartials P = G.carve_partials(pc);
+    if (!pc.ok()) return DLKA_ERR_WORKSPACE;
+    const float *h = S.h, *a = S.a, *t1 = S.t1, *t = S.t, *off = S.off, *f = S.f, *g1 = S.g1, *m = S.m;
+    float *prep = S.prep;
+    float *gg1 = Wb.gg1, *ga1 = Wb.ga1, *gf = Wb.gf, *gta = Wb.gta, *gt = Wb.gt, *gt1 = Wb.gt1, *ga2 = Wb.ga2, *gh = Wb.gh;
+    float *goff = Wb.goff, *scratch = Wb.scratch, *blkA = Wb.blkA, *blkB = Wb.blkB, *padt = Wb.padt;
+    float *samp = wgrad_gather() ? nullptr : Wb.samp;   // (the switch is read once here)
     const float *x = (const float *)x_, *gy = (const float *)gy_;
     float *gx = (float *)gx_;
     const float *N0 = nullptr;
     TokPrep PW;
     DLKA_TRY(carve_prep(G, prep, PW, p, st, false));
     // partial-sum areas, one per weight gradient; folded by ONE launch at the end
-    float *part_p2 = part, *part_c1 = part_p2 + G.part_pw(), *part_p1 = part_c1 + G.part_pw(), *part_off = part_p1 + G.part_pw();
-    float *part_dcn = part_off + G.part_off(), *stage5 = part_dcn + G.part_dcn(), *stage7 = stage5 + (size_t)(G.dw5.K + 1) * C;
+    float *part_p2 = P.p2, *part_c1 = P.c1, *part_p1 = P.p1, *part_off = P.off, *part_dcn = P.dcn, *stage5 = P.stage5, *stage7 = P.stage7;
     FinalizeBatch fb;
     memset(&fb, 0, sizeof(fb));
 
@@ -594,8 +559,8 @@ int dlka_lka3d_tokens_saved_offsets_v(int B, int C, int D, int H, int W, int dty
 {
     if (!byte_offset) return DLKA_ERR_NULL;
     if (!dlka_lka3d_tokens_supported_v(B, C, D, H, W, dtype, variant)) return DLKA_ERR_UNSUPPORTED;
-    TokGeoms G(B, C, D, H, W, dtype, variant);
-    *byte_offset = 4 * align256(G.E * G.SB);   // tokens_forward_impl carves h, a, t1, t, then the offsets
+    Carver sv = Carver::probing();
+    *byte_offset = sv.offset_of(carve_tok_saved(sv, TokGeoms(B, C, D, H, W, dtype, variant)).off);
     return DLKA_OK;
 }
 

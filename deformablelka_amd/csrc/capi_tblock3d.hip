@@ -12,7 +12,10 @@ namespace {
 struct TBlockGeoms {
     SameConv c3, pw;   // the 3^3 dense convs of UnetResBlock, the 1x1x1 conv of conv8
     size_t E, M;
-    TBlockGeoms(int B, int C, int D, int H, int W)
+    TokGeoms lka;      // the D-LKA attention inside
+    mutable size_t lka_ws = 0;   // its workspace size (both workspace layouts start with it; measured on first use)
+    size_t lka_ws_bytes() const { return lka_ws ? lka_ws : (lka_ws = tok_workspace_bytes(lka)); }
+    TBlockGeoms(int B, int C, int D, int H, int W, int dtype, int variant) : lka(B, C, D, H, W, dtype, variant)
     {
         dlka_conv_geom g;
         memset(&g, 0, sizeof(g));
@@ -37,7 +40,7 @@ struct TBlockSaved {
     size_t lka_bytes;
 };
 
-bool carve_tblock_saved(Carver &sv, const TBlockGeoms &G, int B, int C, int D, int H, int W, TBlockSaved &S, int variant = DLKA_LKA3D_SYNAPSE, int dtype = DLKA_F32)
+bool carve_tblock_saved(Carver &sv, const TBlockGeoms &G, TBlockSaved &S)
 {
     S.xt = (float *)sv.take(G.E * 4); S.xn = (float *)sv.take(G.E * 4); S.e = (float *)sv.take(G.E * 4); S.attn = (float *)sv.take(G.E * 4);
     S.c1 = (float *)sv.take(G.E * 4); S.a1 = (float *)sv.take(G.E * 4); S.c2 = (float *)sv.take(G.E * 4); S.rd = (float *)sv.take(G.E * 4);
@@ -45,9 +48,50 @@ bool carve_tblock_saved(Carver &sv, const TBlockGeoms &G, int B, int C, int D, i
     S.w1_f = (float *)sv.take(dense_wp_floats(G.c3) * 4); S.w1_b = (float *)sv.take(dense_wp_floats(G.c3) * 4);
     S.w2_f = (float *)sv.take(dense_wp_floats(G.c3) * 4); S.w2_b = (float *)sv.take(dense_wp_floats(G.c3) * 4);
     S.w8_f = (float *)sv.take(dense_wp_floats(G.pw) * 4); S.w8_b = (float *)sv.take(dense_wp_floats(G.pw) * 4);
-    S.lka_bytes = dlka_lka3d_tokens_saved_bytes_v(B, C, D, H, W, dtype, variant);
-    S.lka = sv.take(S.lka_bytes);
+    S.lka_bytes = tok_saved_bytes(G.lka);
+    S.lka = sv.take(S.lka_bytes);   // TokSaved
     return sv.ok();
+}
+
+// `workspace`, both directions: the attention's own workspace in front, then what the wrapper's kernels use
+struct TBlockFwdWs {
+    void *lka;
+    size_t lka_bytes;
+    float *wp_reserve;   // (unused since the prepared weights moved into `saved`)
+    float *sums;         // BatchNorm sums (atomics)
+    float *xn32;         // mixed mode: LayerNorm's unrounded output, for the offset-determining chain of the attention.  Forward-only: it sits where the backward
+                         // call's partial sums and gradient buffers will be
+};
+TBlockFwdWs carve_tblock_fwd_ws(Carver &cv, const TBlockGeoms &G, bool want_xn32)
+{
+    TBlockFwdWs W;
+    W.lka_bytes = G.lka_ws_bytes();
+    W.lka = cv.take(W.lka_bytes);
+    W.wp_reserve = (float *)cv.take(G.wp_floats() * 4);
+    W.sums = (float *)cv.take(4096);
+    W.xn32 = want_xn32 ? (float *)cv.take(G.E * 4) : nullptr;
+    return W;
+}
+struct TBlockBwdWs {
+    void *lka, *lka_part;   // lka_part: the attention's partial sums when the pass is split (phase 1 / 2): outside its own workspace
+    size_t lka_bytes, lka_part_bytes;
+    float *wp_reserve, *part1, *part2, *part8;
+    float *b[6];            // gradient buffers (the phased backward call says which gradient lives in which)
+    float *sums;
+};
+TBlockBwdWs carve_tblock_bwd_ws(Carver &cv, const TBlockGeoms &G)
+{
+    TBlockBwdWs W;
+    W.lka_bytes = G.lka_ws_bytes();
+    W.lka = cv.take(W.lka_bytes);
+    W.wp_reserve = (float *)cv.take(G.wp_floats() * 4);
+    W.part1 = (float *)cv.take(G.part_floats() * 4); W.part2 = (float *)cv.take(G.part_floats() * 4);
+    W.part8 = (float *)cv.take(cl_wgrad_part_floats(G.pw.M, 1, G.pw.Cout, G.pw.Cin) * 4);
+    for (float *&b : W.b) b = (float *)cv.take(G.E * 4);
+    W.sums = (float *)cv.take(4096);
+    W.lka_part_bytes = G.lka.part_bytes;
+    W.lka_part = cv.take(W.lka_part_bytes);
+    return W;
 }
 
 }  // namespace
@@ -65,20 +109,20 @@ size_t dlka_tblock3d_saved_bytes(int B, int C, int D, int H, int W, int dtype) {
 size_t dlka_tblock3d_saved_bytes_v(int B, int C, int D, int H, int W, int dtype, int variant)
 {
     if (!dlka_tblock3d_supported_v(B, C, D, H, W, dtype, variant)) return 0;
-    TBlockGeoms G(B, C, D, H, W);
-    return 8 * align256(G.E * 4) + align256(G.M * 2 * 4) + 4 * align256(dense_wp_floats(G.c3) * 4) + 2 * align256(dense_wp_floats(G.pw) * 4) +
-           align256(dlka_lka3d_tokens_saved_bytes_v(B, C, D, H, W, dtype, variant));
+    const TBlockGeoms G(B, C, D, H, W, dtype, variant);
+    return carved_bytes([&](Carver &m) { TBlockSaved S; carve_tblock_saved(m, G, S); });
 }
 
 int dlka_tblock3d_saved_offsets_v(int B, int C, int D, int H, int W, int dtype, int variant, size_t *byte_offset)
 {
     if (!byte_offset) return DLKA_ERR_NULL;
     if (!dlka_tblock3d_supported_v(B, C, D, H, W, dtype, variant)) return DLKA_ERR_UNSUPPORTED;
-    TBlockGeoms G(B, C, D, H, W);
-    size_t inner = 0;
-    DLKA_TRY(dlka_lka3d_tokens_saved_offsets_v(B, C, D, H, W, dtype, variant, &inner));
-    // carve_tblock_saved: eight activation tensors, the LayerNorm statistics, six prepared weight forms, then the D-LKA block's own `saved`
-    *byte_offset = 8 * align256(G.E * 4) + align256(G.M * 2 * 4) + 4 * align256(dense_wp_floats(G.c3) * 4) + 2 * align256(dense_wp_floats(G.pw) * 4) + inner;
+    const TBlockGeoms G(B, C, D, H, W, dtype, variant);
+    Carver sv = Carver::probing();
+    TBlockSaved S;
+    carve_tblock_saved(sv, G, S);
+    Carver lsv(S.lka, S.lka_bytes);
+    *byte_offset = sv.offset_of(carve_tok_saved(lsv, G.lka).off);
     return DLKA_OK;
 }
 
@@ -86,10 +130,11 @@ int dlka_tblock3d_saved_activations_v(int B, int C, int D, int H, int W, int dty
 {
     if (!byte_offsets) return DLKA_ERR_NULL;
     if (!dlka_tblock3d_supported_v(B, C, D, H, W, dtype, variant)) return DLKA_ERR_UNSUPPORTED;
-    TBlockGeoms G(B, C, D, H, W);
-    // carve_tblock_saved: xt, xn, e, attn, c1, a1, c2, rd
-    byte_offsets[0] = 5 * align256(G.E * 4);
-    byte_offsets[1] = 7 * align256(G.E * 4);
+    Carver sv = Carver::probing();
+    TBlockSaved S;
+    carve_tblock_saved(sv, TBlockGeoms(B, C, D, H, W, dtype, variant), S);
+    byte_offsets[0] = sv.offset_of(S.a1);
+    byte_offsets[1] = sv.offset_of(S.rd);
     return DLKA_OK;
 }
 
@@ -97,10 +142,10 @@ size_t dlka_tblock3d_workspace_bytes(int B, int C, int D, int H, int W, int dtyp
 size_t dlka_tblock3d_workspace_bytes_v(int B, int C, int D, int H, int W, int dtype, int variant)
 {
     if (!dlka_tblock3d_supported_v(B, C, D, H, W, dtype, variant)) return 0;
-    TBlockGeoms G(B, C, D, H, W);
-    return align256(dlka_lka3d_tokens_workspace_bytes_v(B, C, D, H, W, dtype, variant)) + align256(G.wp_floats() * 4) + 2 * align256(G.part_floats() * 4) +
-           align256(cl_wgrad_part_floats(G.pw.M, 1, G.pw.Cout, G.pw.Cin) * 4) + 6 * align256(G.E * 4) + align256(4096) +
-           align256(dlka_lka3d_tokens_partials_bytes_v(B, C, D, H, W, dtype, variant));   // (the phased backward's partial sums of the attention: dlka_tblock3d_backward_phase_v)
+    const TBlockGeoms G(B, C, D, H, W, dtype, variant);
+    const size_t f = carved_bytes([&](Carver &m) { carve_tblock_fwd_ws(m, G, true); });   // (xn32 at its capacity: the size does not depend on the mixed-mode switch)
+    const size_t b = carved_bytes([&](Carver &m) { carve_tblock_bwd_ws(m, G); });
+    return f > b ? f : b;
 }
 
 int dlka_tblock3d_forward(const void *x, int x_planar, const dlka_tblock3d_params *p, const dlka_lka3d_params *lka, const void *drop_mask, int training,
@@ -121,23 +166,20 @@ int dlka_tblock3d_forward_v(const void *x, int x_planar, const dlka_tblock3d_par
         return DLKA_ERR_NULL;
     if (!dlka_tblock3d_supported_v(B, C, D, H, W, dtype, variant)) return DLKA_ERR_UNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;
-    TBlockGeoms G(B, C, D, H, W);
+    const TBlockGeoms G(B, C, D, H, W, dtype, variant);
     Carver sv(saved, saved_bytes), cv(workspace, workspace_bytes);
     TBlockSaved S;
-    if (!carve_tblock_saved(sv, G, B, C, D, H, W, S, variant, dtype)) return DLKA_ERR_WORKSPACE;
-    const size_t lka_ws_bytes = dlka_lka3d_tokens_workspace_bytes_v(B, C, D, H, W, dtype, variant);
-    void *lka_ws = cv.take(lka_ws_bytes);
-    float *wp = (float *)cv.take(G.wp_floats() * 4);
-    float *sums = (float *)cv.take(4096);
+    if (!carve_tblock_saved(sv, G, S)) return DLKA_ERR_WORKSPACE;
     const int lo = dtype == DLKA_BF16 ? 1 : 0;   // the D-LKA attention runs DLKA_BF16: xn / e are bf16 storage
-    // mixed mode: LayerNorm's unrounded output, for the offset-determining chain of the attention (in the region the backward call uses for its six gradient buffers)
     static const bool xn32_on = [] { const char *e = getenv("DLKA_MIXED_XN32"); return !(e && e[0] == '0'); }();   // (A/B: 0 = the chain starts from the bf16 tensor, as in round 4)
-    float *xn32 = (lo && xn32_on) ? (float *)cv.take(G.E * 4) : nullptr;
+    const TBlockFwdWs Wf = carve_tblock_fwd_ws(cv, G, lo && xn32_on);
     if (!cv.ok()) return DLKA_ERR_WORKSPACE;
+    void *lka_ws = Wf.lka;
+    const size_t lka_ws_bytes = Wf.lka_bytes;
+    float *sums = Wf.sums, *xn32 = Wf.xn32;
     const long M = (long)G.M, N = G.c3.N;
     float *st1 = (float *)bn_stats, *st2 = st1 + 3 * C;
     const float slope = 0.01f;   // UnetResBlock's act_name default (dynunet_block.py:41)
-    (void)wp;
     // ONE launch prepares the wrapper's six weight forms (kept in `saved` for the backward call) and zero-fills what this direction accumulates
     // into with atomics (BatchNorm sums, tap-split conv outputs)
     {
@@ -158,15 +200,11 @@ int dlka_tblock3d_forward_v(const void *x, int x_planar, const dlka_tblock3d_par
         // in its first kernel, as they do behind the engine's hoisted preparation)
         const void *const *pp = (const void *const *)lka;
         for (size_t k = 0; k < sizeof(*lka) / sizeof(void *); ++k) if (!pp[k]) return DLKA_ERR_NULL;
-        TokGeoms TG(B, C, D, H, W, dtype, variant);
-        Carver lsv(S.lka, S.lka_bytes);   // (the layout tokens_forward_impl carves: h, a, t1, t, offsets, f, g1, then the prepared weights)
-        for (int e = 0; e < 4; ++e) (void)lsv.take(TG.E * TG.SB);
-        (void)lsv.take(TG.Off * 4);
-        (void)lsv.take(TG.E * TG.SB); (void)lsv.take(TG.E * TG.SB);
-        float *lprep = (float *)lsv.take(TG.prep_floats() * 4);
+        Carver lsv(S.lka, S.lka_bytes);
+        const TokSaved LS = carve_tok_saved(lsv, G.lka);
         if (!lsv.ok()) return DLKA_ERR_WORKSPACE;
         TokPrep PWl;
-        DLKA_TRY(carve_prep(TG, lprep, PWl, lka, st, true, nullptr, &pb, true));
+        DLKA_TRY(carve_prep(G.lka, LS.prep, PWl, lka, st, true, nullptr, &pb, true));
         DLKA_TRY(launch_cl_prep_batch(pb, st));
     }
     // tokens (+ pos_embed) and LayerNorm (:620-624)
@@ -225,21 +263,16 @@ int dlka_tblock3d_backward_phase_v(const dlka_tblock3d_params *p, const dlka_lka
     if ((p->pos_embed != nullptr) != (gr->pos_embed != nullptr)) return DLKA_ERR_NULL;
     if (!dlka_tblock3d_supported_v(B, C, D, H, W, dtype, variant)) return DLKA_ERR_UNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;
-    TBlockGeoms G(B, C, D, H, W);
-    Carver sv((void *)saved, saved_bytes), cv(workspace, workspace_bytes);
+    const TBlockGeoms G(B, C, D, H, W, dtype, variant);
+    Carver sv(saved, saved_bytes), cv(workspace, workspace_bytes);
     TBlockSaved S;
-    if (!carve_tblock_saved(sv, G, B, C, D, H, W, S, variant, dtype)) return DLKA_ERR_WORKSPACE;
-    const size_t lka_ws_bytes = dlka_lka3d_tokens_workspace_bytes_v(B, C, D, H, W, dtype, variant);
-    void *lka_ws = cv.take(lka_ws_bytes);
-    (void)cv.take(G.wp_floats() * 4);   // (layout kept: the forward call carves the same region)
-    float *part1 = (float *)cv.take(G.part_floats() * 4), *part2 = (float *)cv.take(G.part_floats() * 4);
-    float *part8 = (float *)cv.take(cl_wgrad_part_floats(G.pw.M, 1, G.pw.Cout, G.pw.Cin) * 4);
-    float *b0 = (float *)cv.take(G.E * 4), *b1 = (float *)cv.take(G.E * 4), *b2 = (float *)cv.take(G.E * 4), *b3 = (float *)cv.take(G.E * 4);
-    float *b4 = (float *)cv.take(G.E * 4), *b5 = (float *)cv.take(G.E * 4);
-    float *sums = (float *)cv.take(4096);
-    const size_t lka_part_bytes = dlka_lka3d_tokens_partials_bytes_v(B, C, D, H, W, dtype, variant);
-    void *lka_part = cv.take(lka_part_bytes);   // the attention's partial sums when the pass is split (phase 1 / 2): outside its own workspace
+    if (!carve_tblock_saved(sv, G, S)) return DLKA_ERR_WORKSPACE;
+    const TBlockBwdWs Wb = carve_tblock_bwd_ws(cv, G);
     if (!cv.ok()) return DLKA_ERR_WORKSPACE;
+    void *lka_ws = Wb.lka, *lka_part = Wb.lka_part;
+    const size_t lka_ws_bytes = Wb.lka_bytes, lka_part_bytes = Wb.lka_part_bytes;
+    float *part1 = Wb.part1, *part2 = Wb.part2, *part8 = Wb.part8, *sums = Wb.sums;
+    float *b0 = Wb.b[0], *b1 = Wb.b[1], *b2 = Wb.b[2], *b3 = Wb.b[3], *b4 = Wb.b[4], *b5 = Wb.b[5];
     const long M = (long)G.M, N = G.c3.N;
     const float *st1 = (const float *)bn_stats, *st2 = st1 + 3 * C;
     const float *gy = (const float *)grad_y, *mask = (const float *)drop_mask;

@@ -2,6 +2,7 @@
 // geometry record of a stride-1 same-size convolution, and the per-operator drivers (cl_host_ops.hip) the block drivers and the C entry points call.
 // Process-wide state (cached switches) lives in cl_host_ops.hip alone and is reached through the functions declared here.
 #pragma once
+#include <stdint.h>
 #include <stdlib.h>
 
 #include "cl_args.h"
@@ -11,15 +12,24 @@ namespace dlka {
 
 inline size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
 
+// Bump carver over a caller-provided buffer.  A buffer's layout is ONE function that carves a record of named pointers from a Carver; the forward call, the
+// backward call and the size / offset queries all run that function:
+//   Carver(p, n)          the real buffer: take() fails (ok() turns false) when the layout does not fit
+//   Carver::measuring()   no buffer, unlimited capacity: hands out no pointers and only advances `used` — the layout's size is `used` after its carve
+//   Carver::probing()     a dummy non-null base, unlimited capacity: pointers that must never be dereferenced — offset_of(field) is a field's position
 struct Carver {
-    unsigned char *base;
+    uintptr_t base;
     size_t cap, used;
-    Carver(void *p, size_t n) : base((unsigned char *)p), cap(n), used(0) {}
+    bool measure;
+    Carver(const void *p, size_t n) : base((uintptr_t)p), cap(n), used(0), measure(false) {}
+    static Carver measuring() { Carver c(nullptr, ~(size_t)0); c.measure = true; return c; }
+    static Carver probing() { return Carver((const void *)(uintptr_t)256, ~(size_t)0 >> 1); }
     void *take(size_t n)
     {
         n = align256(n);
+        if (measure) { used += n; return nullptr; }
         if (!base || used + n > cap) { used = cap + 1; return nullptr; }
-        void *r = base + used;
+        void *r = (void *)(base + used);
         used += n;
         return r;
     }
@@ -27,13 +37,33 @@ struct Carver {
     void *take_opt(size_t n, bool want)
     {
         n = align256(n);
-        if (!want || !base || used > cap || used + n > cap) return nullptr;
-        void *r = base + used;
+        if (!want) return nullptr;
+        if (measure) { used += n; return nullptr; }
+        if (!base || used > cap || used + n > cap) return nullptr;
+        void *r = (void *)(base + used);
         used += n;
         return r;
     }
+    // whether the optional area whose take_opt() returned `p` was carved (a measuring carver counts every wanted area)
+    bool got(const void *p) const { return measure || p != nullptr; }
+    // the next take() starts at byte `n` or later
+    void skip_to(size_t n)
+    {
+        if (!measure && n > cap) used = cap + 1;
+        else if (n > used) used = n;
+    }
+    size_t offset_of(const void *field) const { return (size_t)((uintptr_t)field - base); }
     bool ok() const { return used <= cap; }
 };
+
+// size of a layout: where a measuring carver stands after `carve` ran on it
+template <typename Carve>
+size_t carved_bytes(Carve carve)
+{
+    Carver m = Carver::measuring();
+    carve(m);
+    return m.used;
+}
 
 #define DLKA_TRY(expr)                  \
     do {                                \

@@ -3,7 +3,7 @@
 // launch sequences.  No allocation, no synchronisation: every function is legal inside hipGraph capture.
 #include <algorithm>
 
-#include "dlka_kernels.h"
+#include "cl_host.h"
 
 using namespace dlka;
 
@@ -47,30 +47,7 @@ int make_geom(const dlka_conv_geom *c, bool deform, Geom &g)
     return DLKA_OK;
 }
 
-inline size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
 inline size_t esz(int dtype) { return dtype == DLKA_BF16 ? 2 : 4; }
-
-// simple bump carver over a caller-provided workspace
-struct Carver {
-    unsigned char *base;
-    size_t cap, used;
-    Carver(void *p, size_t n) : base((unsigned char *)p), cap(n), used(0) {}
-    void *take(size_t n)
-    {
-        n = align256(n);
-        if (!base || used + n > cap) { used = cap + 1; return nullptr; }
-        void *r = base + used;
-        used += n;
-        return r;
-    }
-    bool ok() const { return used <= cap; }
-};
-
-#define DLKA_TRY(expr)            \
-    do {                          \
-        int rc_ = (expr);         \
-        if (rc_ != DLKA_OK) return rc_; \
-    } while (0)
 
 // ---------------------------------------------------------------------------------------------
 // typed implementations
@@ -222,18 +199,60 @@ struct Lka3dGeoms {
     }
 };
 
+// ---- buffer layouts of the planar blocks (3-D and 2-D; GEOMS = Lka3dGeoms / Lka2dGeoms): one record and ONE carve function per buffer and direction ----
+// `saved`: seven tensors of the block's dtype (the 2-D block's: PlanarSaved2d, behind Lka2dGeoms)
+template <typename T> struct PlanarSaved { T *h, *a, *t1, *t, *off, *f, *g1; };
+template <typename T>
+PlanarSaved<T> carve_lka3d_saved(Carver &sv, const Lka3dGeoms &G)
+{
+    const size_t e = sizeof(T);
+    PlanarSaved<T> S;
+    S.h = (T *)sv.take(G.E * e); S.a = (T *)sv.take(G.E * e); S.t1 = (T *)sv.take(G.E * e); S.t = (T *)sv.take(G.E * e);
+    S.off = (T *)sv.take(G.Off * e); S.f = (T *)sv.take(G.E * e); S.g1 = (T *)sv.take(G.E * e);
+    return S;
+}
+// `workspace`, forward and backward call.  goff_elems: the (larger) offset tensor's size — bO holds grad_offset of one deformable conv at a time
+template <typename T> struct PlanarFwdWs { float *wt; T *m; };
+template <typename T> struct PlanarBwdWs { float *scr; T *bA, *bB, *bC, *bD, *bO; float *gw32, *gx32; };   // gw32, gx32: fp32 accumulators of the bf16 path
+template <typename T, typename GEOMS>
+PlanarFwdWs<T> carve_planar_fwd_ws(Carver &cv, const GEOMS &G)
+{
+    PlanarFwdWs<T> W;
+    W.wt = (float *)cv.take(G.scratch_floats() * 4);
+    W.m = (T *)cv.take(G.E * sizeof(T));
+    return W;
+}
+template <typename T, typename GEOMS>
+PlanarBwdWs<T> carve_planar_bwd_ws(Carver &cv, const GEOMS &G, size_t goff_elems, int dtype)
+{
+    const size_t e = sizeof(T);
+    PlanarBwdWs<T> W;
+    W.scr = (float *)cv.take(G.scratch_floats() * 4);
+    W.bA = (T *)cv.take(G.E * e); W.bB = (T *)cv.take(G.E * e); W.bC = (T *)cv.take(G.E * e); W.bD = (T *)cv.take(G.E * e);
+    W.bO = (T *)cv.take(goff_elems * e);
+    W.gw32 = dtype != DLKA_F32 ? (float *)cv.take(G.max_weight_elems() * 4) : nullptr;
+    W.gx32 = dtype != DLKA_F32 ? (float *)cv.take(G.E * 4) : nullptr;
+    return W;
+}
+template <typename T, typename GEOMS>
+size_t planar_workspace_bytes(const GEOMS &G, size_t goff_elems, int dtype)
+{
+    const size_t f = carved_bytes([&](Carver &m) { carve_planar_fwd_ws<T>(m, G); });
+    const size_t b = carved_bytes([&](Carver &m) { carve_planar_bwd_ws<T>(m, G, goff_elems, dtype); });
+    return f > b ? f : b;
+}
+
 template <typename T>
 int lka3d_forward_t(const void *x, const dlka_lka3d_params *p, void *y, void *saved, size_t savedb, void *ws, size_t wsb,
                     int B, int C, int D, int H, int W, hipStream_t st)
 {
     Lka3dGeoms G(B, C, D, H, W);
-    const size_t e = sizeof(T);
     Carver sv(saved, savedb), cv(ws, wsb);
-    T *h = (T *)sv.take(G.E * e), *a = (T *)sv.take(G.E * e), *t1 = (T *)sv.take(G.E * e), *t = (T *)sv.take(G.E * e);
-    T *off = (T *)sv.take(G.Off * e), *f = (T *)sv.take(G.E * e), *g1 = (T *)sv.take(G.E * e);
-    float *wt = (float *)cv.take(G.scratch_floats() * 4);
-    T *m = (T *)cv.take(G.E * e);
+    const PlanarSaved<T> S = carve_lka3d_saved<T>(sv, G);
+    const PlanarFwdWs<T> Wf = carve_planar_fwd_ws<T>(cv, G);
     if (!sv.ok() || !cv.ok()) return DLKA_ERR_WORKSPACE;
+    T *h = S.h, *a = S.a, *t1 = S.t1, *t = S.t, *off = S.off, *f = S.f, *g1 = S.g1, *m = Wf.m;
+    float *wt = Wf.wt;
     DLKA_TRY(launch_conv_fwd<T>((const T *)x, (const T *)p->proj_1_w, (const T *)p->proj_1_b, h, wt, G.pw, st));          // :667
     DLKA_TRY(launch_gelu_fwd<T>(h, a, G.E, st));                                                                          // :668
     DLKA_TRY(launch_conv_fwd<T>(a, (const T *)p->conv0_w, (const T *)p->conv0_b, t1, wt, G.dw5, st));                     // :646
@@ -268,19 +287,13 @@ int lka3d_backward_t(const void *x_, const dlka_lka3d_params *p, const void *gy_
                      const dlka_lka3d_grads *gr, void *ws, size_t wsb, int B, int C, int D, int H, int W, int dtype, hipStream_t st)
 {
     Lka3dGeoms G(B, C, D, H, W);
-    const size_t e = sizeof(T);
-    Carver sv((void *)saved, savedb), cv(ws, wsb);
-    const T *h = (T *)sv.take(G.E * e), *a = (T *)sv.take(G.E * e), *t1 = (T *)sv.take(G.E * e), *t = (T *)sv.take(G.E * e);
-    const T *off = (T *)sv.take(G.Off * e), *f = (T *)sv.take(G.E * e), *g1 = (T *)sv.take(G.E * e);
-    float *scr = (float *)cv.take(G.scratch_floats() * 4);
-    T *bA = (T *)cv.take(G.E * e), *bB = (T *)cv.take(G.E * e), *bC = (T *)cv.take(G.E * e), *bD = (T *)cv.take(G.E * e);
-    T *bO = (T *)cv.take(G.Off * e);
-    float *gw32 = nullptr, *gx32 = nullptr;
-    if (dtype != DLKA_F32) {
-        gw32 = (float *)cv.take(G.max_weight_elems() * 4);
-        gx32 = (float *)cv.take(G.E * 4);
-    }
+    Carver sv(saved, savedb), cv(ws, wsb);
+    const PlanarSaved<T> S = carve_lka3d_saved<T>(sv, G);
+    const PlanarBwdWs<T> Wb = carve_planar_bwd_ws<T>(cv, G, G.Off, dtype);
     if (!sv.ok() || !cv.ok()) return DLKA_ERR_WORKSPACE;
+    const T *h = S.h, *a = S.a, *t1 = S.t1, *t = S.t, *off = S.off, *f = S.f, *g1 = S.g1;
+    T *bA = Wb.bA, *bB = Wb.bB, *bC = Wb.bC, *bD = Wb.bD, *bO = Wb.bO;
+    float *scr = Wb.scr, *gw32 = Wb.gw32, *gx32 = Wb.gx32;
     const T *x = (const T *)x_, *gy = (const T *)gy_;
     T *gx = (T *)gx_;
 
@@ -361,18 +374,27 @@ struct Lka2dGeoms {
     }
 };
 
+template <typename T> struct PlanarSaved2d { T *h, *a, *o5, *t1, *o7, *t2, *g1; };
+template <typename T>
+PlanarSaved2d<T> carve_lka2d_saved(Carver &sv, const Lka2dGeoms &G)
+{
+    const size_t e = sizeof(T);
+    PlanarSaved2d<T> S;
+    S.h = (T *)sv.take(G.E * e); S.a = (T *)sv.take(G.E * e); S.o5 = (T *)sv.take(G.Off5 * e); S.t1 = (T *)sv.take(G.E * e);
+    S.o7 = (T *)sv.take(G.Off7 * e); S.t2 = (T *)sv.take(G.E * e); S.g1 = (T *)sv.take(G.E * e);
+    return S;
+}
 template <typename T>
 int lka2d_forward_t(const void *x, const dlka_lka2d_params *p, void *y, void *saved, size_t savedb, void *ws, size_t wsb,
                     int B, int C, int H, int W, hipStream_t st)
 {
     Lka2dGeoms G(B, C, H, W);
-    const size_t e = sizeof(T);
     Carver sv(saved, savedb), cv(ws, wsb);
-    T *h = (T *)sv.take(G.E * e), *a = (T *)sv.take(G.E * e), *o5 = (T *)sv.take(G.Off5 * e), *t1 = (T *)sv.take(G.E * e);
-    T *o7 = (T *)sv.take(G.Off7 * e), *t2 = (T *)sv.take(G.E * e), *g1 = (T *)sv.take(G.E * e);
-    float *wt = (float *)cv.take(G.scratch_floats() * 4);
-    T *m = (T *)cv.take(G.E * e);
+    const PlanarSaved2d<T> S = carve_lka2d_saved<T>(sv, G);
+    const PlanarFwdWs<T> Wf = carve_planar_fwd_ws<T>(cv, G);
     if (!sv.ok() || !cv.ok()) return DLKA_ERR_WORKSPACE;
+    T *h = S.h, *a = S.a, *o5 = S.o5, *t1 = S.t1, *o7 = S.o7, *t2 = S.t2, *g1 = S.g1, *m = Wf.m;
+    float *wt = Wf.wt;
     DLKA_TRY(launch_conv_fwd<T>((const T *)x, (const T *)p->proj_1_w, (const T *)p->proj_1_b, h, wt, G.pw, st));                     // :135
     DLKA_TRY(launch_gelu_fwd<T>(h, a, G.E, st));                                                                                     // :136
     DLKA_TRY(launch_conv_fwd<T>(a, (const T *)p->conv0_offset_w, (const T *)p->conv0_offset_b, o5, wt, G.off5, st));                 // :28
@@ -411,19 +433,13 @@ int lka2d_backward_t(const void *x_, const dlka_lka2d_params *p, const void *gy_
                      const dlka_lka2d_grads *gr, void *ws, size_t wsb, int B, int C, int H, int W, int dtype, hipStream_t st)
 {
     Lka2dGeoms G(B, C, H, W);
-    const size_t e = sizeof(T);
-    Carver sv((void *)saved, savedb), cv(ws, wsb);
-    const T *h = (T *)sv.take(G.E * e), *a = (T *)sv.take(G.E * e), *o5 = (T *)sv.take(G.Off5 * e), *t1 = (T *)sv.take(G.E * e);
-    const T *o7 = (T *)sv.take(G.Off7 * e), *t2 = (T *)sv.take(G.E * e), *g1 = (T *)sv.take(G.E * e);
-    float *scr = (float *)cv.take(G.scratch_floats() * 4);
-    T *bA = (T *)cv.take(G.E * e), *bB = (T *)cv.take(G.E * e), *bC = (T *)cv.take(G.E * e), *bD = (T *)cv.take(G.E * e);
-    T *bO = (T *)cv.take(G.Off7 * e);
-    float *gw32 = nullptr, *gx32 = nullptr;
-    if (dtype != DLKA_F32) {
-        gw32 = (float *)cv.take(G.max_weight_elems() * 4);
-        gx32 = (float *)cv.take(G.E * 4);
-    }
+    Carver sv(saved, savedb), cv(ws, wsb);
+    const PlanarSaved2d<T> S = carve_lka2d_saved<T>(sv, G);
+    const PlanarBwdWs<T> Wb = carve_planar_bwd_ws<T>(cv, G, G.Off7, dtype);
     if (!sv.ok() || !cv.ok()) return DLKA_ERR_WORKSPACE;
+    const T *h = S.h, *a = S.a, *o5 = S.o5, *t1 = S.t1, *o7 = S.o7, *t2 = S.t2, *g1 = S.g1;
+    T *bA = Wb.bA, *bB = Wb.bB, *bC = Wb.bC, *bD = Wb.bD, *bO = Wb.bO;
+    float *scr = Wb.scr, *gw32 = Wb.gw32, *gx32 = Wb.gx32;
     const T *x = (const T *)x_, *gy = (const T *)gy_;
     T *gx = (T *)gx_;
     DLKA_TRY(launch_mul_fwd<T>(a, g1, bA, G.E, st));                                                                        // m
@@ -695,16 +711,14 @@ size_t dlka_lka3d_saved_bytes(int B, int C, int D, int H, int W, int dtype)
 {
     if (check_block(B, C, D, H, W)) return 0;
     Lka3dGeoms G(B, C, D, H, W);
-    return 6 * align256(G.E * esz(dtype)) + align256(G.Off * esz(dtype));
+    return carved_bytes([&](Carver &m) { esz(dtype) == 2 ? (void)carve_lka3d_saved<bf16_t>(m, G) : (void)carve_lka3d_saved<float>(m, G); });
 }
 
 size_t dlka_lka3d_workspace_bytes(int B, int C, int D, int H, int W, int dtype)
 {
     if (check_block(B, C, D, H, W)) return 0;
     Lka3dGeoms G(B, C, D, H, W);
-    size_t n = align256(G.scratch_floats() * 4) + 4 * align256(G.E * esz(dtype)) + align256(G.Off * esz(dtype));
-    if (dtype != DLKA_F32) n += align256(G.max_weight_elems() * 4) + align256(G.E * 4);
-    return n;
+    return esz(dtype) == 2 ? planar_workspace_bytes<bf16_t>(G, G.Off, dtype) : planar_workspace_bytes<float>(G, G.Off, dtype);
 }
 
 int dlka_lka3d_attention_forward(const void *x, const dlka_lka3d_params *p, void *y, void *saved, size_t saved_bytes,
@@ -756,7 +770,7 @@ size_t dlka_lka2d_saved_bytes(int B, int C, int H, int W, int dtype)
 {
     if (check_block(B, C, 1, H, W)) return 0;
     Lka2dGeoms G(B, C, H, W);
-    size_t n = 5 * align256(G.E * esz(dtype)) + align256(G.Off5 * esz(dtype)) + align256(G.Off7 * esz(dtype));
+    size_t n = carved_bytes([&](Carver &m) { esz(dtype) == 2 ? (void)carve_lka2d_saved<bf16_t>(m, G) : (void)carve_lka2d_saved<float>(m, G); });
     if (lka2d_cl_supported(B, C, H, W, dtype)) n = std::max(n, lka2d_cl_saved_bytes(B, C, H, W, dtype));   // channels-last fast path (capi_lka2d_cl.hip)
     return n;
 }
@@ -765,8 +779,7 @@ size_t dlka_lka2d_workspace_bytes(int B, int C, int H, int W, int dtype)
 {
     if (check_block(B, C, 1, H, W)) return 0;
     Lka2dGeoms G(B, C, H, W);
-    size_t n = align256(G.scratch_floats() * 4) + 4 * align256(G.E * esz(dtype)) + align256(G.Off7 * esz(dtype));
-    if (dtype != DLKA_F32) n += align256(G.max_weight_elems() * 4) + align256(G.E * 4);
+    size_t n = esz(dtype) == 2 ? planar_workspace_bytes<bf16_t>(G, G.Off7, dtype) : planar_workspace_bytes<float>(G, G.Off7, dtype);
     if (lka2d_cl_supported(B, C, H, W, dtype)) n = std::max(n, lka2d_cl_workspace_bytes(B, C, H, W, dtype));
     return n;
 }
@@ -794,12 +807,11 @@ int dlka_lka2d_saved_offsets(int B, int C, int H, int W, int dtype, size_t byte_
     if (lka2d_cl_supported(B, C, H, W, dtype) && !lka2d_general())
         return lka2d_cl_saved_offsets(B, C, H, W, dtype, byte_offsets, elem_bytes);
     if (dtype == DLKA_BF16) return DLKA_ERR_UNSUPPORTED;
-    // lka2d_forward_t: h, a, o5, t1, o7, ...
-    Lka2dGeoms G(B, C, H, W);
-    const size_t e = esz(dtype);
-    byte_offsets[0] = 2 * align256(G.E * e);
-    byte_offsets[1] = 3 * align256(G.E * e) + align256(G.Off5 * e);
-    *elem_bytes = (int)e;
+    Carver sv = Carver::probing();
+    const PlanarSaved2d<float> S = carve_lka2d_saved<float>(sv, Lka2dGeoms(B, C, H, W));   // (fp32 and, as fp32, float64: bf16 took the branch above)
+    byte_offsets[0] = sv.offset_of(S.o5);
+    byte_offsets[1] = sv.offset_of(S.o7);
+    *elem_bytes = (int)esz(dtype);
     return DLKA_OK;
 }
 

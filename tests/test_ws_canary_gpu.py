@@ -107,3 +107,18 @@ def test_wrapper_block_2d_block_and_operators_stay_inside_their_buffers(guarded)
         go = torch.randn((2, cout, 10, 9, 12) if planar else (2, 10, 9, 12, cout), device=DEV)   # (the offset conv's grad_out arrives planar, as in the block)
         ops.conv3d_backward_cl(xc, wc, go, p, d, g, grad_out_planar=planar)
         guarded.verify(f"conv3d_cl {cin}->{cout} k{k}")
+
+
+def test_acdc_wrapper_block_with_wgrad_overlap_stays_inside_its_buffers(guarded):
+    """The ACDC variant's depthwise pairs (other kernels, other workspace terms) and the phased backward pass: the data chain on the current stream, the
+    weight gradients on the side stream from the same workspace, the attention's partial sums in the area behind the wrapper's own."""
+    from deformablelka_amd import acdc
+    torch.manual_seed(0)
+    for C, dims in [(32, (5, 6, 7)), (256, (4, 4, 4))]:
+        H, W, D = dims
+        m = acdc.TransformerBlock_3D_single_deform_LKA(H * W * D, C, C, 4, dropout_rate=0.1, pos_embed=True).to(DEV).train()
+        m.wgrad_overlap = True
+        x = torch.randn(2, C, H, W, D, device=DEV, requires_grad=True)
+        m(x).sum().backward()   # (the side stream is joined when backward() returns)
+        assert guarded.verify(f"acdc tblock, wgrad_overlap, C={C} {dims}") >= 2
+        assert all(bool(torch.isfinite(p.grad).all()) for p in m.parameters() if p.grad is not None) and bool(torch.isfinite(x.grad).all())
