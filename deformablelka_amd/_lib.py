@@ -273,6 +273,8 @@ SIGNATURES = {
     "dlka_spline_prefilter": (c_int, [c_void_p, POINTER(c_int64), c_int, c_int, c_void_p]),
     "dlka_augment_spatial": (c_int, [c_void_p, c_void_p, c_void_p, _AGD, c_void_p, c_void_p, c_void_p]),
     "dlka_augment_spatial_labels": (c_int, [c_void_p, c_void_p, _AGD, c_void_p, c_void_p, c_void_p]),
+    "dlka_augment_spatial2d": (c_int, [c_void_p, c_void_p, c_void_p, _AGD, c_void_p, c_void_p, c_void_p]),
+    "dlka_augment_spatial2d_labels": (c_int, [c_void_p, c_void_p, _AGD, c_void_p, c_void_p, c_void_p]),
     "dlka_augment_gaussian": (c_int, [c_void_p, c_void_p, c_int, c_int64, POINTER(c_int64), c_int, c_void_p, c_void_p, c_void_p]),
     "dlka_augment_stats_workspace_bytes": (c_size_t, [c_int64, c_int64]),
     "dlka_augment_channel_stats": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int64, c_int64, c_void_p]),

@@ -1,4 +1,4 @@
-"""The 3-D trainer's train-time augmentation on the HIP kernels of ``csrc/cl_augment.hip`` (include/dlka.h: ``dlka_augment_*``): what
+"""The 3-D trainers' train-time augmentation on the HIP kernels of ``csrc/cl_augment.hip`` (include/dlka.h: ``dlka_augment_*``): what
 ``get_moreDA_augmentation`` (3D/d_lka_former/training/data_augmentation/data_augmentation_moreDA.py:60-147) composes from batchgenerators'
 transforms and the reference runs on scipy in four worker processes (d_lka_former_trainer_synapse.py:114).
 
@@ -7,11 +7,14 @@ Every transform is split in two.  ``draw_*`` runs on the host, takes a ``numpy.r
 (``params=``; without one it draws with ``rs``).  The rules are batchgenerators 0.21's, restated in DESIGN.md 4.18.
 
   ``draw_spatial`` / ``augment_spatial``      SpatialTransform: rotation, scaling, centre or random crop; orders 0 / 1 / 3 for the image,
-                                              0 / 1 for the label map, border modes 'constant' and 'nearest'; no elastic deformation
+                                              0 / 1 for the label map, border modes 'constant' and 'nearest'; no elastic deformation.
+                                              Rank-4 arrays (B, P, H, W) with a 2-entry patch_size are batchgenerators' dim == 2 form: one
+                                              in-plane rotation, scale and crop per sample for all of its planes
   ``augment_gaussian_noise``, ``augment_gaussian_blur``, ``augment_brightness_multiplicative``, ``augment_brightness_additive``,
   ``augment_contrast``, ``augment_linear_downsampling_scipy``, ``augment_gamma``, ``augment_mirroring``   the colour and mirror transforms
   ``downsample_seg_for_ds_transform2``        training/data_augmentation/downsampling.py:88, on ``resampling``'s label path
-  ``MoreDAAugmentation``                      the chain of data_augmentation_moreDA.py:60-147
+  ``MoreDAAugmentation``                      the chain of data_augmentation_moreDA.py:60-147, and with ``dummy_2D`` its :54-75 / :91-94 form
+                                              (the ACDC trainer's anisotropic patch): the spatial step on the planes, the rest in 3-D
 
 Unlike the package's per-sample functions these take the batch: ``data`` (B, C, D, H, W), ``seg`` (B, Cs, D, H, W), numpy arrays or tensors on
 either side (host data is moved to the device).  The inputs are not written to; results are device tensors in the input's dtype.  Without a
@@ -41,11 +44,11 @@ def launch_count() -> int:
 
 
 # ---- containers ------------------------------------------------------------------------------------------------------------------------------
-def _device(x, what):
+def _device(x, what, ndim=(5,)):
     """A detached tensor on the working device; never the caller's own storage when it is going to be returned."""
     t = to_working_device(x, "augmentation", what)
-    if t.ndim != 5:
-        raise RuntimeError(f"augmentation: {what} is (b, c, x, y, z), got {tuple(t.shape)}")
+    if t.ndim not in ndim:
+        raise RuntimeError(f"augmentation: {what} is (b, c, x, y, z)" + (" or (b, planes, y, z)" if 4 in ndim else "") + f", got {tuple(t.shape)}")
     return t
 
 
@@ -81,6 +84,10 @@ def _steps(B, C):
 
 
 # ---- SpatialTransform ------------------------------------------------------------------------------------------------------------------------
+def _rotation_2d(a):
+    return np.array([[np.cos(a), -np.sin(a)], [np.sin(a), np.cos(a)]])
+
+
 def _rotation(ax, ay, az):
     def rx(a):
         return np.array([[1, 0, 0], [0, np.cos(a), -np.sin(a)], [0, np.sin(a), np.cos(a)]])
@@ -99,52 +106,59 @@ def draw_spatial(rs, src_shape, patch_size, batch, patch_center_dist_from_border
                  p_scale_per_sample=1, p_rot_per_sample=1, independent_scale_for_each_axis=False, p_rot_per_axis=1,
                  p_independent_scale_per_axis=1, **_apply_only):
     """Per sample: ``modified`` (bool), ``angles`` (3), ``rotation`` (3, 3; coords <- (coords^T . rotation)^T), ``scale`` (3), ``center`` (3; where
-    the patch centre lands in the source when the sample is modified) and ``crop_lb`` (3; the box when it is not)."""
+    the patch centre lands in the source when the sample is modified) and ``crop_lb`` (3; the box when it is not).  With two spatial axes
+    (batchgenerators' dim == 2): one angle (``angle_x``) and trailing extents of 2, ``angles`` (1), ``rotation`` (2, 2)."""
     if do_elastic_deform:
         raise NotImplementedError("augmentation: do_elastic_deform=True (the 3-D trainer sets do_elastic = False)")
     src_shape, patch_size = tuple(int(v) for v in src_shape), tuple(int(v) for v in patch_size)
-    if len(src_shape) != 3 or len(patch_size) != 3:
-        raise NotImplementedError("augmentation: patch_size and the source have three spatial axes (the 2-D chain is not part of this module)")
+    if len(src_shape) != len(patch_size):
+        raise ValueError(f"augmentation: patch_size {patch_size} and the source {src_shape} differ in rank")
+    dim = len(patch_size)
+    if dim not in (2, 3):
+        raise NotImplementedError(f"augmentation: patch_size and the source have two or three spatial axes, got {dim}")
     if any(p > s for p, s in zip(patch_size, src_shape)):
         raise ValueError(f"augmentation: patch_size {patch_size} is larger than the source {src_shape}")
     dist = patch_center_dist_from_border
-    dist = [dist] * 3 if not isinstance(dist, (list, tuple, np.ndarray)) else list(dist)
-    rec = {"modified": np.zeros(batch, bool), "angles": np.zeros((batch, 3)), "rotation": np.tile(np.identity(3), (batch, 1, 1)),
-           "scale": np.ones((batch, 3)), "center": np.zeros((batch, 3)), "crop_lb": np.zeros((batch, 3), np.int64)}
+    dist = [dist] * dim if not isinstance(dist, (list, tuple, np.ndarray)) else list(dist)
+    rec = {"modified": np.zeros(batch, bool), "angles": np.zeros((batch, 3 if dim == 3 else 1)),
+           "rotation": np.tile(np.identity(dim), (batch, 1, 1)), "scale": np.ones((batch, dim)), "center": np.zeros((batch, dim)),
+           "crop_lb": np.zeros((batch, dim), np.int64)}
     for b in range(batch):
         if do_rotation and rs.uniform() < p_rot_per_sample:
-            a = [rs.uniform(r[0], r[1]) if rs.uniform() <= p_rot_per_axis else 0.0 for r in (angle_x, angle_y, angle_z)]
-            rec["angles"][b], rec["rotation"][b], rec["modified"][b] = a, _rotation(*a), True
+            a = [rs.uniform(r[0], r[1]) if rs.uniform() <= p_rot_per_axis else 0.0 for r in (angle_x, angle_y, angle_z)[:len(rec["angles"][b])]]
+            rec["angles"][b], rec["rotation"][b], rec["modified"][b] = a, _rotation(*a) if dim == 3 else _rotation_2d(*a), True
         if do_scale and rs.uniform() < p_scale_per_sample:
             if independent_scale_for_each_axis and rs.uniform() < p_independent_scale_per_axis:
-                rec["scale"][b] = [_range_factor(rs, scale[0], scale[1]) for _ in range(3)]
+                rec["scale"][b] = [_range_factor(rs, scale[0], scale[1]) for _ in range(dim)]
             else:
                 rec["scale"][b] = _range_factor(rs, scale[0], scale[1])
             rec["modified"][b] = True
         if rec["modified"][b]:
-            for d in range(3):
+            for d in range(dim):
                 rec["center"][b, d] = rs.uniform(dist[d], src_shape[d] - dist[d]) if random_crop else src_shape[d] / 2. - 0.5
         else:
-            for d in range(3):
+            for d in range(dim):
                 margin = int(dist[d]) - patch_size[d] // 2 if random_crop else 0
                 lo, hi = margin, src_shape[d] - patch_size[d] - margin
                 rec["crop_lb"][b, d] = rs.randint(lo, hi + 1) if random_crop and hi > lo >= 0 else (src_shape[d] - patch_size[d]) // 2
     return rec
 
 
-def _spatial_tables(params, B):
+def _spatial_tables(params, B, dim=3):
     mod = np.asarray(params["modified"]).astype(bool).reshape(-1)
-    rot = np.asarray(params["rotation"], dtype=np.float64).reshape(-1, 3, 3)
-    sc = np.asarray(params["scale"], dtype=np.float64).reshape(-1, 3)
-    ctr = np.asarray(params["center"], dtype=np.float64).reshape(-1, 3)
-    lb = np.asarray(params["crop_lb"]).astype(np.int64).reshape(-1, 3)
+    if np.asarray(params["rotation"]).size != len(mod) * dim * dim:
+        raise ValueError(f"augmentation: the spatial record is not one of {dim} spatial axes (rotation {np.asarray(params['rotation']).shape})")
+    rot = np.asarray(params["rotation"], dtype=np.float64).reshape(-1, dim, dim)
+    sc = np.asarray(params["scale"], dtype=np.float64).reshape(-1, dim)
+    ctr = np.asarray(params["center"], dtype=np.float64).reshape(-1, dim)
+    lb = np.asarray(params["crop_lb"]).astype(np.int64).reshape(-1, dim)
     if not (len(mod) == len(rot) == len(sc) == len(ctr) == len(lb) == B):
         raise ValueError(f"augmentation: the spatial record is for {len(mod)} samples, the batch has {B}")
-    maps, plain = np.zeros((B, 3, 4)), np.zeros((B, 4), np.int32)
+    maps, plain = np.zeros((B, dim, dim + 1)), np.zeros((B, dim + 1), np.int32)
     for b in range(B):
         if mod[b]:
-            maps[b, :, :3] = rot[b].T * sc[b][:, None]         # source axis d = sum_e g[e] rotation[e][d], times scale[d]
-            maps[b, :, 3] = ctr[b]
+            maps[b, :, :dim] = rot[b].T * sc[b][:, None]       # source axis d = sum_e g[e] rotation[e][d], times scale[d]
+            maps[b, :, dim] = ctr[b]
         else:
             plain[b, 0], plain[b, 1:] = 1, lb[b]
     return maps, plain
@@ -156,7 +170,8 @@ def augment_spatial(data, seg, patch_size, patch_center_dist_from_border=30, do_
                     border_cval_seg=0, order_seg=0, random_crop=True, p_el_per_sample=1, p_scale_per_sample=1, p_rot_per_sample=1,
                     independent_scale_for_each_axis=False, p_rot_per_axis=1, p_independent_scale_per_axis=1, params=None, rs=None):
     """batchgenerators' ``augment_spatial`` without the elastic deformation (``do_elastic_deform`` defaults to False here and True raises).
-    ``seg`` may be None.  Returns (data, seg) of extents ``patch_size``."""
+    ``seg`` may be None.  Returns (data, seg) of extents ``patch_size``.  Rank-4 ``data`` / ``seg`` (B, P, H, W) with a 2-entry ``patch_size``
+    is its dim == 2 form: every plane of a sample goes through the same in-plane transform (``ops.augment_spatial2d``)."""
     if do_elastic_deform:
         raise NotImplementedError("augmentation: do_elastic_deform=True (the 3-D trainer sets do_elastic = False)")
     if order_data not in (0, 1, 3):
@@ -166,25 +181,32 @@ def augment_spatial(data, seg, patch_size, patch_center_dist_from_border=30, do_
     for name, mode in (("border_mode_data", border_mode_data), ("border_mode_seg", border_mode_seg)):
         if mode not in _MODES:
             raise NotImplementedError(f"augmentation: {name}={mode!r} (supported: 'constant', 'nearest')")
-    x = _device(data, "data")
+    x = _device(data, "data", (4, 5))
     B, patch_size = x.shape[0], tuple(int(v) for v in patch_size)
+    dim = x.ndim - 2
+    if len(patch_size) != dim:
+        raise ValueError(f"augmentation: patch_size {patch_size} does not go with data {tuple(x.shape)} of {dim} spatial axes")
+    spatial, spatial_labels = (ops.augment_spatial, ops.augment_spatial_labels) if dim == 3 else (ops.augment_spatial2d,
+                                                                                                  ops.augment_spatial2d_labels)
     if params is None:
         params = draw_spatial(_rs(rs), x.shape[2:], patch_size, B, patch_center_dist_from_border, False, do_rotation, angle_x, angle_y, angle_z,
                               do_scale, scale, random_crop, p_scale_per_sample, p_rot_per_sample, independent_scale_for_each_axis,
                               p_rot_per_axis, p_independent_scale_per_axis)
-    maps, plain = _spatial_tables(params, B)
+    maps, plain = _spatial_tables(params, B, dim)
     xn, back = _native(x)
-    out = ops.augment_spatial(xn, patch_size, maps, plain, order_data, _MODES[border_mode_data], float(border_cval_data)).to(back)
+    out = spatial(xn, patch_size, maps, plain, order_data, _MODES[border_mode_data], float(border_cval_data)).to(back)
     out_seg = None
     if seg is not None:
-        s = _device(seg, "seg")
+        s = _device(seg, "seg", (4, 5))
+        if s.ndim != x.ndim:
+            raise ValueError(f"augmentation: seg {tuple(s.shape)} and data {tuple(x.shape)} differ in rank")
         if s.shape[0] != B or tuple(s.shape[2:]) != tuple(x.shape[2:]):
             raise ValueError(f"augmentation: seg {tuple(s.shape)} does not go with data {tuple(x.shape)}")
         if order_seg == 1 and border_mode_seg == "constant" and not float(border_cval_seg) < 0.5:
             raise NotImplementedError(f"augmentation: border_cval_seg={border_cval_seg!r} with order_seg=1 (every label would pass the 0.5 "
                                       "threshold outside the volume; supported: values below 0.5)")
         labels = resampling._as_labels(s)
-        out_seg = ops.augment_spatial_labels(labels, patch_size, maps, plain, order_seg, _MODES[border_mode_seg], float(border_cval_seg))
+        out_seg = spatial_labels(labels, patch_size, maps, plain, order_seg, _MODES[border_mode_seg], float(border_cval_seg))
         out_seg = out_seg.to(s.dtype)
     return out, out_seg
 
@@ -380,7 +402,7 @@ def draw_linear_downsampling_scipy(rs, batch, channels, zoom_range=(0.5, 1), per
     return rec
 
 
-def _apply_lowres(x, params, order_downsample, order_upsample):
+def _apply_lowres(x, params, order_downsample, order_upsample, ignore_axes=None):
     zoom = _per_channel(params["zoom"], x.shape[0], x.shape[1], "zoom")
     if not (zoom > 0).any():
         return x
@@ -390,6 +412,8 @@ def _apply_lowres(x, params, order_downsample, order_upsample):
         for c in range(x.shape[1]):
             if zoom[b, c] > 0:
                 target = np.round(shape * zoom[b, c]).astype(int)
+                for i in ignore_axes or ():
+                    target[i] = shape[i]
                 low = resampling.resample_data_or_seg(x[b, c:c + 1], target, False, order=order_downsample)
                 y[b, c:c + 1] = resampling.resample_data_or_seg(low, shape, False, order=order_upsample)
     return y
@@ -398,15 +422,18 @@ def _apply_lowres(x, params, order_downsample, order_upsample):
 def augment_linear_downsampling_scipy(data, zoom_range=(0.5, 1), per_channel=True, p_per_channel=1, channels=None, order_downsample=1,
                                       order_upsample=0, ignore_axes=None, p_per_sample=1, params=None, rs=None):
     """Every channel with a zoom in the record goes down to ``round(shape * zoom)`` and back up (``resize(..., mode='edge',
-    anti_aliasing=False)``: ``resampling.resample_data_or_seg``)."""
+    anti_aliasing=False)``: ``resampling.resample_data_or_seg``).  ``ignore_axes``: spatial axes whose extent the low-resolution array keeps
+    (the dummy-2D branch passes ``(0,)``)."""
     if channels is not None:
         raise NotImplementedError("augmentation: channels= (the trainer's SimulateLowResolutionTransform processes every channel)")
     if ignore_axes is not None:
-        raise NotImplementedError("augmentation: ignore_axes= (set by the dummy-2D branch only)")
+        ignore_axes = tuple(int(i) for i in ignore_axes)
+        if any(i not in (0, 1, 2) for i in ignore_axes):
+            raise ValueError(f"augmentation: ignore_axes={ignore_axes!r} (spatial axes 0, 1, 2)")
     x, back = _native(_device(data, "data"))
     if params is None:
         params = draw_linear_downsampling_scipy(_rs(rs), x.shape[0], x.shape[1], zoom_range, per_channel, p_per_channel, p_per_sample)
-    y = _apply_lowres(x, params, order_downsample, order_upsample)
+    y = _apply_lowres(x, params, order_downsample, order_upsample, ignore_axes)
     return (y.clone() if y is x else y).to(back)
 
 
@@ -514,15 +541,26 @@ class MoreDAAugmentation:
 
     ``params`` has the keys of ``default_3D_augmentation_params``.  ``seed`` seeds the numpy stream of the draws and the torch stream of the noise
     field; two instances with the same seed give bitwise equal batches.  ``draw(batch, src_shape, channels)`` returns the records of one call and
-    ``__call__(..., records=...)`` applies given ones."""
+    ``__call__(..., records=...)`` applies given ones.
+
+    ``params['dummy_2D']`` (the ACDC trainer's anisotropic 16 x 160 x 160 patch, data_augmentation_moreDA.py:54-75) takes the 2-entry
+    ``patch_size`` the trainer passes (``patch_size[1:]``): data and seg (B, C, D, H, W) go through the spatial step as (B, C D, H, W) planes,
+    one in-plane transform per sample, and come back as (B, C, D, h, w); the low-resolution stage keeps the depth extent
+    (``ignore_axes=(0,)``, :91-94); everything else runs in 3-D as without it."""
 
     def __init__(self, patch_size, params, deep_supervision_scales=None, order_data=3, order_seg=1, border_val_seg=-1, seed=None, soft_ds=False,
                  regions=None):
         assert params.get('mirror') is None, "old version of params, use new keyword do_mirror"
         if params.get("selected_data_channels") is not None:
             raise NotImplementedError("augmentation: selected_data_channels")
-        if params.get("dummy_2D"):
-            raise NotImplementedError("augmentation: dummy_2D")
+        self.patch_size = tuple(int(v) for v in patch_size)
+        self.dummy_2D = bool(params.get("dummy_2D"))
+        if self.dummy_2D and len(self.patch_size) != 2:
+            raise NotImplementedError(f"augmentation: dummy_2D with patch_size {self.patch_size} (the trainer passes patch_size[1:], the two "
+                                      "in-plane extents)")
+        if not self.dummy_2D and len(self.patch_size) != 3:
+            raise NotImplementedError(f"augmentation: patch_size {self.patch_size} without dummy_2D (three spatial extents; the 2-D loader's "
+                                      "chain is not part of this module)")
         if params.get("do_elastic"):
             raise NotImplementedError("augmentation: do_elastic (the 3-D trainer sets do_elastic = False)")
         for key in _CASCADE_KEYS:
@@ -535,7 +573,6 @@ class MoreDAAugmentation:
         mask = params.get("mask_was_used_for_normalization")
         if mask is not None and any(bool(v) for v in (mask.values() if hasattr(mask, "values") else mask)):
             raise NotImplementedError("augmentation: mask_was_used_for_normalization with a channel set (MaskTransform)")
-        self.patch_size = tuple(int(v) for v in patch_size)
         self.params = dict(params)
         self.deep_supervision_scales = deep_supervision_scales
         self.order_data, self.order_seg, self.border_val_seg = order_data, order_seg, border_val_seg
@@ -552,9 +589,13 @@ class MoreDAAugmentation:
                     independent_scale_for_each_axis=p.get("independent_scale_factor_for_each_axis"))
 
     def draw(self, batch, src_shape, channels):
-        """The records of one call, drawn in the chain's order."""
+        """The records of one call, drawn in the chain's order.  ``src_shape``: the three spatial extents of the batch (with ``dummy_2D`` the
+        spatial record is drawn for its last two)."""
         p, rs = self.params, self.rs
-        rec = {"spatial": draw_spatial(rs, src_shape, self.patch_size, batch, **self._spatial_keywords()),
+        src_shape = tuple(int(v) for v in src_shape)
+        if len(src_shape) != 3:
+            raise ValueError(f"augmentation: src_shape {src_shape} (the three spatial extents of the batch)")
+        rec = {"spatial": draw_spatial(rs, src_shape[1:] if self.dummy_2D else src_shape, self.patch_size, batch, **self._spatial_keywords()),
                "noise": draw_gaussian_noise(rs, batch, (0, 0.1), 0.1),
                "blur": draw_gaussian_blur(rs, batch, channels, (0.5, 1.), True, 0.5, 0.2),
                "brightness": draw_brightness_multiplicative(rs, batch, channels, (0.75, 1.25), True, 0.15)}
@@ -581,9 +622,15 @@ class MoreDAAugmentation:
         if noise is None and self.generator is None and bool(np.asarray(rec["noise"]["apply"]).any()):
             self.generator = torch.Generator(device=x.device)
             self.generator.manual_seed(int(self.seed) if self.seed is not None else int(self.rs.randint(0, 2 ** 31 - 1)))
+        if self.dummy_2D:                                                   # Convert3DTo2DTransform: (channel, depth slice) -> plane
+            if tuple(s.shape[2:]) != tuple(x.shape[2:]):
+                raise ValueError(f"augmentation: seg {tuple(s.shape)} does not go with data {tuple(x.shape)}")
+            depth, x, s = x.shape[2], x.reshape(B, -1, *x.shape[3:]), s.reshape(B, -1, *s.shape[3:])
         x, s = augment_spatial(x, s, self.patch_size, do_elastic_deform=False, border_mode_data=p.get("border_mode_data"), border_cval_data=0,
                                order_data=self.order_data, border_mode_seg="constant", border_cval_seg=self.border_val_seg,
                                order_seg=self.order_seg, params=rec["spatial"])
+        if self.dummy_2D:                                                   # Convert2DTo3DTransform
+            x, s = x.reshape(B, C, depth, *x.shape[2:]), s.reshape(B, -1, depth, *s.shape[2:])
         x = x if x.dtype == torch.float32 else x.to(torch.float32)          # the loader's batches are float32; so is NumpyToTensor('float')
         flip = _flip_masks(rec["mirror"], B) if "mirror" in rec else np.zeros(B, np.int32)
         last = "gamma" if "gamma" in rec else "gamma_inverted"              # the mirror rides on the last streaming pass of the image
@@ -593,7 +640,7 @@ class MoreDAAugmentation:
         if "additive" in rec:
             x = _apply_scale_add(x, rec["additive"]["apply"], np.ones((B, C)), _per_channel(rec["additive"]["add"], B, C, "add"))
         x = _apply_contrast(x, rec["contrast"])
-        x = _apply_lowres(x, rec["lowres"], 0, 3)
+        x = _apply_lowres(x, rec["lowres"], 0, 3, (0,) if self.dummy_2D else None)
         retain = bool(p.get("gamma_retain_stats"))
         x = _apply_gamma(x, rec["gamma_inverted"], True, retain, flip if last == "gamma_inverted" else None)
         if "gamma" in rec:

@@ -8,6 +8,10 @@
 //             code builds is never stored), applies scipy.ndimage.map_coordinates' border rule, gathers 1 / 8 / 64 taps with scipy's weights
 //             in scipy's order and stores in the input's type.  Order 3 reads float64 B-spline coefficients.  A sample flagged "plain" is a
 //             copy of a box.
+//   in-plane  (a) and (b) for the ACDC trainer's dummy-2D branch (Convert3DTo2DTransform around SpatialTransform, data_augmentation_moreDA.py:
+//             54-75; batchgenerators' augment_spatial with dim == 2): arrays (B, P, H, W), every plane of a sample sampled at the same in-plane
+//             coordinates from a 2x3 map.  The same kernels with RANK = 2: depth is no interpolation axis, so 1 / 4 / 16 taps, 4 neighbours
+//             for the labels and coefficients filtered along H and W only.
 //   labels    (b) the same coordinates for the label map.  Order 1 is batchgenerators' per-label rule (one map_coordinates of the indicator per
 //             label, ascending, later labels overwrite where the result is >= 0.5) in ONE visit of the 8 neighbours: a label's interpolant is
 //             the sum of the weights of the cells that hold it, so the per-label volumes are never written.
@@ -83,10 +87,13 @@ __device__ __forceinline__ bool aug_lane(const AugArgs &a, int channels, AugLane
     return true;
 }
 
-// The box of a plain sample, kept inside the source whatever the table says.
+// The box of a plain sample, kept inside the source whatever the table says.  pl: (flag, lb of each of the RANK axes).
+template <int RANK>
 __device__ __forceinline__ long aug_plain_row(const AugArgs &a, const int *pl, const AugLane &l)
 {
-    const int z = min(max(l.oz + pl[1], 0), a.src[0] - 1), y = min(max(l.oy + pl[2], 0), a.src[1] - 1);
+    const int y = min(max(l.oy + pl[RANK - 1], 0), a.src[1] - 1);
+    if (RANK == 2) return (long)y * a.src[2];
+    const int z = min(max(l.oz + pl[1], 0), a.src[0] - 1);
     return ((long)z * a.src[1] + y) * a.src[2];
 }
 
@@ -138,16 +145,23 @@ __device__ __forceinline__ bool aug_axis(double cc, int n_src, int pad, int mode
     return true;
 }
 
+// cc[3 - RANK .. 2]: the source coordinate on the RANK interpolation axes from the sample's RANK x (RANK + 1) map.
+template <int RANK>
 __device__ __forceinline__ void aug_coordinate(const AugArgs &a, const double *m, int oz, int oy, int ox, double *cc)
 {
 #pragma clang fp contract(off)
-    const double g0 = (double)oz - (double)(a.out[0] - 1) / 2.0, g1 = (double)oy - (double)(a.out[1] - 1) / 2.0,
-                 g2 = (double)ox - (double)(a.out[2] - 1) / 2.0;
+    const double g1 = (double)oy - (double)(a.out[1] - 1) / 2.0, g2 = (double)ox - (double)(a.out[2] - 1) / 2.0;
+    if (RANK == 2) {
+        for (int d = 0; d < 2; ++d) cc[1 + d] = (m[3 * d] * g1 + m[3 * d + 1] * g2) + m[3 * d + 2];
+        return;
+    }
+    const double g0 = (double)oz - (double)(a.out[0] - 1) / 2.0;
     for (int d = 0; d < 3; ++d) cc[d] = ((m[4 * d] * g0 + m[4 * d + 1] * g1) + m[4 * d + 2] * g2) + m[4 * d + 3];
 }
 
-// (a) ORDER 0 / 1: S = T, the image itself; ORDER 3: S = double, the coefficients.
-template <typename T, typename S, int ORDER>
+// (a) ORDER 0 / 1: S = T, the image itself; ORDER 3: S = double, the coefficients.  RANK 2: the planes of a sample are its channels
+// (a.C planes, a.src[0] = a.ext[0] = a.out[0] = 1), axis 0 has one tap at 0 and no weight.
+template <typename T, typename S, int ORDER, int RANK>
 __global__ void __launch_bounds__(AUG_THREADS) dlka_augment_spatial_kernel(AugArgs a, const T *x, const S *src, T *y, const double *maps,
                                                                               const int *plain)
 {
@@ -156,31 +170,35 @@ __global__ void __launch_bounds__(AUG_THREADS) dlka_augment_spatial_kernel(AugAr
     if (!aug_lane(a, a.C, l)) return;
     const long ch = (long)l.b * a.C + l.c;
     T *out = y + ((ch * a.out[0] + l.oz) * a.out[1] + l.oy) * a.out[2] + l.ox0;
-    const int *pl = plain + 4 * l.b;
+    const int *pl = plain + (RANK + 1) * l.b;
     if (pl[0]) {
-        const T *row = x + ch * a.src_cells + aug_plain_row(a, pl, l);
-        for (int v = 0; v < l.nv; ++v) out[v] = row[min(max(l.ox0 + v + pl[3], 0), a.src[2] - 1)];
+        const T *row = x + ch * a.src_cells + aug_plain_row<RANK>(a, pl, l);
+        for (int v = 0; v < l.nv; ++v) out[v] = row[min(max(l.ox0 + v + pl[RANK], 0), a.src[2] - 1)];
         return;
     }
-    constexpr int TAPS = ORDER == 3 ? 4 : ORDER + 1;
+    constexpr int TAPS = ORDER == 3 ? 4 : ORDER + 1, TAPS0 = RANK == 3 ? TAPS : 1;
     const int pad = ORDER == 3 ? a.pad : 0;
     const int e1 = a.src[1] + 2 * pad, e2 = a.src[2] + 2 * pad;
     const S *p = src + ch * (ORDER == 3 ? a.ext_cells : a.src_cells);
     for (int v = 0; v < l.nv; ++v) {
         double cc[3], w[3][TAPS];
         int idx[3][TAPS];
-        aug_coordinate(a, maps + 12 * l.b, l.oz, l.oy, l.ox0 + v, cc);
+        aug_coordinate<RANK>(a, maps + RANK * (RANK + 1) * l.b, l.oz, l.oy, l.ox0 + v, cc);
         bool inside = true;
-        for (int d = 0; d < 3; ++d) inside = aug_axis<ORDER>(cc[d], a.src[d], pad, a.mode, idx[d], w[d]) && inside;
+        if (RANK == 2) idx[0][0] = 0;
+        for (int d = 3 - RANK; d < 3; ++d) inside = aug_axis<ORDER>(cc[d], a.src[d], pad, a.mode, idx[d], w[d]) && inside;
         double t = a.cval;
         if (inside) {
             t = 0.0;
-            for (int k0 = 0; k0 < TAPS; ++k0)
+            for (int k0 = 0; k0 < TAPS0; ++k0)
                 for (int k1 = 0; k1 < TAPS; ++k1) {
                     const S *row = p + ((long)idx[0][k0] * e1 + idx[1][k1]) * e2;
                     for (int k2 = 0; k2 < TAPS; ++k2) {
                         double coeff = aug_ld(row, idx[2][k2]);
-                        if (ORDER > 0) coeff = ((coeff * w[0][k0]) * w[1][k1]) * w[2][k2];
+                        if (ORDER > 0) {
+                            if (RANK == 3) coeff = coeff * w[0][k0];
+                            coeff = (coeff * w[1][k1]) * w[2][k2];
+                        }
                         t = t + coeff;
                     }
                 }
@@ -189,8 +207,8 @@ __global__ void __launch_bounds__(AUG_THREADS) dlka_augment_spatial_kernel(AugAr
     }
 }
 
-// (b)
-template <int ORDER>
+// (b) RANK 2: the 4 in-plane neighbours.
+template <int ORDER, int RANK>
 __global__ void __launch_bounds__(AUG_THREADS) dlka_augment_labels_kernel(AugArgs a, const int *seg, int *y, const double *maps, const int *plain)
 {
 #pragma clang fp contract(off)
@@ -199,19 +217,23 @@ __global__ void __launch_bounds__(AUG_THREADS) dlka_augment_labels_kernel(AugArg
     const long ch = (long)l.b * a.C + l.c;
     int *out = y + ((ch * a.out[0] + l.oz) * a.out[1] + l.oy) * a.out[2] + l.ox0;
     const int *p = seg + ch * a.src_cells;
-    const int *pl = plain + 4 * l.b;
+    const int *pl = plain + (RANK + 1) * l.b;
     if (pl[0]) {
-        const int *row = p + aug_plain_row(a, pl, l);
-        for (int v = 0; v < l.nv; ++v) out[v] = row[min(max(l.ox0 + v + pl[3], 0), a.src[2] - 1)];
+        const int *row = p + aug_plain_row<RANK>(a, pl, l);
+        for (int v = 0; v < l.nv; ++v) out[v] = row[min(max(l.ox0 + v + pl[RANK], 0), a.src[2] - 1)];
         return;
     }
-    constexpr int TAPS = ORDER + 1;
+    constexpr int TAPS = ORDER + 1, TAPS0 = RANK == 3 ? TAPS : 1;
     for (int v = 0; v < l.nv; ++v) {
         double cc[3], w[3][TAPS];
         int idx[3][TAPS];
-        aug_coordinate(a, maps + 12 * l.b, l.oz, l.oy, l.ox0 + v, cc);
+        aug_coordinate<RANK>(a, maps + RANK * (RANK + 1) * l.b, l.oz, l.oy, l.ox0 + v, cc);
         bool inside = true;
-        for (int d = 0; d < 3; ++d) inside = aug_axis<ORDER>(cc[d], a.src[d], 0, a.mode, idx[d], w[d]) && inside;
+        if (RANK == 2) {
+            idx[0][0] = 0;
+            w[0][0] = 1.0;
+        }
+        for (int d = 3 - RANK; d < 3; ++d) inside = aug_axis<ORDER>(cc[d], a.src[d], 0, a.mode, idx[d], w[d]) && inside;
         if (!inside) {                      // order 1: every label's interpolant is cval < 0.5
             out[v] = ORDER == 0 ? (int)a.cval : 0;
             continue;
@@ -223,11 +245,11 @@ __global__ void __launch_bounds__(AUG_THREADS) dlka_augment_labels_kernel(AugArg
         int lab[8];
         double wt[8];
         int n = 0;
-        for (int k0 = 0; k0 < TAPS; ++k0)
+        for (int k0 = 0; k0 < TAPS0; ++k0)
             for (int k1 = 0; k1 < TAPS; ++k1)
                 for (int k2 = 0; k2 < TAPS; ++k2) {
                     lab[n] = p[((long)idx[0][k0] * a.src[1] + idx[1][k1]) * a.src[2] + idx[2][k2]];
-                    wt[n] = ((1.0 * w[0][k0]) * w[1][k1]) * w[2][k2];
+                    wt[n] = ((1.0 * w[0][k0]) * w[1][k1]) * w[2][k2];      // rank 2: w[0][0] is 1.0, which changes no bit
                     ++n;
                 }
         bool found = false;
@@ -404,19 +426,24 @@ __global__ void __launch_bounds__(AUG_THREADS) dlka_augment_pointwise_kernel(Aug
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------------------------------
-static int aug_check(const dlka_augment_desc *d, AugArgs *a)
+// rank 2: the description's src[0..1] / out[0..1] are (H, W) and its third entries are 0; the kernels see a depth of one cell that is never
+// padded, and C planes per sample.
+static int aug_check(const dlka_augment_desc *d, AugArgs *a, int rank)
 {
     if (!d) return DLKA_ERR_NULL;
     if (d->B < 1 || d->C < 1 || d->pad < 0) return DLKA_ERR_SHAPE;
     if (d->mode != DLKA_AUG_CONSTANT && d->mode != DLKA_AUG_NEAREST) return DLKA_ERR_UNSUPPORTED;
     if (d->pad > 64) return DLKA_ERR_UNSUPPORTED;
+    if (rank == 2 && (d->src[2] != 0 || d->out[2] != 0)) return DLKA_ERR_SHAPE;
     long sc = 1, ec = 1, oc = 1;
-    for (int ax = 0; ax < 3; ++ax) {
-        if (d->src[ax] < 1 || d->out[ax] < 1) return DLKA_ERR_SHAPE;
-        if (d->src[ax] > 0x7fffffffL - 128 || d->out[ax] > 0x7fffffffL) return DLKA_ERR_UNSUPPORTED;
-        a->src[ax] = (int)d->src[ax];
-        a->ext[ax] = (int)d->src[ax] + 2 * d->pad;
-        a->out[ax] = (int)d->out[ax];
+    a->src[0] = a->ext[0] = a->out[0] = 1;
+    for (int ax = 3 - rank; ax < 3; ++ax) {
+        const int64_t n_src = d->src[ax - (3 - rank)], n_out = d->out[ax - (3 - rank)];
+        if (n_src < 1 || n_out < 1) return DLKA_ERR_SHAPE;
+        if (n_src > 0x7fffffffL - 128 || n_out > 0x7fffffffL) return DLKA_ERR_UNSUPPORTED;
+        a->src[ax] = (int)n_src;
+        a->ext[ax] = (int)n_src + 2 * d->pad;
+        a->out[ax] = (int)n_out;
         sc *= a->src[ax];
         ec *= a->ext[ax];
         oc *= a->out[ax];
@@ -441,30 +468,27 @@ static unsigned aug_blocks(const AugArgs &a)
     return (unsigned)cdivl((long)a.B * a.C * a.out[0] * a.out[1] * cdiv(a.out[2], AUG_VPT), AUG_THREADS);
 }
 
-template <typename T>
+template <typename T, int RANK>
 static void aug_launch_spatial(const AugArgs &a, const void *x, const double *coef, void *y, const double *maps, const int32_t *plain,
                                hipStream_t st)
 {
     const dim3 grid(aug_blocks(a)), block(AUG_THREADS);
     if (a.order == 0)
-        DLKA_LAUNCH((dlka_augment_spatial_kernel<T, T, 0>), grid, block, 0, st, a, (const T *)x, (const T *)x, (T *)y, maps, plain);
+        DLKA_LAUNCH((dlka_augment_spatial_kernel<T, T, 0, RANK>), grid, block, 0, st, a, (const T *)x, (const T *)x, (T *)y, maps, plain);
     else if (a.order == 1)
-        DLKA_LAUNCH((dlka_augment_spatial_kernel<T, T, 1>), grid, block, 0, st, a, (const T *)x, (const T *)x, (T *)y, maps, plain);
+        DLKA_LAUNCH((dlka_augment_spatial_kernel<T, T, 1, RANK>), grid, block, 0, st, a, (const T *)x, (const T *)x, (T *)y, maps, plain);
     else
-        DLKA_LAUNCH((dlka_augment_spatial_kernel<T, double, 3>), grid, block, 0, st, a, (const T *)x, coef, (T *)y, maps, plain);
+        DLKA_LAUNCH((dlka_augment_spatial_kernel<T, double, 3, RANK>), grid, block, 0, st, a, (const T *)x, coef, (T *)y, maps, plain);
 }
 
 static bool aug_dtype_ok(int dtype) { return dtype == DLKA_F32 || dtype == DLKA_BF16 || dtype == DLKA_F64 || dtype == DLKA_AUG_I16; }
 
-}  // namespace dlka
-
-using namespace dlka;
-
-extern "C" int dlka_augment_spatial(const void *x, const double *coef, void *y, const dlka_augment_desc *d, const double *maps,
-                                    const int32_t *plain, void *stream)
+template <int RANK>
+static int aug_spatial(const void *x, const double *coef, void *y, const dlka_augment_desc *d, const double *maps, const int32_t *plain,
+                       void *stream)
 {
     AugArgs a;
-    const int rc = aug_check(d, &a);
+    const int rc = aug_check(d, &a, RANK);
     if (rc != DLKA_OK) return rc;
     if (!x || !y || !maps || !plain) return DLKA_ERR_NULL;
     if (x == y) return DLKA_ERR_UNSUPPORTED;
@@ -475,22 +499,23 @@ extern "C" int dlka_augment_spatial(const void *x, const double *coef, void *y, 
     g_aug_launches.fetch_add(1, std::memory_order_relaxed);
     hipStream_t st = (hipStream_t)stream;
     if (d->dtype == DLKA_F32)
-        aug_launch_spatial<float>(a, x, coef, y, maps, plain, st);
+        aug_launch_spatial<float, RANK>(a, x, coef, y, maps, plain, st);
     else if (d->dtype == DLKA_BF16)
-        aug_launch_spatial<bf16_t>(a, x, coef, y, maps, plain, st);
+        aug_launch_spatial<bf16_t, RANK>(a, x, coef, y, maps, plain, st);
     else if (d->dtype == DLKA_F64)
-        aug_launch_spatial<double>(a, x, coef, y, maps, plain, st);
+        aug_launch_spatial<double, RANK>(a, x, coef, y, maps, plain, st);
     else
-        aug_launch_spatial<int16_t>(a, x, coef, y, maps, plain, st);
+        aug_launch_spatial<int16_t, RANK>(a, x, coef, y, maps, plain, st);
     DLKA_CHECK_LAUNCH();
     return DLKA_OK;
 }
 
-extern "C" int dlka_augment_spatial_labels(const int32_t *seg, int32_t *out, const dlka_augment_desc *d, const double *maps,
-                                           const int32_t *plain, void *stream)
+template <int RANK>
+static int aug_spatial_labels(const int32_t *seg, int32_t *out, const dlka_augment_desc *d, const double *maps, const int32_t *plain,
+                              void *stream)
 {
     AugArgs a;
-    const int rc = aug_check(d, &a);
+    const int rc = aug_check(d, &a, RANK);
     if (rc != DLKA_OK) return rc;
     if (!seg || !out || !maps || !plain) return DLKA_ERR_NULL;
     if (seg == out || d->pad != 0) return DLKA_ERR_UNSUPPORTED;
@@ -500,11 +525,39 @@ extern "C" int dlka_augment_spatial_labels(const int32_t *seg, int32_t *out, con
     g_aug_launches.fetch_add(1, std::memory_order_relaxed);
     const dim3 grid(aug_blocks(a)), block(AUG_THREADS);
     if (d->order == 0)
-        DLKA_LAUNCH(dlka_augment_labels_kernel<0>, grid, block, 0, (hipStream_t)stream, a, seg, out, maps, plain);
+        DLKA_LAUNCH((dlka_augment_labels_kernel<0, RANK>), grid, block, 0, (hipStream_t)stream, a, seg, out, maps, plain);
     else
-        DLKA_LAUNCH(dlka_augment_labels_kernel<1>, grid, block, 0, (hipStream_t)stream, a, seg, out, maps, plain);
+        DLKA_LAUNCH((dlka_augment_labels_kernel<1, RANK>), grid, block, 0, (hipStream_t)stream, a, seg, out, maps, plain);
     DLKA_CHECK_LAUNCH();
     return DLKA_OK;
+}
+
+}  // namespace dlka
+
+using namespace dlka;
+
+extern "C" int dlka_augment_spatial(const void *x, const double *coef, void *y, const dlka_augment_desc *d, const double *maps,
+                                    const int32_t *plain, void *stream)
+{
+    return aug_spatial<3>(x, coef, y, d, maps, plain, stream);
+}
+
+extern "C" int dlka_augment_spatial_labels(const int32_t *seg, int32_t *out, const dlka_augment_desc *d, const double *maps,
+                                           const int32_t *plain, void *stream)
+{
+    return aug_spatial_labels<3>(seg, out, d, maps, plain, stream);
+}
+
+extern "C" int dlka_augment_spatial2d(const void *x, const double *coef, void *y, const dlka_augment_desc *d, const double *maps,
+                                      const int32_t *plain, void *stream)
+{
+    return aug_spatial<2>(x, coef, y, d, maps, plain, stream);
+}
+
+extern "C" int dlka_augment_spatial2d_labels(const int32_t *seg, int32_t *out, const dlka_augment_desc *d, const double *maps,
+                                             const int32_t *plain, void *stream)
+{
+    return aug_spatial_labels<2>(seg, out, d, maps, plain, stream);
 }
 
 extern "C" int dlka_augment_gaussian(const void *x, void *y, int dtype, int64_t channels, const int64_t *ext, int axis, const int32_t *radius,

@@ -1452,6 +1452,94 @@ def augment_spatial_labels(seg, out, maps, plain, order, mode, cval):
     return y
 
 
+# the dummy-2D branch: (b, p, h, w), p the planes of a sample (channels x depth slices)
+def _aug_planes(x, what):
+    L.require_device(x)
+    if x.ndim != 4 or x.numel() == 0:
+        raise RuntimeError(f"augment: {what} is (b, p, y, z) with no empty axis, got {tuple(x.shape)}")
+    if x[0, 0].numel() >= 2 ** 31:
+        raise RuntimeError("augment: fewer than 2^31 cells per plane")
+    return x.contiguous()
+
+
+def _aug_desc2d(x, out, order, mode, cval, pad=0, dtype=L.DLKA_F32):
+    out = tuple(int(v) for v in out)
+    if len(out) != 2 or min(out) < 1 or out[0] * out[1] >= 2 ** 31:
+        raise RuntimeError(f"augment: two positive patch extents below 2^31 cells, got {out}")
+    d = L.AugmentDesc()
+    d.B, d.C, d.dtype, d.order, d.mode, d.pad, d.cval = int(x.shape[0]), int(x.shape[1]), dtype, int(order), int(mode), int(pad), float(cval)
+    for ax in range(2):
+        d.src[ax], d.out[ax] = int(x.shape[2 + ax]), out[ax]
+    d.src[2] = d.out[2] = 0
+    return d, out
+
+
+def _aug_sample_tables2d(x, out, maps, plain):
+    """maps (B, 2, 3) float64 and plain (B, 3) int (flag, lb_y, lb_x) on the device.  The kernels trust the boxes: checked here."""
+    maps = np.ascontiguousarray(np.asarray(maps, dtype=np.float64).reshape(-1, 6))
+    plain = np.ascontiguousarray(np.asarray(plain, dtype=np.int32).reshape(-1, 3))
+    if maps.shape[0] != x.shape[0] or plain.shape[0] != x.shape[0]:
+        raise RuntimeError(f"augment: one map and one crop record per sample ({x.shape[0]})")
+    for b in range(plain.shape[0]):
+        if plain[b, 0] and any(plain[b, 1 + ax] < 0 or plain[b, 1 + ax] + out[ax] > x.shape[2 + ax] for ax in range(2)):
+            raise RuntimeError(f"augment: the crop of sample {b} at {plain[b, 1:].tolist()} leaves the source {tuple(x.shape[2:])}")
+    return torch.from_numpy(maps).to(x.device), torch.from_numpy(plain).to(x.device)
+
+
+def augment_spline_coefficients2d(x, mode):
+    """float64 cubic B-spline coefficients of every plane of ``x`` (b, p, y, z), as scipy.ndimage.map_coordinates prepares them for a 2-D
+    array: the in-plane axes alone are padded (mode 'nearest': DLKA_RESAMPLE_SPLINE_PAD edge samples, 'reflect' start values; 'constant': no
+    padding, 'mirror') and filtered.  The batch's stack of planes is ONE volume (b p, y, z) filtered along its axes 1 and 2: three launches
+    whatever b and p are; a stack of 2^31 padded cells or more goes sample by sample.  Returns (coefficients (b, p, y + 2 pad, z + 2 pad), pad)."""
+    x = _aug_planes(x, "data")
+    src = x if x.dtype in _RS_DTYPES else x.to(torch.float64 if x.dtype == torch.int16 else torch.float32)
+    pad, boundary = (L.DLKA_RESAMPLE_SPLINE_PAD, L.DLKA_SPLINE_REFLECT) if mode == L.DLKA_AUG_NEAREST else (0, L.DLKA_SPLINE_MIRROR)
+    B, P = int(x.shape[0]), int(x.shape[1])
+    ext = [int(n) + 2 * pad for n in x.shape[2:]]
+    if P * ext[0] * ext[1] >= 2 ** 31:
+        raise RuntimeError("augment: fewer than 2^31 cells per padded sample")
+    coef = torch.empty([B, P] + ext, dtype=torch.float64, device=x.device)
+    if B * P * ext[0] * ext[1] < 2 ** 31:
+        spline_coefficients(src.reshape(B * P, *x.shape[2:]), (0, pad, pad), boundary, (1, 2), out=coef.reshape(B * P, *ext))
+    else:
+        for b in range(B):
+            spline_coefficients(src[b], (0, pad, pad), boundary, (1, 2), out=coef[b])
+    return coef, pad
+
+
+def augment_spatial2d(x, out, maps, plain, order, mode, cval):
+    """``x`` (b, p, y, z; float32, bfloat16, float64, int16): every plane of sample b sampled at the in-plane affine ``maps[b]`` (2, 3) with
+    scipy's 2-D map_coordinates rules (orders 0, 1, 3: 1 / 4 / 16 taps; mode DLKA_AUG_CONSTANT / DLKA_AUG_NEAREST); samples whose ``plain``
+    flag is set are copied in-plane boxes.  batchgenerators' augment_spatial with dim == 2 on the planes the dummy-2D branch makes."""
+    x = _aug_planes(x, "data")
+    if x.dtype not in _AUG_DTYPES:
+        raise RuntimeError(f"augment: float32, bfloat16, float64 or int16 planes, got {x.dtype}")
+    coef, pad = (augment_spline_coefficients2d(x, mode) if order == 3 and not all(int(p[0]) for p in np.asarray(plain).reshape(-1, 3))
+                 else (None, 0))
+    if order == 3 and coef is None:
+        order = 0                                            # every sample is a plain crop: nothing is interpolated
+    d, out = _aug_desc2d(x, out, order, mode, cval, pad, _AUG_DTYPES[x.dtype])
+    m, p = _aug_sample_tables2d(x, out, maps, plain)
+    y = torch.empty(tuple(x.shape[:2]) + out, dtype=x.dtype, device=x.device)
+    L.check(L.get_lib().dlka_augment_spatial2d(L.ptr(x), L.ptr(coef), L.ptr(y), ctypes.byref(d), L.ptr(m), L.ptr(p), L.stream_ptr(x)),
+            "augment_spatial2d")
+    return y
+
+
+def augment_spatial2d_labels(seg, out, maps, plain, order, mode, cval):
+    """int32 label planes (b, p, y, z) at the same coordinates: order 0 the nearest cell, order 1 the largest label whose bilinear weight over
+    the 4 in-plane neighbours is >= 0.5, else 0."""
+    seg = _aug_planes(seg, "seg")
+    if seg.dtype != torch.int32:
+        raise RuntimeError(f"augment: int32 label maps, got {seg.dtype}")
+    d, out = _aug_desc2d(seg, out, order, mode, cval)
+    m, p = _aug_sample_tables2d(seg, out, maps, plain)
+    y = torch.empty(tuple(seg.shape[:2]) + out, dtype=torch.int32, device=seg.device)
+    L.check(L.get_lib().dlka_augment_spatial2d_labels(L.ptr(seg), L.ptr(y), ctypes.byref(d), L.ptr(m), L.ptr(p), L.stream_ptr(seg)),
+            "augment_spatial2d_labels")
+    return y
+
+
 def augment_gaussian(x, radius, weights):
     """scipy.ndimage.gaussian_filter of every channel of ``x`` (b, c, x, y, z), one launch per axis: ``radius`` (b * c,) int, < 0 = the channel
     is copied; ``weights`` (b * c, DLKA_AUG_RADIUS_MAX + 1) float64, centre first."""

@@ -842,6 +842,15 @@ int dlka_spline_prefilter(double *coef, const int64_t *ext, int axis, int bounda
  * dlka_augment_spatial_labels   int32 maps.  order 0: the nearest cell (cval outside).  order 1: batchgenerators' per-label rule in one
  *              visit of the 8 neighbours: the largest label whose summed trilinear weight is >= 0.5, else 0; outside under 'constant'
  *              every label's interpolant is cval, which must be < 0.5: 0.
+ * dlka_augment_spatial2d, dlka_augment_spatial2d_labels   the same two for the dummy-2D branch of the ACDC trainer (Convert3DTo2DTransform
+ *              around SpatialTransform, data_augmentation_moreDA.py:54-75; batchgenerators' augment_spatial with dim == 2): arrays
+ *              [B][P][H][W] with d->C = P, the planes of a sample (channels x depth slices), d->src[0..1] = (H, W), d->out[0..1] = (h, w) and
+ *              d->src[2] = d->out[2] = 0 (anything else, a 3-D description included: DLKA_ERR_SHAPE).  maps[6 b ..] is the sample's 2 x 3
+ *              map (src[d] = (m[3d] g_y + m[3d+1] g_x) + m[3d+2]), plain[3 b ..] = (flag, lb_y, lb_x); every plane of a sample is sampled at
+ *              the same in-plane coordinates.  Depth is no interpolation axis: 1 / 4 / 16 taps (outer H, inner W, ((coeff w_y) w_x) summed
+ *              left to right, scipy's 2-D map_coordinates), 4 neighbours for order-1 labels, and coef [B*P][H + 2 pad][W + 2 pad] is padded
+ *              and filtered along H and W only (the stack of planes as ONE volume through dlka_spline_pad with pad (0, pad, pad) and
+ *              dlka_spline_prefilter on axes 1 and 2).  Orders, modes, storage types, border rules and return codes are those above.
  * dlka_augment_gaussian   one axis of scipy.ndimage.gaussian_filter per launch: radius[ch] taps on either side (radius < 0: the channel is
  *              copied) with the weights w[ch][0 .. radius] (centre first, DLKA_AUG_RADIUS_MAX + 1 per channel), mode 'reflect', float64 sums.
  * dlka_augment_channel_stats   stats[4 ch ..] = (sum, sum of squares about the mean, min, max) in float64: lanes, waves, workgroups and the
@@ -875,6 +884,10 @@ int dlka_augment_spatial(const void *x, const double *coef, void *y, const dlka_
                          void *stream);
 int dlka_augment_spatial_labels(const int32_t *seg, int32_t *out, const dlka_augment_desc *d, const double *maps, const int32_t *plain,
                                 void *stream);
+int dlka_augment_spatial2d(const void *x, const double *coef, void *y, const dlka_augment_desc *d, const double *maps, const int32_t *plain,
+                           void *stream);
+int dlka_augment_spatial2d_labels(const int32_t *seg, int32_t *out, const dlka_augment_desc *d, const double *maps, const int32_t *plain,
+                                  void *stream);
 int dlka_augment_gaussian(const void *x, void *y, int dtype, int64_t channels, const int64_t *ext, int axis, const int32_t *radius,
                           const double *weights, void *stream);
 size_t dlka_augment_stats_workspace_bytes(int64_t channels, int64_t cells);
