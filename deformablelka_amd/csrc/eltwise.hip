@@ -7,7 +7,17 @@
 namespace dlka {
 
 
-struct OpGelu { __device__ __forceinline__ float operator()(float x) const { return gelu_f(x); } };
+// GELU and its derivative of the stand-alone entries, with the negative tail kept: 2 Phi(x) = 1 + erf(t), t = x / sqrt 2, cancels as t falls — below t = -3 a
+// few bits of the value are left, below t = -3.9 none (gelu_f returns -0 where GELU is -1e-8 .. -1e-38) — while erfc(-t) is the same quantity without a
+// subtraction.  The absolute error of gelu_f, about 6e-8 |x|, is inside every fp32 bound; a bf16 output, whose ulp scales with the value, shows it.  Above
+// t = -0.5 the sum is at least 0.48 and loses nothing.  (The fused epilogues of the blocks keep gelu_f / dgelu_f of dlka_common.h.)
+__device__ __forceinline__ float two_phi_f(float x)
+{
+    const float t = x * 0.70710678118654752440f;
+    return t < -0.5f ? erfcf(-t) : 1.f + erff(t);
+}
+__device__ __forceinline__ float gelu_tail_f(float x) { return 0.5f * x * two_phi_f(x); }
+__device__ __forceinline__ float dgelu_tail_f(float x) { return 0.5f * two_phi_f(x) + x * (0.39894228040143267794f * expf(-0.5f * x * x)); }
 
 template <typename T, int MODE>
 __global__ __launch_bounds__(256) void eltwise_kernel(const T *a, const T *b, const T *c,
@@ -16,9 +26,9 @@ __global__ __launch_bounds__(256) void eltwise_kernel(const T *a, const T *b, co
     const long stride = (long)gridDim.x * blockDim.x;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
         if (MODE == 0) {  // gelu fwd: o1 = gelu(a)
-            stf(o1 + i, gelu_f(ldf(a + i)));
+            stf(o1 + i, gelu_tail_f(ldf(a + i)));
         } else if (MODE == 1) {  // gelu bwd: o1 = b * dgelu(a)
-            stf(o1 + i, ldf(b + i) * dgelu_f(ldf(a + i)));
+            stf(o1 + i, ldf(b + i) * dgelu_tail_f(ldf(a + i)));
         } else if (MODE == 2) {  // mul fwd
             stf(o1 + i, ldf(a + i) * ldf(b + i));
         } else if (MODE == 3) {  // mul bwd: o1 = c*b ; o2 = c*a
@@ -29,7 +39,7 @@ __global__ __launch_bounds__(256) void eltwise_kernel(const T *a, const T *b, co
         } else if (MODE == 4) {  // add
             stf(o1 + i, ldf(a + i) + ldf(b + i));
         } else {  // gelu bwd of a sum: o1 = (b + c) * dgelu(a)
-            stf(o1 + i, (ldf(b + i) + ldf(c + i)) * dgelu_f(ldf(a + i)));
+            stf(o1 + i, (ldf(b + i) + ldf(c + i)) * dgelu_tail_f(ldf(a + i)));
         }
     }
 }

@@ -28,15 +28,30 @@ __device__ __forceinline__ float block_sum(float v, float *red)
     __syncthreads();
     return r;
 }
+
+// The value every BatchNorm kernel of a channel centres on: the median of five values spread over the channel's first plane (at 10, 30, 50, 70 and 90 % of it).
+// The sums are taken about it — var = m2 - m1^2 loses about eps_fp32 (1 + d^2) of its value, d = (pivot - mean) / std — so it has to be TYPICAL of the channel: a
+// single voxel (it used to be x[0][c][0], the corner that zero padding or a cropped background sets apart) can lie hundreds of std away.  Five wave-uniform loads,
+// no further pass over x; every workgroup of the statistics kernel finds the same value, pl_bn_finish_kernel hands it to the other kernels in stats[4C + c].
+__device__ __forceinline__ float pl_bn_pivot(const float *__restrict__ x, int c, long N)
+{
+    const float *xp = x + (long)c * N;
+    float a = xp[N / 10], b = xp[3 * N / 10], m = xp[N / 2], d = xp[7 * N / 10], e = xp[9 * N / 10], t;
+#define PL_SORT2(u, v) { t = fminf(u, v); v = fmaxf(u, v); u = t; }
+    PL_SORT2(a, b) PL_SORT2(d, e) PL_SORT2(a, d) PL_SORT2(b, e)   // a is the least of {a, b, d, e}, e their greatest: neither is the median of the five
+    PL_SORT2(b, m) PL_SORT2(m, d) PL_SORT2(b, m)                  // the median of the other three
+#undef PL_SORT2
+    return m;
+}
 }  // namespace
 
 // ---- BatchNorm3d, training mode ----------------------------------------------------------------------------------------------------
-// acc[c] = {sum (x - p_c), sum (x - p_c)^2} with the pivot p_c = x[0][c][0] (|mean| >> std must not cancel the variance away)
+// acc[c] = {sum (x - p_c), sum (x - p_c)^2} with the pivot p_c = pl_bn_pivot (|mean| >> std must not cancel the variance away)
 __global__ __launch_bounds__(PL_THREADS) void pl_bn_stats_kernel(const float *__restrict__ x, float *__restrict__ acc, int C, long N)
 {
     __shared__ float red[PL_THREADS];
     const int plane = blockIdx.y, c = plane % C;
-    const float p = x[(long)c * N];
+    const float p = pl_bn_pivot(x, c, N);
     const float *xp = x + (long)plane * N;
     const long e0 = (long)blockIdx.x * PL_RCHUNK;
     float s1 = 0.f, s2 = 0.f;
@@ -54,13 +69,13 @@ __global__ __launch_bounds__(PL_THREADS) void pl_bn_stats_kernel(const float *__
     if (threadIdx.x == 0) { atomicAdd(acc + 2 * c, s1); atomicAdd(acc + 2 * c + 1, s2); }
 }
 
-// stats[c] = mean, stats[C + c] = rstd, stats[2C + c] = unbiased variance (for the running estimate), stats[3C + c] = mean - pivot: the kernels
-// centre as (x - pivot) - (mean - pivot) — with |mean| >> std the fp32 mean itself is only good to a fraction of the std
+// stats[c] = mean, stats[C + c] = rstd, stats[2C + c] = unbiased variance (for the running estimate), stats[3C + c] = mean - pivot, stats[4C + c] = pivot: the
+// kernels centre as (x - pivot) - (mean - pivot) — with |mean| >> std the fp32 mean itself is only good to a fraction of the std
 __global__ void pl_bn_finish_kernel(const float *__restrict__ x, const float *__restrict__ acc, float *__restrict__ stats, int C, long N, long count, float eps)
 {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= C) return;
-    const float p = x[(long)c * N];
+    const float p = pl_bn_pivot(x, c, N);
     const float m1 = acc[2 * c] / (float)count, m2 = acc[2 * c + 1] / (float)count;
     float var = m2 - m1 * m1;
     var = var > 0.f ? var : 0.f;
@@ -68,6 +83,7 @@ __global__ void pl_bn_finish_kernel(const float *__restrict__ x, const float *__
     stats[C + c] = 1.f / sqrtf(var + eps);
     stats[2 * C + c] = count > 1 ? var * (float)count / (float)(count - 1) : var;
     stats[3 * C + c] = m1;
+    stats[4 * C + c] = p;
 }
 
 // y = (x - mean) rstd w + b
@@ -75,7 +91,7 @@ __global__ __launch_bounds__(PL_THREADS) void pl_bn_apply_kernel(const float *__
                                                                  const float *__restrict__ b, float *__restrict__ y, int C, long N)
 {
     const int plane = blockIdx.y, c = plane % C;
-    const float piv = x[(long)c * N], dm = stats[3 * C + c], sc = stats[C + c] * (w ? w[c] : 1.f), sh = b ? b[c] : 0.f;
+    const float piv = stats[4 * C + c], dm = stats[3 * C + c], sc = stats[C + c] * (w ? w[c] : 1.f), sh = b ? b[c] : 0.f;
     const float *xp = x + (long)plane * N;
     float *yp = y + (long)plane * N;
     const long e0 = (long)blockIdx.x * PL_CHUNK;
@@ -97,7 +113,7 @@ __global__ __launch_bounds__(PL_THREADS) void pl_bn_bwd_reduce_kernel(const floa
 {
     __shared__ float red[PL_THREADS];
     const int plane = blockIdx.y, c = plane % C;
-    const float piv = x[(long)c * N], dm = stats[3 * C + c], rstd = stats[C + c];
+    const float piv = stats[4 * C + c], dm = stats[3 * C + c], rstd = stats[C + c];
     const float *xp = x + (long)plane * N, *gp = g + (long)plane * N;
     const long e0 = (long)blockIdx.x * PL_RCHUNK;
     float s1 = 0.f, s2 = 0.f;
@@ -121,7 +137,7 @@ __global__ __launch_bounds__(PL_THREADS) void pl_bn_bwd_apply_kernel(const float
                                                                      float *__restrict__ gw, float *__restrict__ gb, int C, long N, long count)
 {
     const int plane = blockIdx.y, c = plane % C;
-    const float piv = x[(long)c * N], dm = stats[3 * C + c], rstd = stats[C + c];
+    const float piv = stats[4 * C + c], dm = stats[3 * C + c], rstd = stats[C + c];
     const float sg = acc[2 * c], sgx = acc[2 * c + 1];
     const float k0 = rstd * (w ? w[c] : 1.f), mg = sg / (float)count, mgx = sgx / (float)count;
     if (blockIdx.x == 0 && plane == c && threadIdx.x == 0) {

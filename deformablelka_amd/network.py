@@ -197,7 +197,8 @@ class InstanceNorm3d(nn.InstanceNorm3d):
 
     def forward(self, x):
         if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 5 and not self.affine and not self.track_running_stats
-                and not torch.is_autocast_enabled() and x.shape[0] * x.shape[1] <= 65535):   # (one grid row per (b, c) plane)
+                and not torch.is_autocast_enabled() and x.shape[0] * x.shape[1] <= 65535     # (one grid row per (b, c) plane)
+                and x[0, 0].numel() > 1):   # (one spatial element: the stock layer raises its ValueError)
             return super().forward(x)
         from . import nn_ops
         B, C = x.shape[:2]
@@ -213,7 +214,8 @@ class BatchNorm3d(nn.BatchNorm3d):
 
     def forward(self, x):
         if not (self.training and x.is_cuda and x.dtype == torch.float32 and x.dim() == 5 and not torch.is_autocast_enabled()
-                and (self.weight is None or self.weight.dtype == torch.float32) and x.shape[0] * x.shape[1] <= 65535):
+                and (self.weight is None or self.weight.dtype == torch.float32) and x.shape[0] * x.shape[1] <= 65535
+                and x.numel() > x.shape[1]):   # (one value per channel: the stock layer raises its ValueError, the kernels would return the bias)
             return super().forward(x)
         from . import nn_ops
         y, stats = nn_ops.batch_norm_train(x.contiguous(), self.weight, self.bias, self.eps)

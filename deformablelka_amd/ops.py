@@ -298,12 +298,23 @@ def gelu_backward(x, gy):
 # planar (NCDHW) plumbing of the full net: BatchNorm3d in training mode, 1x1x1 convs on few channels (csrc/planar_ops.hip)
 # ------------------------------------------------------------------------------------------------------------
 PLANAR_PW_CIN = (1, 2, 4, 8, 14, 16, 32)
+PLANAR_BN_STATS_ROWS = 5   # rows of the BatchNorm statistics tensor (include/dlka.h: dlka_batchnorm_planar_forward)
+
+
+def _planar_f32(name, *tensors):
+    """The planar BatchNorm kernels read fp32 contiguous memory: anything else is refused (dtype) or made contiguous (layout)."""
+    for t in tensors:
+        if t is not None and t.dtype != torch.float32:
+            raise RuntimeError(f"{name}: float32 tensors only, got {t.dtype}")
+    return [None if t is None else t.contiguous() for t in tensors]
 
 
 def batchnorm_planar_forward(x, weight, bias, eps=1e-5, out=None):
-    """x (B, C, *spatial) fp32 contiguous -> y, stats (4, C) = mean, rstd, unbiased variance, mean - pivot (batch statistics).
+    """x (B, C, *spatial) fp32 -> y, stats (PLANAR_BN_STATS_ROWS, C) = mean, rstd, unbiased variance, mean - pivot, pivot (batch statistics; the pivot is the
+    value the kernels centre on, see csrc/planar_ops.hip).
     out: a contiguous fp32 tensor of x's element count (any shape) that receives y instead of a fresh tensor of x's shape."""
-    L.require_device(x)
+    L.require_device(x, weight, bias)
+    x, weight, bias = _planar_f32("batchnorm_planar_forward", x, weight, bias)
     B, C = x.shape[:2]
     N = x[0, 0].numel()
     if out is None:
@@ -311,7 +322,7 @@ def batchnorm_planar_forward(x, weight, bias, eps=1e-5, out=None):
     else:
         assert out.is_contiguous() and out.numel() == x.numel() and out.dtype == x.dtype and out.device == x.device
         y = out
-    stats = torch.empty(4, C, dtype=torch.float32, device=x.device)
+    stats = torch.empty(PLANAR_BN_STATS_ROWS, C, dtype=torch.float32, device=x.device)
     scratch = torch.empty(2 * C, dtype=torch.float32, device=x.device)
     L.check(L.get_lib().dlka_batchnorm_planar_forward(L.ptr(x), L.ptr(weight), L.ptr(bias), L.ptr(stats), L.ptr(y), L.ptr(scratch), B, C, N, float(eps),
                                                       L.stream_ptr(x)), "batchnorm_planar_forward")
@@ -319,9 +330,13 @@ def batchnorm_planar_forward(x, weight, bias, eps=1e-5, out=None):
 
 
 def batchnorm_planar_backward(g, x, weight, stats, affine=True):
-    L.require_device(x, g)
+    """g, x (B, C, *spatial) fp32, stats as batchnorm_planar_forward returned it for this x -> gx, gw, gb (the latter two None without affine)."""
+    L.require_device(x, g, weight, stats)
+    g, x, weight, stats = _planar_f32("batchnorm_planar_backward", g, x, weight, stats)
     B, C = x.shape[:2]
     N = x[0, 0].numel()
+    if g.shape != x.shape or tuple(stats.shape) != (PLANAR_BN_STATS_ROWS, C):
+        raise RuntimeError(f"batchnorm_planar_backward: grad_out {tuple(g.shape)} / stats {tuple(stats.shape)} do not belong to x {tuple(x.shape)}")
     gx = torch.empty_like(x)
     gw = torch.empty(C, dtype=torch.float32, device=x.device) if affine else None
     gb = torch.empty(C, dtype=torch.float32, device=x.device) if affine else None

@@ -403,7 +403,8 @@ int dlka_channel_scale(const void *x, const void *mask, void *y, int B, int64_t 
 /* ---- planar (NCDHW) plumbing of the full D_LKA_Former --------------------------------------------------------------
  * nn.BatchNorm3d in TRAINING mode over fp32 [B][C][N] tensors (the UnetResBlock norms of encoder1 / decoder2 at full resolution,
  * 3D/d_lka_former/network_architecture/dynunet_block.py:66-80): y = (x - mean) rstd w + b with batch statistics;
- * stats = {mean[C], rstd[C], unbiased var[C], mean - x[0][c][0]} — 4*C floats; the caller updates its running estimates from rows 0 and 2;
+ * stats = {mean[C], rstd[C], unbiased var[C], mean - pivot[C], pivot[C]} — 5*C floats, written by forward and read by backward; the pivot is the value the
+ * sums are centred on, the median of five values of the channel's first plane; the caller updates its running estimates from rows 0 and 2;
  * w / b may be NULL; scratch: 2*C floats.
  * backward: gx fully overwritten, gw / gb (optional) = the affine gradients. */
 int dlka_batchnorm_planar_forward(const void *x, const void *w, const void *b, void *stats, void *y, void *scratch,
