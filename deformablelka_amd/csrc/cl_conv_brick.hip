@@ -422,28 +422,24 @@ bool cl_conv_brick3_supported(const IgemmArgs &a)
     return true;
 }
 
+// f(kernel, threads) for NT = NP / 32 column tiles (every: no selector given, for all three members); one row tile per wave at NT = 1, two beyond
+template <class F> static void brick3_family(F &&f, bool every = true, int NT = 0)
+{
+    dispatch_int<3, 1, 2>(NT, [&](auto nt) {
+        constexpr int N = DLKA_V(nt), MT = N == 1 ? 1 : 2;
+        f(cl_conv_brick3_kernel<N, MT>, 64 * (8 / MT) * N);
+    }, every);
+}
+
 int launch_cl_conv_brick3(const IgemmArgs &a, hipStream_t st)
 {
     if (!cl_conv_brick3_supported(a)) return DLKA_ERR_UNSUPPORTED;
     const int TD = (a.D & 1) ? 1 : 2, TH = 256 / (TD * a.W), NT = a.NP / 32;
     const size_t lds = (size_t)(TD + 2) * (TH + 2) * (a.W + 2) * BRICK3_ROW;
-#if !defined(HIPEMU)
     static std::atomic<uint64_t> attr_done{0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return DLKA_ERR_LAUNCH;
-    const uint64_t bit = 1ull << (dev & 63);
-    if (!(attr_done.load(std::memory_order_acquire) & bit)) {
-        const void *fns[3] = {reinterpret_cast<const void *>(cl_conv_brick3_kernel<1, 1>), reinterpret_cast<const void *>(cl_conv_brick3_kernel<2, 2>),
-                              reinterpret_cast<const void *>(cl_conv_brick3_kernel<3, 2>)};
-        for (int f = 0; f < 3; ++f)
-            if (hipFuncSetAttribute(fns[f], hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return DLKA_ERR_LAUNCH;
-        attr_done.fetch_or(bit, std::memory_order_release);
-    }
-#endif
+    if (prepare_large_lds(attr_done, [](auto set) { brick3_family([&](auto k, int) { set(k); }); }) != DLKA_OK) return DLKA_ERR_LAUNCH;
     dim3 grid(a.B * (a.D / TD) * (a.H / TH));
-    if (NT == 1) { auto k = cl_conv_brick3_kernel<1, 1>; DLKA_LAUNCH(k, grid, dim3(512), lds, st, a, TD, TH); }
-    else if (NT == 2) { auto k = cl_conv_brick3_kernel<2, 2>; DLKA_LAUNCH(k, grid, dim3(512), lds, st, a, TD, TH); }
-    else { auto k = cl_conv_brick3_kernel<3, 2>; DLKA_LAUNCH(k, grid, dim3(768), lds, st, a, TD, TH); }
+    brick3_family([&](auto k, int threads) { DLKA_LAUNCH(k, grid, dim3(threads), lds, st, a, TD, TH); }, false, NT);
     DLKA_CHECK_LAUNCH();
     g_conv_brick_launches.fetch_add(1, std::memory_order_relaxed);
     return DLKA_OK;
@@ -456,6 +452,16 @@ int cl_conv_brick_split(const IgemmArgs &a)
     return (cl_conv_brick_supported(a) && brick_tile(a, bt)) ? bt.csplit : 0;
 }
 
+// f(kernel) for the member that (NT, storage of `out`, row tiles per wave, waves) select; every (no selectors given): for all twelve
+template <class F> static void brick_family(F &&f, bool every = true, int NT = 0, bool out_bf16 = false, int mt = 0, int waves = 0)
+{
+    dispatch_act(out_bf16, [&](auto t) { dispatch_int<2, 1>(NT, [&](auto nt) {
+        dispatch_int<2, 0, 1>(mt == 2 ? 0 : waves == 4 ? 1 : 2, [&](auto c) {   // (waves, row tiles): 4 x 2, 4 x 1, 8 x 1
+            f(cl_conv_brick_kernel<DLKA_V(nt), DLKA_T(t), DLKA_V(c) == 2 ? 8 : 4, DLKA_V(c) == 0 ? 2 : 1>);
+        }, every);
+    }, every); }, every);
+}
+
 // DLKA_ERR_UNSUPPORTED: the caller takes cl_conv_wave_kernel / cl_igemm_kernel.
 int launch_cl_conv_brick(const IgemmArgs &a, hipStream_t st)
 {
@@ -465,32 +471,12 @@ int launch_cl_conv_brick(const IgemmArgs &a, hipStream_t st)
     const int NT = a.NP / 32;
     const int nwg = a.B * (a.D / bt.TD) * (a.H / bt.TH);
     const size_t lds = bt.lds;
-#if !defined(HIPEMU)
-    static std::atomic<uint64_t> attr_done{0};   // dynamic LDS above 64 KB: per function AND per device (cl_deform_bwd2.hip has the same pattern)
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return DLKA_ERR_LAUNCH;
-    const uint64_t bit = 1ull << (dev & 63);
-    if (!(attr_done.load(std::memory_order_acquire) & bit)) {
-#define DLKA_BRICK_FNS(WV, MTV) reinterpret_cast<const void *>(cl_conv_brick_kernel<1, float, WV, MTV>), reinterpret_cast<const void *>(cl_conv_brick_kernel<2, float, WV, MTV>), \
-                           reinterpret_cast<const void *>(cl_conv_brick_kernel<1, bf16_t, WV, MTV>), reinterpret_cast<const void *>(cl_conv_brick_kernel<2, bf16_t, WV, MTV>)
-        const void *fns[12] = {DLKA_BRICK_FNS(4, 1), DLKA_BRICK_FNS(8, 1), DLKA_BRICK_FNS(4, 2)};
-#undef DLKA_BRICK_FNS
-        for (int f = 0; f < 12; ++f)
-            if (hipFuncSetAttribute(fns[f], hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return DLKA_ERR_LAUNCH;
-        attr_done.fetch_or(bit, std::memory_order_release);
-    }
-#endif
+    static std::atomic<uint64_t> attr_done{0};
+    if (prepare_large_lds(attr_done, [](auto set) { brick_family(set); }) != DLKA_OK) return DLKA_ERR_LAUNCH;
     dim3 grid(nwg, bt.csplit), block(64 * bt.waves);
     if (bt.csplit > 1 && !a.out_zeroed && launch_zero(a.out, (size_t)a.M * a.Cout * 4, st) != DLKA_OK) return DLKA_ERR_LAUNCH;
-#define DLKA_BRICK_GO(NTV, TT)                                                                                                   \
-    {                                                                                                                            \
-        if (bt.mt == 2) { auto k = cl_conv_brick_kernel<NTV, TT, 4, 2>; DLKA_LAUNCH(k, grid, block, lds, st, a, bt.TD, bt.TH); }      \
-        else if (bt.waves == 4) { auto k = cl_conv_brick_kernel<NTV, TT, 4>; DLKA_LAUNCH(k, grid, block, lds, st, a, bt.TD, bt.TH); } \
-        else { auto k = cl_conv_brick_kernel<NTV, TT, 8>; DLKA_LAUNCH(k, grid, block, lds, st, a, bt.TD, bt.TH); }               \
-    }
-    if (a.act_bf16 && bt.csplit == 1) { if (NT == 1) DLKA_BRICK_GO(1, bf16_t) else DLKA_BRICK_GO(2, bf16_t) }   // (split: `out` is the caller's fp32 accumulation buffer)
-    else { if (NT == 1) DLKA_BRICK_GO(1, float) else DLKA_BRICK_GO(2, float) }
-#undef DLKA_BRICK_GO
+    // (split: `out` is the caller's fp32 accumulation buffer)
+    brick_family([&](auto k) { DLKA_LAUNCH(k, grid, block, lds, st, a, bt.TD, bt.TH); }, false, NT, a.act_bf16 && bt.csplit == 1, bt.mt, bt.waves);
     DLKA_CHECK_LAUNCH();
     g_conv_brick_launches.fetch_add(1, std::memory_order_relaxed);
     return DLKA_OK;

@@ -217,28 +217,27 @@ int launch_cl_conv_kw(int amode, int omode, const IgemmArgs &a, hipStream_t st)
     const int tiles = row_tiles * (nt_total / nt);
     const int kw = (nt > 1 || tiles * 4 >= 1024) ? 4 : 8;   // waves per tile: four where that fills the chip (16^3 and up); the 8^3 / 4^3 stages take eight
     dim3 grid(row_tiles, 1, nt_total / nt), block(64 * kw);
-#define DLKA_KW1(AM, OM, SP, TT, KWV, NTV) { auto k = cl_conv_kw_kernel<AM, OM, SP, KWV, NTV, TT>; DLKA_LAUNCH(k, grid, block, 0, st, a); }
-#define DLKA_KW(AM, OM, SP, TT)                      \
-    {                                                \
-        if (kw == 8) DLKA_KW1(AM, OM, SP, TT, 8, 1)  \
-        else if (nt == 1) DLKA_KW1(AM, OM, SP, TT, 4, 1) \
-        else if (nt == 2) DLKA_KW1(AM, OM, SP, TT, 4, 2) \
-        else if (nt == 3) DLKA_KW1(AM, OM, SP, TT, 4, 3) \
-        else DLKA_KW1(AM, OM, SP, TT, 4, 4)          \
-    }
+    // kernel<AM, OM, SP, waves per tile, column tiles, storage>: eight waves go with one column tile only
+    auto go = [&](auto am, auto om, auto sp, auto t) {
+        dispatch_int<4, 1, 2, 3>(nt, [&](auto n) { dispatch_bool(kw == 8, [&](auto w8) {
+            if constexpr (!DLKA_V(w8) || DLKA_V(n) == 1) {
+                auto k = cl_conv_kw_kernel<DLKA_V(am), DLKA_V(om), DLKA_V(sp), DLKA_V(w8) ? 8 : 4, DLKA_V(n), DLKA_T(t)>;
+                DLKA_LAUNCH(k, grid, block, 0, st, a);
+            }
+        }); });
+    };
+    constexpr int_c<0> c0; constexpr int_c<1> c1; constexpr int_c<2> c2; constexpr int_c<3> c3;
     if (a.act_bf16) {
-        if (amode == 0) DLKA_KW(0, 1, 2, bf16_t)
-        else DLKA_KW(2, 0, 2, bf16_t)
+        if (amode == 0) go(c0, c1, c2, type_tag<bf16_t>{});
+        else go(c2, c0, c2, type_tag<bf16_t>{});
     } else if (a.split_bf16 == 3) {
-        if (omode == 1) DLKA_KW(0, 1, 3, float)
-        else DLKA_KW(0, 0, 3, float)
+        if (omode == 1) go(c0, c1, c3, type_tag<float>{});
+        else go(c0, c0, c3, type_tag<float>{});
     } else {
-        if (amode == 0 && omode == 0) DLKA_KW(0, 0, 2, float)
-        else if (amode == 0) DLKA_KW(0, 1, 2, float)
-        else DLKA_KW(2, 0, 2, float)
+        if (amode == 0 && omode == 0) go(c0, c0, c2, type_tag<float>{});
+        else if (amode == 0) go(c0, c1, c2, type_tag<float>{});
+        else go(c2, c0, c2, type_tag<float>{});
     }
-#undef DLKA_KW
-#undef DLKA_KW1
     DLKA_CHECK_LAUNCH();
     g_conv_kw_launches.fetch_add(1, std::memory_order_relaxed);
     return DLKA_OK;

@@ -188,60 +188,35 @@ __global__ __launch_bounds__(256) void cl_conv_wave_kernel(IgemmArgs p)
 // Split-operand convs with K > 1, epilogues 0 and 3.  Returns DLKA_ERR_UNSUPPORTED for anything else (the caller then uses cl_igemm_kernel).
 int launch_cl_conv_wave(int amode, int omode, const IgemmArgs &a, int splits, hipStream_t st)
 {
-    constexpr bool off = false;
-    if (off || a.K <= 1 || (a.split_bf16 != 2 && a.split_bf16 != 3) || (a.epi != 0 && a.epi != 3)) return DLKA_ERR_UNSUPPORTED;
+    if (a.K <= 1 || (a.split_bf16 != 2 && a.split_bf16 != 3) || (a.epi != 0 && a.epi != 3)) return DLKA_ERR_UNSUPPORTED;
     if (amode != 0 && amode != 2) return DLKA_ERR_UNSUPPORTED;
     if ((long)a.K * (a.CinP / 32) * (a.split_bf16 == 3 ? 48 : 32) * a.NP * 4 >= (1l << 31)) return DLKA_ERR_UNSUPPORTED;   // 32-bit buffer offsets
     const int NT_total = a.NP / 32;
-    // column tiles per wave / prefetch depth.  DLKA_CONV_WAVE_CFG=<NT><DEPTH> overrides for tuning (e.g. 32 = NT 3, depth 2).
-    constexpr int cfg = 0;
-    int NT = 1, DEPTH = 2;
-    if (cfg) { NT = cfg / 10; DEPTH = cfg % 10; }
-    else {
-        // Measured (profiles/archive/r01w_conv_wave_cfg.txt, us, this kernel vs cl_igemm_kernel): offset conv forward (three-term, 96 columns) 128 vs 81 at
-        // C=32/32^3 — one column tile per wave re-reads the A rows three times through the "lane = row" loads, which cost one L1 access per row —
-        // but 46 vs 52 at C=64/16^3 and 28 vs 39 at C=128/8^3; data gradient (two-term) 88 vs 104 at C=32/32^3, equal elsewhere.  A deeper
-        // register ring (3 stages) changed nothing: these launches are not waiting on latency.
-        if (a.split_bf16 == 3 && a.M > 16384) return DLKA_ERR_UNSUPPORTED;
-        if (a.split_bf16 == 2 && NT_total != 1 && !a.act_bf16) return DLKA_ERR_UNSUPPORTED;
-        // bf16 activations: the offset-predict conv forward only, where the fp32 path takes this kernel too (its three-term variant)
-        if (a.act_bf16 && !(amode == 0 && omode == 1 && a.split_bf16 == 2 && a.M <= 16384)) return DLKA_ERR_UNSUPPORTED;
-    }
-    if (a.act_bf16 && (NT != 1 || DEPTH != 2)) return DLKA_ERR_UNSUPPORTED;
-    if (NT < 1 || NT > 3 || NT_total % NT || (DEPTH != 2 && DEPTH != 3)) return DLKA_ERR_UNSUPPORTED;
-    dim3 grid(cdiv(a.M, 128), splits, NT_total / NT), block(256);
+    // One column tile per wave, a register ring of depth 2 (the kernel's NT and DEPTH).
+    // Measured (profiles/archive/r01w_conv_wave_cfg.txt, us, this kernel vs cl_igemm_kernel): offset conv forward (three-term, 96 columns) 128 vs 81 at
+    // C=32/32^3 — one column tile per wave re-reads the A rows three times through the "lane = row" loads, which cost one L1 access per row —
+    // but 46 vs 52 at C=64/16^3 and 28 vs 39 at C=128/8^3; data gradient (two-term) 88 vs 104 at C=32/32^3, equal elsewhere.  A deeper
+    // register ring (3 stages) changed nothing: these launches are not waiting on latency.
+    if (a.split_bf16 == 3 && a.M > 16384) return DLKA_ERR_UNSUPPORTED;
+    if (a.split_bf16 == 2 && NT_total != 1 && !a.act_bf16) return DLKA_ERR_UNSUPPORTED;
+    // bf16 activations: the offset-predict conv forward only, where the fp32 path takes this kernel too (its three-term variant)
+    if (a.act_bf16 && !(amode == 0 && omode == 1 && a.split_bf16 == 2 && a.M <= 16384)) return DLKA_ERR_UNSUPPORTED;
+    dim3 grid(cdiv(a.M, 128), splits, NT_total), block(256);
     IgemmArgs ax = a;
     ax.xcd_nx = 0;
     if (xcd_swizzle_enabled() && grid.x >= (unsigned)xcd_min_blocks()) { ax.xcd_nx = (int)grid.x; grid.x = xcd_grid(ax.xcd_nx); }
-#define DLKA_CW(AM, OM, NTV, SP, DP)                                        \
-    {                                                                       \
-        auto k = cl_conv_wave_kernel<AM, OM, NTV, SP, DP>;                  \
-        DLKA_LAUNCH(k, grid, block, 0, st, ax);                      \
-    }
-#define DLKA_CW_NT(AM, OM, SP)                                              \
-    {                                                                       \
-        if (NT == 1 && DEPTH == 3) DLKA_CW(AM, OM, 1, SP, 3)                \
-        else if (NT == 1) DLKA_CW(AM, OM, 1, SP, 2)                         \
-        else if (NT == 2 && DEPTH == 3) DLKA_CW(AM, OM, 2, SP, 3)           \
-        else if (NT == 2) DLKA_CW(AM, OM, 2, SP, 2)                         \
-        else if (DEPTH == 2) DLKA_CW(AM, OM, 3, SP, 2)                      \
-        else return DLKA_ERR_UNSUPPORTED;                                   \
-    }
-    if (a.act_bf16) {
-        auto k = cl_conv_wave_kernel<0, 1, 1, 2, 2, bf16_t>;
-        DLKA_LAUNCH(k, grid, block, 0, st, ax);
-    } else if (a.split_bf16 == 3) {
-        if (amode == 0 && omode == 1) DLKA_CW_NT(0, 1, 3)
-        else if (amode == 0 && omode == 0) DLKA_CW_NT(0, 0, 3)
+    auto go = [&](auto k) { DLKA_LAUNCH(k, grid, block, 0, st, ax); };
+    if (a.act_bf16) go(cl_conv_wave_kernel<0, 1, 1, 2, 2, bf16_t>);
+    else if (a.split_bf16 == 3) {
+        if (amode == 0 && omode == 1) go(cl_conv_wave_kernel<0, 1, 1, 3, 2>);
+        else if (amode == 0 && omode == 0) go(cl_conv_wave_kernel<0, 0, 1, 3, 2>);
         else return DLKA_ERR_UNSUPPORTED;
     } else {
-        if (amode == 0 && omode == 0) DLKA_CW_NT(0, 0, 2)
-        else if (amode == 0 && omode == 1) DLKA_CW_NT(0, 1, 2)
-        else if (amode == 2 && omode == 0) DLKA_CW_NT(2, 0, 2)
+        if (amode == 0 && omode == 0) go(cl_conv_wave_kernel<0, 0, 1, 2, 2>);
+        else if (amode == 0 && omode == 1) go(cl_conv_wave_kernel<0, 1, 1, 2, 2>);
+        else if (amode == 2 && omode == 0) go(cl_conv_wave_kernel<2, 0, 1, 2, 2>);
         else return DLKA_ERR_UNSUPPORTED;
     }
-#undef DLKA_CW_NT
-#undef DLKA_CW
     DLKA_CHECK_LAUNCH();
     return DLKA_OK;
 }

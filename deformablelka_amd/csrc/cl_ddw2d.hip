@@ -574,12 +574,8 @@ int launch_cl_ddw2d_fwd(const DwArgs2d &d, hipStream_t st)
     if (per == 3 && mblocks * (nch / 3) < 512) per = 1;
     dim3 grid(mblocks, nch / per), block(256);
     if (xcd_swizzle_enabled() && mblocks >= xcd_min_blocks()) { a.xcd_nx = mblocks; grid.x = xcd_grid(mblocks); }
-#define DLKA_DDW_F(N_) case N_: { auto k = cl_ddw2d_fwd_kernel<N_>; DLKA_LAUNCH(k, grid, block, 0, st, a); } break;
-    switch (per) {
-        DLKA_DDW_F(1) DLKA_DDW_F(2) DLKA_DDW_F(3) DLKA_DDW_F(4) DLKA_DDW_F(6) DLKA_DDW_F(8) DLKA_DDW_F(12)
-        default: return DLKA_ERR_UNSUPPORTED;
-    }
-#undef DLKA_DDW_F
+    if (!dispatch_menu<1, 2, 3, 4, 6, 8, 12>(per, [&](auto n) { auto k = cl_ddw2d_fwd_kernel<DLKA_V(n)>; DLKA_LAUNCH(k, grid, block, 0, st, a); }))
+        return DLKA_ERR_UNSUPPORTED;
     DLKA_CHECK_LAUNCH();
     return DLKA_OK;
 }
@@ -605,13 +601,10 @@ int launch_cl_ddw2d_bwd(const DwArgs2d &d, float *gw, hipStream_t st, hipStream_
         grid.y = cdiv(a.K, a.tpg);
     }
     if (xcd_swizzle_enabled() && nblocks >= xcd_min_blocks()) { a.xcd_nx = nblocks; grid.x = xcd_grid(nblocks); }
-#define DLKA_DDW_B(N_) case N_: { if (d.act_bf16) { auto k = cl_ddw2d_bwd_kernel<N_, bf16_t>; DLKA_LAUNCH(k, grid, block, 0, st, a); }   \
-                                  else { auto k = cl_ddw2d_bwd_kernel<N_, float>; DLKA_LAUNCH(k, grid, block, 0, st, a); } } break;
-    switch (nch) {
-        DLKA_DDW_B(1) DLKA_DDW_B(2) DLKA_DDW_B(3) DLKA_DDW_B(4) DLKA_DDW_B(6) DLKA_DDW_B(8) DLKA_DDW_B(12)
-        default: return DLKA_ERR_UNSUPPORTED;
-    }
-#undef DLKA_DDW_B
+    if (!dispatch_menu<1, 2, 3, 4, 6, 8, 12>(nch, [&](auto n) { dispatch_act(d.act_bf16, [&](auto t) {
+            auto k = cl_ddw2d_bwd_kernel<DLKA_V(n), DLKA_T(t)>; DLKA_LAUNCH(k, grid, block, 0, st, a);
+        }); }))
+        return DLKA_ERR_UNSUPPORTED;
     DLKA_CHECK_LAUNCH();
     DLKA_LAUNCH(cl_ddw2d_fold_kernel, dim3(cdiv(a.K * a.C, 32)), dim3(256), 0, st, (const float *)a.part, gw, nblocks, a.K, a.C);
     DLKA_CHECK_LAUNCH();
@@ -654,22 +647,12 @@ int launch_cl_ddw2d_bwd(const DwArgs2d &d, float *gw, hipStream_t st, hipStream_
         }
         const size_t lds = lds_bytes(TH, TW);
         if (lds > 150 * 1024) return DLKA_ERR_UNSUPPORTED;
-#if !defined(HIPEMU)
-        static std::atomic<uint64_t> attr_done{0};   // dynamic LDS above 64 KB: per function and per device
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess) return DLKA_ERR_LAUNCH;
-        const uint64_t bit = 1ull << (dev & 63);
-        if (!(attr_done.load(std::memory_order_acquire) & bit)) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void *>(cl_ddw2d_gx_kernel<float>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-                hipFuncSetAttribute(reinterpret_cast<const void *>(cl_ddw2d_gx_kernel<bf16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-                return DLKA_ERR_LAUNCH;
-            attr_done.fetch_or(bit, std::memory_order_release);
-        }
-#endif
         const int ntx = cdiv(a.W, TW), nty = cdiv(a.H, TH);
         dim3 ggrid(a.B * nty * ntx, a.C / GX2_CS);
-        if (d.act_bf16) { auto k = cl_ddw2d_gx_kernel<bf16_t>; DLKA_LAUNCH(k, ggrid, dim3(256), lds, gst, a, TH, TW, ntx, nty, reach_y, reach_x); }
-        else { auto k = cl_ddw2d_gx_kernel<float>; DLKA_LAUNCH(k, ggrid, dim3(256), lds, gst, a, TH, TW, ntx, nty, reach_y, reach_x); }
+        auto gx_family = [](auto &&f, bool every = true, bool bf16 = false) { dispatch_act(bf16, [&](auto t) { f(cl_ddw2d_gx_kernel<DLKA_T(t)>); }, every); };
+        static std::atomic<uint64_t> attr_done{0};
+        if (prepare_large_lds(attr_done, [&](auto set) { gx_family(set); }) != DLKA_OK) return DLKA_ERR_LAUNCH;
+        gx_family([&](auto k) { DLKA_LAUNCH(k, ggrid, dim3(256), lds, gst, a, TH, TW, ntx, nty, reach_y, reach_x); }, false, d.act_bf16);
         DLKA_CHECK_LAUNCH();
     }
     return DLKA_OK;

@@ -586,8 +586,6 @@ struct GxGeom {
     int ngroups;            // ceil(K / TG)
     int resident;           // all tap groups' weight tiles fit in LDS next to the window
     int xcd_nx;             // > 0: blockIdx.x is mapped through xcd_item() (set by the launcher)
-    int item_grid;          // 1: 1-D grid over (brick, slice) items; 0: x = brick, y = slice
-    int tap_far;            // 1: half-waves take taps 16 apart (K <= 32 = 4 groups of 8), see gx_tap()
     float fx_magic;         // 1.5 * 2^23 (second-generation kernel: rounding constant, passed in a register on purpose)
     float fx_lim;           // fixed-point window: largest scaled magnitude of one contribution, R*K * (fx_lim + 1/2) < 2^31 (R = rows of a
                             // brick, K = taps), see the kernel
@@ -596,12 +594,9 @@ struct GxGeom {
 // MFMA row t8 of tap group grp <-> tap.  The two half-waves scatter rows t8 = 2*r4 and 2*r4 + 1 in the same instruction; with consecutive
 // taps there (tk, tk + 1) lane (j, 1) and lane (j + 1, 0) aim at the SAME window cell whenever their offsets floor alike — the
 // "consecutive + 0/1 jitter" pattern that costs 21 instead of 9.4 cycles per ds_add_f64 in isolation (profiles/archive/r01e_lds_f64_patterns.txt).
-// tap_far pairs tap x with tap x + 16 instead (another d-plane of the window).  In the real kernel it did NOT pay (390 vs 370 us at 32^3):
-// the LDS unit serves the half-waves in separate passes, and neighbouring taps share offset / window cache lines.  Kept as an A/B knob.
-__device__ __host__ __forceinline__ int gx_tap(int grp, int t8, int tap_far)
-{
-    return tap_far ? (t8 & 1) * 16 + grp * 4 + (t8 >> 1) : grp * TG + t8;
-}
+// Pairing tap x with tap x + 16 instead (another d-plane of the window; "far taps first") did NOT pay in the real kernel (390 vs 370 us at 32^3,
+// slower): the LDS unit serves the half-waves in separate passes, and neighbouring taps share offset / window cache lines.
+__device__ __host__ __forceinline__ int gx_tap(int grp, int t8) { return grp * TG + t8; }
 
 __device__ __host__ __forceinline__ void gx_window(int b0, int bsz, int size, int &lo, int &len)
 {
@@ -630,15 +625,11 @@ __global__ __launch_bounds__(512, FX ? 4 : 2) void cl_deform_gx_kernel(DeformBwd
     float *Bs = reinterpret_cast<float *>(smem + (size_t)(gg.wvox_max + 64) * (FX ? CS / 2 : CS) * sizeof(double));   // [CoutP][32]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwaves = blockDim.x >> 6;
     const int j = lane & 31, h = lane >> 5;
-    // XCD-aware order: an XCD owns a contiguous range of bricks (they share halo rows of grad_out / offsets); optionally (item_grid) a 1-D grid
-    // over (brick, slice) items with the slices of a brick adjacent
-    int item;
-    if (gg.item_grid) item = gg.xcd_nx > 0 ? xcd_item((int)blockIdx.x, gg.xcd_nx) : (int)blockIdx.x;
-    else {   // brick-major 2-D grid (x = brick, XCD-swizzled; y = slice)
-        const int bk = DLKA_XCD_BX(gg.xcd_nx);
-        item = bk < 0 ? -1 : bk * gg.nslices + (int)blockIdx.y;
-    }
-    if (item < 0) return;
+    // XCD-aware order: an XCD owns a contiguous range of bricks (they share halo rows of grad_out / offsets).  Brick-major 2-D grid:
+    // x = brick, XCD-swizzled; y = slice
+    const int bk = DLKA_XCD_BX(gg.xcd_nx);
+    if (bk < 0) return;
+    const int item = bk * gg.nslices + (int)blockIdx.y;
     const int brick = item / gg.nslices;
     int bid = brick;
     const int bw_i = bid % gg.nbw; bid /= gg.nbw;
@@ -661,7 +652,7 @@ __global__ __launch_bounds__(512, FX ? 4 : 2) void cl_deform_gx_kernel(DeformBwd
     // A operand tile of group grp: Bs[co][t8*4 + c4] = W[co][slice*4 + c4][tap = grp*8 + t8]   (wp[tap][co][ci], zero beyond K)
     auto stage_weights = [&](int grp, float *dstB) {
         for (int e = tid; e < p.CoutP * TG; e += blockDim.x) {
-            const int co = e / TG, t8 = e - co * TG, tap = gx_tap(grp, t8, gg.tap_far);
+            const int co = e / TG, t8 = e - co * TG, tap = gx_tap(grp, t8);
             f32x4 val = {0.f, 0.f, 0.f, 0.f};
             if (tap < p.K) val = *reinterpret_cast<const f32x4 *>(p.wp + ((long)tap * p.CoutP + co) * p.C + slice * CS);
             reinterpret_cast<f32x4 *>(dstB)[e] = val;
@@ -693,7 +684,7 @@ __global__ __launch_bounds__(512, FX ? 4 : 2) void cl_deform_gx_kernel(DeformBwd
         float offv[4][3];
 #pragma unroll
         for (int r4 = 0; r4 < 4; ++r4) {
-            const int tq = gx_tap(grp, 2 * r4 + h, gg.tap_far);
+            const int tq = gx_tap(grp, 2 * r4 + h);
             const float *op = p.off + ((long)b * 3 * p.K + 3 * (tq < p.K ? tq : 0)) * p.N + v;
             offv[r4][0] = op[0]; offv[r4][1] = op[p.N]; offv[r4][2] = op[2 * (long)p.N];
         }
@@ -724,7 +715,7 @@ __global__ __launch_bounds__(512, FX ? 4 : 2) void cl_deform_gx_kernel(DeformBwd
             // juggling per corner.  Corners inside the volume but outside the window (rare: |offset| > HALO) take global atomics.
 #pragma unroll
         for (int r4 = 0; r4 < 4; ++r4) {
-            const int tap = gx_tap(grp, 2 * r4 + h, gg.tap_far);
+            const int tap = gx_tap(grp, 2 * r4 + h);
             if (!ok || tap >= p.K) continue;
             int ti, tj, tk;
             if (p.kw == 3 && p.kh == 3) { ti = tap / 9; const int rr = tap - 9 * ti; tj = rr / 3; tk = rr - 3 * tj; }   // uniform
@@ -1323,18 +1314,13 @@ static GxGeom pick_gx_geom(const DeformBwdArgs &a)
     GxGeom g;
     // Bricks are long along W: the 32 voxels of a wave tile are then consecutive in w, and with spatially smooth offsets
     // their corner cells are consecutive fp64 cells of the window — distinct LDS banks (a cubic 8x8x8 brick puts 4 short
-    // w-rows in a tile, whose cells collide).  DLKA_GX_BRICK=cube restores the cubic shape for A/B runs.
-    constexpr bool cube = false;
-    if (cube) {
-        g.bd = a.D < 8 ? a.D : 8; g.bh = a.H < 8 ? a.H : 8; g.bw = a.W < 8 ? a.W : 8;
-    } else {
-        g.bw = a.W < 32 ? a.W : 32;
-        g.bh = a.H < 4 ? a.H : 4;
-        int rest = 512 / (g.bw * g.bh);
-        if (rest < 1) rest = 1;
-        g.bd = a.D < rest ? a.D : rest;
-        if (g.bd > 8) g.bd = 8;
-    }
+    // w-rows in a tile, whose cells collide).
+    g.bw = a.W < 32 ? a.W : 32;
+    g.bh = a.H < 4 ? a.H : 4;
+    int rest = 512 / (g.bw * g.bh);
+    if (rest < 1) rest = 1;
+    g.bd = a.D < rest ? a.D : rest;
+    if (g.bd > 8) g.bd = 8;
     g.nslices = a.C / CS;
     g.ngroups = cdiv(a.K, TG);
     auto blocks = [&]() { return (long)a.B * cdiv(a.D, g.bd) * cdiv(a.H, g.bh) * cdiv(a.W, g.bw) * g.nslices; };
@@ -1371,6 +1357,20 @@ int cl_deform_goff_ccsplit(const DeformBwdArgs &a)
     return cdiv(ncc, cdiv(ncc, split));
 }
 
+// The grad_input scatter kernels, all of which take the > 64 KB window: f(kernel) for the member that the selectors name, or (every: no
+// selectors given) for all 28 of them.  win: row of GX_FX2_WIN for the second-generation kernel, < 0 = first generation.
+constexpr int GX_FX2_WIN[2][3] = {{18, 10, 14}, {34, 10, 10}};   // window shapes SW, SH, SD, in the order they are tried
+template <class F> static void gx_family(F &&f, bool every = true, int win = 0, bool b16 = false, bool act_bf16 = false, int nk = 0, bool fixed = false)
+{
+    if (every || win < 0)
+        dispatch_bool(fixed, [&](auto fx) { dispatch_act(act_bf16, [&](auto t) { f(cl_deform_gx_kernel<DLKA_V(fx), DLKA_T(t)>); }, every); }, every);
+    if (every || win >= 0)
+        dispatch_int<1, 0>(win, [&](auto w) { dispatch_int<0, 1, 2>(nk, [&](auto n) { dispatch_act(act_bf16, [&](auto t) { dispatch_bool(b16, [&](auto sp) {
+            constexpr const int *s = GX_FX2_WIN[DLKA_V(w)];
+            f(cl_deform_gx_fx2_kernel<s[0], s[1], s[2], DLKA_T(t), DLKA_V(n), DLKA_V(sp)>);
+        }, every); }, every); }, every); }, every);
+}
+
 int launch_cl_deform_bwd2(const DeformBwdArgs &a, float *scratch, hipStream_t st)
 {
     if (a.C % 32 || a.CoutP % 32) return DLKA_ERR_UNSUPPORTED;
@@ -1383,6 +1383,7 @@ int launch_cl_deform_bwd2(const DeformBwdArgs &a, float *scratch, hipStream_t st
         const int tpb = cdiv(a.K, tsplit);
         tsplit = cdiv(a.K, tpb);
         const int nkc = a.CoutP / 32;
+        const bool samp = a.samp != nullptr;
         // (the first "lane = voxel" gather kernel, 225-250 us against 150 at 32^3, was removed in round 2)
         const int ccsplit = cl_deform_goff_ccsplit(a);
         DeformBwdArgs ag = a;
@@ -1403,13 +1404,11 @@ int launch_cl_deform_bwd2(const DeformBwdArgs &a, float *scratch, hipStream_t st
                 dim3 grid16(mb16), block16(64 * WV);
                 ag.xcd_nx = 0;
                 if (xcd_swizzle_enabled() && mb16 >= xcd_min_blocks()) { ag.xcd_nx = mb16; grid16.x = xcd_grid(mb16); }
-#define DLKA_G16(TT, SS) { auto k = cl_deform_goff16_kernel<TT, SS, WV, 3>; DLKA_LAUNCH(k, grid16, block16, 0, st, ag); }
-#define DLKA_G16B(SS) { auto k = cl_deform_goff16_kernel<bf16_t, SS, WV, 3, true>; DLKA_LAUNCH(k, grid16, block16, 0, st, ag); }
-                if (a.act_bf16 && a.wp16) { if (a.samp) DLKA_G16B(true) else DLKA_G16B(false) }   // Col on the bf16 matrix cores
-                else if (a.act_bf16) { if (a.samp) DLKA_G16(bf16_t, true) else DLKA_G16(bf16_t, false) }
-                else { if (a.samp) DLKA_G16(float, true) else DLKA_G16(float, false) }
-#undef DLKA_G16
-#undef DLKA_G16B
+                auto go16 = [&](auto k) { DLKA_LAUNCH(k, grid16, block16, 0, st, ag); };
+                dispatch_bool(samp, [&](auto s) {
+                    if (a.act_bf16 && a.wp16) go16(cl_deform_goff16_kernel<bf16_t, DLKA_V(s), WV, 3, true>);   // Col on the bf16 matrix cores
+                    else dispatch_act(a.act_bf16, [&](auto t) { go16(cl_deform_goff16_kernel<DLKA_T(t), DLKA_V(s), WV, 3>); });
+                });
                 DLKA_CHECK_LAUNCH();
                 done16 = true;
             }
@@ -1421,35 +1420,18 @@ int launch_cl_deform_bwd2(const DeformBwdArgs &a, float *scratch, hipStream_t st
         }
         if (!done16) {
             // storing variant: grad_out rows in registers only at Cout = 32 / fp32 (measured at 32^3: 179 vs 186 us; bf16 149 vs 155 us the other way)
-#define DLKA_GOFF2(NK, TT)                                                                                                           \
-    {                                                                                                                                \
-        if (a.samp && (NK) == 1 && sizeof(TT) == 4) { auto k = cl_deform_goff2_kernel<1, TT, true>; DLKA_LAUNCH(k, grid, block, 0, st, ag, tpb); } \
-        else if (a.samp) { auto k = cl_deform_goff2_kernel<0, TT, true>; DLKA_LAUNCH(k, grid, block, 0, st, ag, tpb); }       \
-        else { auto k = cl_deform_goff2_kernel<NK, TT, false>; DLKA_LAUNCH(k, grid, block, 0, st, ag, tpb); }                 \
-    }
-#define DLKA_GOFF2_B16(NK)                                                                                                           \
-    {                                                                                                                                \
-        if (a.samp) { auto k = cl_deform_goff2_kernel<NK, bf16_t, true, true>; DLKA_LAUNCH(k, grid, block, 0, st, ag, tpb); }        \
-        else { auto k = cl_deform_goff2_kernel<NK, bf16_t, false, true>; DLKA_LAUNCH(k, grid, block, 0, st, ag, tpb); }              \
-    }
-#define DLKA_GOFF2_SPL(NK)                                                                                                           \
-    {                                                                                                                                \
-        if (a.samp) { auto k = cl_deform_goff2_kernel<NK, float, true, true>; DLKA_LAUNCH(k, grid, block, 0, st, ag, tpb); }         \
-        else { auto k = cl_deform_goff2_kernel<NK, float, false, true>; DLKA_LAUNCH(k, grid, block, 0, st, ag, tpb); }               \
-    }
-            if (a.act_bf16 && a.wp16) {   // Col on the bf16 matrix cores (two-term weight records, raw grad_out words)
-                if (nkc == 1) DLKA_GOFF2_B16(1) else if (nkc == 2) DLKA_GOFF2_B16(2) else DLKA_GOFF2_B16(0)
-            }
-            else if (a.wp16) {            // ... fp32 rows, two-term split (rows in registers at one chunk only: the split doubles them)
-                if (nkc == 1) DLKA_GOFF2_SPL(1) else DLKA_GOFF2_SPL(0)
-            }
-            else if (a.act_bf16) {
-                if (nkc == 1) DLKA_GOFF2(1, bf16_t) else if (nkc == 2) DLKA_GOFF2(2, bf16_t) else DLKA_GOFF2(0, bf16_t)
-            }
-            else if (nkc == 1) DLKA_GOFF2(1, float) else if (nkc == 2) DLKA_GOFF2(2, float) else DLKA_GOFF2(0, float)
-#undef DLKA_GOFF2
-#undef DLKA_GOFF2_B16
-#undef DLKA_GOFF2_SPL
+            auto go = [&](auto k) { DLKA_LAUNCH(k, grid, block, 0, st, ag, tpb); };
+            if (a.act_bf16 && a.wp16)     // Col on the bf16 matrix cores (two-term weight records, raw grad_out words)
+                dispatch_int<0, 1, 2>(nkc, [&](auto nk) { dispatch_bool(samp, [&](auto s) { go(cl_deform_goff2_kernel<DLKA_V(nk), bf16_t, DLKA_V(s), true>); }); });
+            else if (a.wp16)              // ... fp32 rows, two-term split (rows in registers at one chunk only: the split doubles them)
+                dispatch_int<0, 1>(nkc, [&](auto nk) { dispatch_bool(samp, [&](auto s) { go(cl_deform_goff2_kernel<DLKA_V(nk), float, DLKA_V(s), true>); }); });
+            else
+                dispatch_act(a.act_bf16, [&](auto t) { dispatch_int<0, 1, 2>(nkc, [&](auto nk) {
+                    using T = DLKA_T(t);
+                    if (samp && DLKA_V(nk) == 1 && sizeof(T) == 4) go(cl_deform_goff2_kernel<1, T, true>);
+                    else if (samp) go(cl_deform_goff2_kernel<0, T, true>);
+                    else go(cl_deform_goff2_kernel<DLKA_V(nk), T, false>);
+                }); });
         }
         DLKA_CHECK_LAUNCH();
     }
@@ -1476,91 +1458,32 @@ int launch_cl_deform_bwd2(const DeformBwdArgs &a, float *scratch, hipStream_t st
         const size_t lds_win = 16 + (size_t)(g.wvox_max + 64) * (fixed ? CS / 2 : CS) * sizeof(double);
         const size_t lds_all = lds_win + (size_t)g.ngroups * a.CoutP * 32 * sizeof(float);
         gl_.resident = (lds_all <= 150 * 1024 && (a.CoutP <= 128 || !fixed)) ? 1 : 0;   // (Cout = 256: resident weights, grad_out rows re-read per item)
-        constexpr bool far_taps = false;   // (measured: 390 vs 370 us at 32^3 — slower)
-        gl_.tap_far = (far_taps && g.ngroups == 4) ? 1 : 0;
         const size_t lds = gl_.resident ? lds_all : lds_win + (size_t)a.CoutP * 32 * sizeof(float);
         if (lds > 160 * 1024) return DLKA_ERR_UNSUPPORTED;
-#if !defined(HIPEMU)
-        // dynamic LDS above 64 KB has to be enabled per function AND per device (a process may drive several GPUs,
-        // e.g. nn.DataParallel in the reference trainers); one bit per device, set after the attribute call succeeded
         static std::atomic<uint64_t> attr_done{0};
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess) return DLKA_ERR_LAUNCH;
-        const uint64_t bit = 1ull << (dev & 63);
-        if (!(attr_done.load(std::memory_order_acquire) & bit)) {
-#define DLKA_FX2_FNS(SWv, SHv, SDv, NK) reinterpret_cast<const void *>(cl_deform_gx_fx2_kernel<SWv, SHv, SDv, float, NK>), reinterpret_cast<const void *>(cl_deform_gx_fx2_kernel<SWv, SHv, SDv, bf16_t, NK>), reinterpret_cast<const void *>(cl_deform_gx_fx2_kernel<SWv, SHv, SDv, bf16_t, NK, true>), reinterpret_cast<const void *>(cl_deform_gx_fx2_kernel<SWv, SHv, SDv, float, NK, true>)
-            const void *fns[28] = {reinterpret_cast<const void *>(cl_deform_gx_kernel<false>), reinterpret_cast<const void *>(cl_deform_gx_kernel<true>),
-                                   reinterpret_cast<const void *>(cl_deform_gx_kernel<false, bf16_t>), reinterpret_cast<const void *>(cl_deform_gx_kernel<true, bf16_t>),
-                                   DLKA_FX2_FNS(18, 10, 14, 0), DLKA_FX2_FNS(18, 10, 14, 1), DLKA_FX2_FNS(18, 10, 14, 2),
-                                   DLKA_FX2_FNS(34, 10, 10, 0), DLKA_FX2_FNS(34, 10, 10, 1), DLKA_FX2_FNS(34, 10, 10, 2)};
-#undef DLKA_FX2_FNS
-            for (int f = 0; f < 28; ++f)
-                if (hipFuncSetAttribute(fns[f], hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return DLKA_ERR_LAUNCH;
-            attr_done.fetch_or(bit, std::memory_order_release);
-        }
-#endif
+        if (prepare_large_lds(attr_done, [](auto set) { gx_family(set); }) != DLKA_OK) return DLKA_ERR_LAUNCH;
         const int bricks = a.B * g.nbd * g.nbh * g.nbw;
-        const int items = bricks * g.nslices;
-        // A/B switch.  The item order (slices of a brick adjacent) cuts the fabric traffic further, 279 -> 199 MB per launch at 32^3, but costs
-        // 1 % of the whole step (15.6 vs 15.44 ms, two runs each): the eight slices of a brick then hit the same L2 channels at once.  Off.
-        constexpr bool item_grid = false;
-        gl_.item_grid = item_grid ? 1 : 0;
-        const int nx = item_grid ? items : bricks;
-        gl_.xcd_nx = (xcd_swizzle_enabled() && nx >= xcd_min_blocks()) ? nx : 0;
-        const dim3 gx_grid(gl_.xcd_nx ? xcd_grid(nx) : nx, item_grid ? 1 : g.nslices);
-        static int gx_threads = 0;
-        if (!gx_threads) gx_threads = 512;
+        // (a 1-D grid over (brick, slice) items, the slices of a brick adjacent, cuts the fabric traffic further, 279 -> 199 MB per launch at 32^3, but
+        // costs 1 % of the whole step, 15.6 vs 15.44 ms, two runs each: the eight slices of a brick then hit the same L2 channels at once)
+        gl_.xcd_nx = (xcd_swizzle_enabled() && bricks >= xcd_min_blocks()) ? bricks : 0;
+        const dim3 gx_grid(gl_.xcd_nx ? xcd_grid(bricks) : bricks, g.nslices);
         // second-generation fixed-point kernel (compile-time window strides + guard cells) where one of its window shapes fits;
         // DLKA_GX_FIXED=2 keeps the first generation for A/B runs
-        if (fixed && gl_.resident && !item_grid && !(fx_env && atoi(fx_env) == 2)) {
+        const bool b16 = a.wp16 != nullptr;   // (wp16 itself is not read here: the kernel stages its own bf16 tiles from wp) — bf16 rows, or fp32 rows split in two terms
+        int win = -1;
+        size_t lds_launch = lds;
+        if (fixed && gl_.resident && !(fx_env && atoi(fx_env) == 2)) {
             auto ext2 = [](int bs, int size) { const int a = size + 2, b = bs + 2 * HALO; return a < b ? a : b; };   // window + guard cells, worst brick
             const int nd = ext2(g.bd, a.D), nh = ext2(g.bh, a.H), nw = ext2(g.bw, a.W);
-            const bool b16 = a.wp16 != nullptr;   // (wp16 itself is not read here: the kernel stages its own bf16 tiles from wp) — bf16 rows, or fp32 rows split in two terms
             const size_t wbytes = b16 ? gx3_b16_wbytes(g.ngroups, a.CoutP) : (size_t)g.ngroups * a.CoutP * 32 * sizeof(float);
             const size_t qbytes = (size_t)8 * GX_QW * 8 * sizeof(float);   // 8 waves x GX_QW far-sample records
-#define DLKA_GX2(SWv, SHv, SDv)                                                                                                    \
-    if (nw <= SWv && nh <= SHv && nd <= SDv && 16 + (size_t)SDv * SHv * SWv * (CS / 2) * 8 + wbytes + qbytes <= 150 * 1024) {       \
-        const size_t lds2 = 16 + (size_t)SDv * SHv * SWv * (CS / 2) * 8 + wbytes + qbytes;                                         \
-        const int nk_ = a.CoutP / 32;                                                                                              \
-        if (b16 && !a.act_bf16) {                                                                                                  \
-            if (nk_ == 1) { auto k = cl_deform_gx_fx2_kernel<SWv, SHv, SDv, float, 1, true>; DLKA_LAUNCH(k, gx_grid, dim3(512), lds2, st, a, gl_, scratch); }       \
-            else if (nk_ == 2) { auto k = cl_deform_gx_fx2_kernel<SWv, SHv, SDv, float, 2, true>; DLKA_LAUNCH(k, gx_grid, dim3(512), lds2, st, a, gl_, scratch); }  \
-            else { auto k = cl_deform_gx_fx2_kernel<SWv, SHv, SDv, float, 0, true>; DLKA_LAUNCH(k, gx_grid, dim3(512), lds2, st, a, gl_, scratch); }                \
-        } else if (b16) {                                                                                                          \
-            if (nk_ == 1) { auto k = cl_deform_gx_fx2_kernel<SWv, SHv, SDv, bf16_t, 1, true>; DLKA_LAUNCH(k, gx_grid, dim3(512), lds2, st, a, gl_, scratch); }      \
-            else if (nk_ == 2) { auto k = cl_deform_gx_fx2_kernel<SWv, SHv, SDv, bf16_t, 2, true>; DLKA_LAUNCH(k, gx_grid, dim3(512), lds2, st, a, gl_, scratch); } \
-            else { auto k = cl_deform_gx_fx2_kernel<SWv, SHv, SDv, bf16_t, 0, true>; DLKA_LAUNCH(k, gx_grid, dim3(512), lds2, st, a, gl_, scratch); }               \
-        } else if (a.act_bf16) {                                                                                                   \
-            if (nk_ == 1) { auto k = cl_deform_gx_fx2_kernel<SWv, SHv, SDv, bf16_t, 1>; DLKA_LAUNCH(k, gx_grid, dim3(512), lds2, st, a, gl_, scratch); }      \
-            else if (nk_ == 2) { auto k = cl_deform_gx_fx2_kernel<SWv, SHv, SDv, bf16_t, 2>; DLKA_LAUNCH(k, gx_grid, dim3(512), lds2, st, a, gl_, scratch); } \
-            else { auto k = cl_deform_gx_fx2_kernel<SWv, SHv, SDv, bf16_t, 0>; DLKA_LAUNCH(k, gx_grid, dim3(512), lds2, st, a, gl_, scratch); }               \
-        } else {                                                                                                                   \
-            if (nk_ == 1) { auto k = cl_deform_gx_fx2_kernel<SWv, SHv, SDv, float, 1>; DLKA_LAUNCH(k, gx_grid, dim3(512), lds2, st, a, gl_, scratch); }       \
-            else if (nk_ == 2) { auto k = cl_deform_gx_fx2_kernel<SWv, SHv, SDv, float, 2>; DLKA_LAUNCH(k, gx_grid, dim3(512), lds2, st, a, gl_, scratch); }  \
-            else { auto k = cl_deform_gx_fx2_kernel<SWv, SHv, SDv, float, 0>; DLKA_LAUNCH(k, gx_grid, dim3(512), lds2, st, a, gl_, scratch); }                \
-        }                                                                                                                          \
-        launched = true;                                                                                                           \
-    }
-            bool launched = false;
-            DLKA_GX2(18, 10, 14)
-            else DLKA_GX2(34, 10, 10)
-#undef DLKA_GX2
-            if (launched) {
-                DLKA_CHECK_LAUNCH();
-                const long total = (long)a.B * a.N * g.nslices;
-                long gb = cdivl(total, 256);
-                if (gb > 4096) gb = 4096;
-                DLKA_LAUNCH(cl_deform_gx_gather_kernel, dim3((unsigned)gb), dim3(256), 0, st, a, g, (const float *)scratch);
-                DLKA_CHECK_LAUNCH();
-                return DLKA_OK;
+            for (int w = 0; w < 2 && win < 0; ++w) {
+                const int *s = GX_FX2_WIN[w];
+                const size_t lds2 = 16 + (size_t)s[2] * s[1] * s[0] * (CS / 2) * 8 + wbytes + qbytes;
+                if (nw <= s[0] && nh <= s[1] && nd <= s[2] && lds2 <= 150 * 1024) { win = w; lds_launch = lds2; }
             }
         }
-        if (a.act_bf16) {
-            if (fixed) { auto k = cl_deform_gx_kernel<true, bf16_t>; DLKA_LAUNCH(k, gx_grid, dim3(gx_threads), lds, st, a, gl_, scratch); }
-            else { auto k = cl_deform_gx_kernel<false, bf16_t>; DLKA_LAUNCH(k, gx_grid, dim3(gx_threads), lds, st, a, gl_, scratch); }
-        }
-        else if (fixed) { auto k = cl_deform_gx_kernel<true>; DLKA_LAUNCH(k, gx_grid, dim3(gx_threads), lds, st, a, gl_, scratch); }
-        else { auto k = cl_deform_gx_kernel<false>; DLKA_LAUNCH(k, gx_grid, dim3(gx_threads), lds, st, a, gl_, scratch); }
+        gx_family([&](auto k) { DLKA_LAUNCH(k, gx_grid, dim3(512), lds_launch, st, a, gl_, scratch); }, false, win, b16, a.act_bf16, a.CoutP / 32, fixed);
         DLKA_CHECK_LAUNCH();
         const long total = (long)a.B * a.N * g.nslices;
         long gb = cdivl(total, 256);

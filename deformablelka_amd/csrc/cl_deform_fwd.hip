@@ -538,8 +538,6 @@ int launch_cl_deform_fwd(IgemmArgs a, int splits, hipStream_t st)
     // (C=256 / 4^3: 57.8 -> 36.0 us with NT = 1; C=128 / 8^3: 47.6 -> 41.0 us with NT = 2; profiles/archive/r01s_dfwd_tuning.txt)
     if (a.M <= 256) NT = 1;
     else if (a.M <= 2048 && NT_total == 4) NT = 2;
-    constexpr int nt_env = 0;
-    if (nt_env == 1 || nt_env == 2 || nt_env == 4) { if (NT_total % nt_env == 0 && nt_env <= NT_total) NT = nt_env; }
     if (a.act_bf16 && a.split_bf16 == 2) {   // weights in two-term bf16 records: the contraction runs on the bf16 matrix cores (all stages)
         dim3 gridb(mblocks, splits, NT_total / NT), blockb(256);
         a.xcd_nx = 0;

@@ -576,6 +576,25 @@ static std::atomic<long> g_dw2p_launches{0};   // dlka_dwconv_2p_launch_count (i
 #ifndef DLKA_DW_2P_MIN_WAVES
 #define DLKA_DW_2P_MIN_WAVES 1000000000   // (no launch size at which it won: off unless DLKA_DW_2P asks for it)
 #endif
+// f(kw, dil_w as constants) for the shapes the kernels of this file are instantiated for: the two D-LKA shapes (5^3, 7^3 dil 3) in both storage
+// types, 3 / 1, 5 / 3 and 7 / 1 in fp32 only.  false: none of them
+template <bool F32, class F> static bool dispatch_kw_dil(int kw, int dil_w, F &&f)
+{
+    if (kw == 5 && dil_w == 1) { f(int_c<5>{}, int_c<1>{}); return true; }
+    if (kw == 7 && dil_w == 3) { f(int_c<7>{}, int_c<3>{}); return true; }
+    if constexpr (F32) {
+        if (kw == 3 && dil_w == 1) { f(int_c<3>{}, int_c<1>{}); return true; }
+        if (kw == 5 && dil_w == 3) { f(int_c<5>{}, int_c<3>{}); return true; }
+        if (kw == 7 && dil_w == 1) { f(int_c<7>{}, int_c<1>{}); return true; }
+    }
+    return false;
+}
+// the same for the kernels that exist for the two D-LKA shapes only (the caller has checked that it is one of them)
+template <class F> static void dispatch_dlka_shape(int kw, F &&f)
+{
+    dispatch_bool(kw == 7, [&](auto k7) { f(int_c<(DLKA_V(k7) ? 7 : 5)>{}, int_c<(DLKA_V(k7) ? 3 : 1)>{}); });
+}
+
 // kw, dil_w select the instantiation; returns DLKA_ERR_UNSUPPORTED for other shapes (caller falls back to conv.hip)
 template <typename T>
 static int launch_cl_dwconv_t(const DwArgs &a, int kw, int dil_w, hipStream_t st)
@@ -587,34 +606,29 @@ static int launch_cl_dwconv_t(const DwArgs &a, int kw, int dil_w, hipStream_t st
     dim3 grid((unsigned)cdivl(runs, rpb), 1, cdiv(a.C, cpb)), block(256);
     if (256 % cpb != 0) return DLKA_ERR_UNSUPPORTED;
     if (!F32 && !((kw == 5 && dil_w == 1) || (kw == 7 && dil_w == 3))) return DLKA_ERR_UNSUPPORTED;
-    constexpr bool v1 = false;
-    constexpr int abl0 = 0;
     // the rows kernel needs (b, d, h) uniform per wave: the 64 / cpb runs of a wave must not straddle two rows
     const int wpr = cpb < 64 ? 64 / cpb : 1;
-    if (!v1 && !abl0 && cdiv(a.W, TW) % wpr == 0 && (long)a.W * a.C * 4 < (1l << 31)) {
+    if (cdiv(a.W, TW) % wpr == 0 && (long)a.W * a.C * 4 < (1l << 31)) {
         DwArgs ax = a;
         ax.xcd_nx = 0;
+        auto go = [&](auto k, const dim3 &g) { DLKA_LAUNCH(k, g, block, 0, st, ax); };
         auto swz = [&](dim3 &g) { if (xcd_swizzle_enabled() && g.x >= (unsigned)xcd_min_blocks()) { ax.xcd_nx = (int)g.x; g.x = xcd_grid(ax.xcd_nx); } };
-        constexpr int th_env = 0;
         const bool cubic = a.kd == kw && a.kh == kw && a.dd == dil_w && a.dh == dil_w;
-        const int th = th_env ? th_env : 2;
-        if ((th == 2 || (th == 3 && F32)) && cubic && a.H >= th * dil_w && ((kw == 7 && dil_w == 3) || (kw == 5 && dil_w == 1))) {
+        constexpr int th = 2;   // output rows per work-item
+        if (cubic && a.H >= th * dil_w && ((kw == 7 && dil_w == 3) || (kw == 5 && dil_w == 1))) {
             // Software-pipelined kernel with two output rows on the halves of v_pk_fma_f32 and two output planes per work-item (cl_dwconv_rows2p_kernel): OPT-IN, measured
             // slower (see its header).  DLKA_DW_2P (read per launch): unset / 0 = never, 1 = wherever its geometry fits (5^3: two rows ahead), 2 = the same with one row ahead.
             {
                 const char *e3 = getenv("DLKA_DW_2P");
                 const int mode = e3 ? atoi(e3) : -1;
-                const bool ok2p = th == 2 && a.C % 32 == 0 && a.D >= 2 * dil_w && a.pd == (kw - 1) / 2 * dil_w && a.ph == a.pd && !a.out_blk && cdiv(a.W, TW) % 2 == 0;
+                const bool ok2p = a.C % 32 == 0 && a.D >= 2 * dil_w && a.pd == (kw - 1) / 2 * dil_w && a.ph == a.pd && !a.out_blk && cdiv(a.W, TW) % 2 == 0;
                 const long runs3 = (long)a.B * dil_w * cdiv(a.D, 2 * dil_w) * dil_w * cdiv(a.H, th * dil_w) * cdiv(a.W, TW);
                 const long waves3 = runs3 / 2 * (a.C / 32);
                 if (ok2p && (mode > 0 || (mode < 0 && waves3 >= DLKA_DW_2P_MIN_WAVES))) {
                     dim3 grid3((unsigned)cdivl(runs3, 8), 1, a.C / 32);
                     swz(grid3);
-                    if (kw == 7) { auto k = cl_dwconv_rows2p_kernel<T, 7, 3, TW, 2>; DLKA_LAUNCH(k, grid3, block, 0, st, ax); }   // (a ring of 4 spills: 262 registers' worth)
-                    else {
-                        if (mode == 2) { auto k = cl_dwconv_rows2p_kernel<T, 5, 1, TW, 2>; DLKA_LAUNCH(k, grid3, block, 0, st, ax); }
-                        else { auto k = cl_dwconv_rows2p_kernel<T, 5, 1, TW, 3>; DLKA_LAUNCH(k, grid3, block, 0, st, ax); }
-                    }
+                    if (kw == 7) go(cl_dwconv_rows2p_kernel<T, 7, 3, TW, 2>, grid3);   // (a ring of 4 spills: 262 registers' worth)
+                    else dispatch_bool(mode == 2, [&](auto one) { go(cl_dwconv_rows2p_kernel<T, 5, 1, TW, DLKA_V(one) ? 2 : 3>, grid3); });
                     DLKA_CHECK_LAUNCH();
                     g_dw2p_launches.fetch_add(1, std::memory_order_relaxed);
                     return DLKA_OK;
@@ -627,18 +641,16 @@ static int launch_cl_dwconv_t(const DwArgs &a, int kw, int dil_w, hipStream_t st
             // kernel's time is ONE wave's serial instruction stream (~7.7 K instructions at 7^3); 4 outputs per work-item double the waves
             // and halve the stream.  Chosen where the 8-wide grid leaves SIMDs empty.
             const long waves8 = runs2 * cpb / 64 * cdiv(a.C, cpb);
-            constexpr bool no_tw4 = false;
             // (measured at the stage shapes, us, 4 vs 8 wide: 5^3 13.3 / 17.9 at 16^3, 12.7 / 17.4 at 8^3, 11.0 / 12.4 at 4^3; 7^3 19.0 / 18.5 at 16^3, 8.8 / 9.5 at 8^3)
             #ifndef DLKA_DW_TW4_5
 #define DLKA_DW_TW4_5 1024   // (waves of the 8-wide grid below which the 4-wide one is taken: 5^3 / 7^3; -D... for scripts/build_variant.sh)
 #define DLKA_DW_TW4_7 384
 #endif
-            if (!no_tw4 && th == 2 && waves8 < (kw == 5 ? DLKA_DW_TW4_5 : DLKA_DW_TW4_7) && a.W % 4 == 0 && cdiv(a.W, 4) % wpr == 0) {
+            if (waves8 < (kw == 5 ? DLKA_DW_TW4_5 : DLKA_DW_TW4_7) && a.W % 4 == 0 && cdiv(a.W, 4) % wpr == 0) {
                 const long runs4 = (long)a.B * a.D * dw_row_groups(a.H, th, dil_w).groups * cdiv(a.W, 4);
                 dim3 grid4((unsigned)cdivl(runs4, rpb), 1, cdiv(a.C, cpb));
                 swz(grid4);
-                if (kw == 7) { auto k = cl_dwconv_rowsN_kernel<T, 7, 3, 4, 2>; DLKA_LAUNCH(k, grid4, block, 0, st, ax); }
-                else { auto k = cl_dwconv_rowsN_kernel<T, 5, 1, 4, 2>; DLKA_LAUNCH(k, grid4, block, 0, st, ax); }
+                dispatch_dlka_shape(kw, [&](auto KW, auto DIL) { go(cl_dwconv_rowsN_kernel<T, DLKA_V(KW), DLKA_V(DIL), 4, th>, grid4); });
                 DLKA_CHECK_LAUNCH();
                 return DLKA_OK;
             }
@@ -647,56 +659,32 @@ static int launch_cl_dwconv_t(const DwArgs &a, int kw, int dil_w, hipStream_t st
             // output did not pay for half the workgroups, twice the LDS weight reads and the longer per-wave stream: these convs are not simply L1-bound.
             {
                 const char *e2 = getenv("DLKA_DW_TD2");
-                const bool td2 = (e2 && e2[0] == '1') && th == 2 && cpb == 32 && a.C == 32 && a.D >= 4 * dil_w && a.pd == (kw - 1) / 2 * dil_w && !a.out_blk;
+                const bool td2 = (e2 && e2[0] == '1') && cpb == 32 && a.C == 32 && a.D >= 4 * dil_w && a.pd == (kw - 1) / 2 * dil_w && !a.out_blk;
                 if (td2) {
                     const long runs3 = (long)a.B * dil_w * cdiv(a.D, 2 * dil_w) * dil_w * cdiv(a.H, th * dil_w) * cdiv(a.W, TW);
                     dim3 grid3((unsigned)cdivl(runs3, rpb), 1, 1);
                     ax.xcd_nx = 0;   // (swz(grid2) above may have set it for the one-plane grid)
                     swz(grid3);
-                    if (kw == 7) { auto k = cl_dwconv_rows2d_kernel<T, 7, 3, TW>; DLKA_LAUNCH(k, grid3, block, 0, st, ax); }
-                    else { auto k = cl_dwconv_rows2d_kernel<T, 5, 1, TW>; DLKA_LAUNCH(k, grid3, block, 0, st, ax); }
+                    dispatch_dlka_shape(kw, [&](auto KW, auto DIL) { go(cl_dwconv_rows2d_kernel<T, DLKA_V(KW), DLKA_V(DIL), TW>, grid3); });
                     DLKA_CHECK_LAUNCH();
                     return DLKA_OK;
                 }
             }
-            constexpr bool no_wl = false;   // (measured: 54.3 -> 45.0 us at 32 channels / 32^3, profiles/r04_notes.md)
-            if (kw == 7 && th == 2 && cpb == 32 && a.kd == 7 && !no_wl) { auto k = cl_dwconv_rowsN_kernel<T, 7, 3, TW, 2, true>; DLKA_LAUNCH(k, grid2, block, 0, st, ax); }
-            else if (kw == 7 && th == 2) { auto k = cl_dwconv_rowsN_kernel<T, 7, 3, TW, 2>; DLKA_LAUNCH(k, grid2, block, 0, st, ax); }
-            else if (kw == 5 && th == 2) { auto k = cl_dwconv_rowsN_kernel<T, 5, 1, TW, 2>; DLKA_LAUNCH(k, grid2, block, 0, st, ax); }
-            else if constexpr (F32) {
-                if (kw == 7) { auto k = cl_dwconv_rowsN_kernel<float, 7, 3, TW, 3>; DLKA_LAUNCH(k, grid2, block, 0, st, ax); }
-                else { auto k = cl_dwconv_rowsN_kernel<float, 5, 1, TW, 3>; DLKA_LAUNCH(k, grid2, block, 0, st, ax); }
-            }
+            // the weights of 7^3 in LDS (measured: 54.3 -> 45.0 us at 32 channels / 32^3, profiles/r04_notes.md)
+            if (kw == 7 && cpb == 32 && a.kd == 7) go(cl_dwconv_rowsN_kernel<T, 7, 3, TW, th, true>, grid2);
+            else dispatch_dlka_shape(kw, [&](auto KW, auto DIL) { go(cl_dwconv_rowsN_kernel<T, DLKA_V(KW), DLKA_V(DIL), TW, th>, grid2); });
             DLKA_CHECK_LAUNCH();
             return DLKA_OK;
         }
-        bool done = true;
         dim3 grid1 = grid;
         swz(grid1);
-        if (kw == 5 && dil_w == 1) { auto k = cl_dwconv_rows_kernel<T, 5, 1, TW>; DLKA_LAUNCH(k, grid1, block, 0, st, ax); }
-        else if (kw == 7 && dil_w == 3) { auto k = cl_dwconv_rows_kernel<T, 7, 3, TW>; DLKA_LAUNCH(k, grid1, block, 0, st, ax); }
-        else if constexpr (F32) {
-            if (kw == 3 && dil_w == 1) { auto k = cl_dwconv_rows_kernel<float, 3, 1, TW>; DLKA_LAUNCH(k, grid1, block, 0, st, ax); }
-            else if (kw == 5 && dil_w == 3) { auto k = cl_dwconv_rows_kernel<float, 5, 3, TW>; DLKA_LAUNCH(k, grid1, block, 0, st, ax); }
-            else if (kw == 7 && dil_w == 1) { auto k = cl_dwconv_rows_kernel<float, 7, 1, TW>; DLKA_LAUNCH(k, grid1, block, 0, st, ax); }
-            else done = false;
-        } else done = false;
-        if (done) { DLKA_CHECK_LAUNCH(); return DLKA_OK; }
+        if (dispatch_kw_dil<F32>(kw, dil_w, [&](auto KW, auto DIL) { go(cl_dwconv_rows_kernel<T, DLKA_V(KW), DLKA_V(DIL), TW>, grid1); })) {
+            DLKA_CHECK_LAUNCH();
+            return DLKA_OK;
+        }
     }
-    if (kw == 5 && dil_w == 1) { auto k = cl_dwconv_kernel<T, 5, 1, TW>; DLKA_LAUNCH(k, grid, block, 0, st, a); }
-    else if (kw == 7 && dil_w == 3) {
-        constexpr int abl = 0;
-        if (F32 && abl == 1) { auto k = cl_dwconv_kernel<float, 7, 3, TW, 1>; DLKA_LAUNCH(k, grid, block, 0, st, a); }
-        else if (F32 && abl == 2) { auto k = cl_dwconv_kernel<float, 7, 3, TW, 2>; DLKA_LAUNCH(k, grid, block, 0, st, a); }
-        else { auto k = cl_dwconv_kernel<T, 7, 3, TW>; DLKA_LAUNCH(k, grid, block, 0, st, a); }
-    }
-    else if constexpr (F32) {
-        if (kw == 3 && dil_w == 1) { auto k = cl_dwconv_kernel<float, 3, 1, TW>; DLKA_LAUNCH(k, grid, block, 0, st, a); }
-        else if (kw == 5 && dil_w == 3) { auto k = cl_dwconv_kernel<float, 5, 3, TW>; DLKA_LAUNCH(k, grid, block, 0, st, a); }
-        else if (kw == 7 && dil_w == 1) { auto k = cl_dwconv_kernel<float, 7, 1, TW>; DLKA_LAUNCH(k, grid, block, 0, st, a); }
-        else return DLKA_ERR_UNSUPPORTED;
-    }
-    else return DLKA_ERR_UNSUPPORTED;
+    if (!dispatch_kw_dil<F32>(kw, dil_w, [&](auto KW, auto DIL) { auto k = cl_dwconv_kernel<T, DLKA_V(KW), DLKA_V(DIL), TW>; DLKA_LAUNCH(k, grid, block, 0, st, a); }))
+        return DLKA_ERR_UNSUPPORTED;
     DLKA_CHECK_LAUNCH();
     return DLKA_OK;
 }
@@ -919,7 +907,6 @@ static int launch_cl_dwconv_wgrad_t(DwWgradArgs a, int kw, int dil_w, hipStream_
         if (launch_zero(a.gwp, (size_t)a.kd * a.kh * kw * a.C * 4, st) != DLKA_OK) return DLKA_ERR_LAUNCH;
         if (a.gb && launch_zero(a.gb, (size_t)a.C * 4, st) != DLKA_OK) return DLKA_ERR_LAUNCH;
     }
-    constexpr bool v1 = false;
     // the centre tap row must exist for the bias ride-along (odd kernels with "same" padding: always)
     const bool centre = (a.pd % a.dd == 0) && (a.ph % a.dh == 0) && a.pd / a.dd < a.kd && a.ph / a.dh < a.kh;
     // measured (profiles/archive/r01o_dw_variants.txt): 7^3 dil 3 178 -> 103 us at 32^3, 38 -> 36 us at 16^3; 5^3 72 -> 66 us at 32^3 but 23.5 -> 26 us at 16^3
@@ -928,26 +915,18 @@ static int launch_cl_dwconv_wgrad_t(DwWgradArgs a, int kw, int dil_w, hipStream_
     const bool pays = kw >= 7 ? rows >= 512 : rows >= 1024;
     const int wpr = cpb < 64 ? 64 / cpb : 1;                       // runs per wave: must not straddle rows (row descriptors)
     const bool uniform = cdiv(a.W, TW) % wpr == 0 && (long)a.W * a.C * 4 < (1l << 31);
-    if (!v1 && pays && uniform && a.kd == kw && a.kh == kw && a.dd == dil_w && a.dh == dil_w && (centre || !a.gb)) {
+    if (pays && uniform && a.kd == kw && a.kh == kw && a.dd == dil_w && a.dh == dil_w && (centre || !a.gb)) {
         dim3 grid2(xb, a.kd, cdiv(a.C, cpb));
         a.xcd_nx = 0;
         if (xcd_swizzle_enabled() && xb >= (unsigned)xcd_min_blocks()) { a.xcd_nx = xb; grid2.x = xcd_grid(xb); }
-        if (kw == 5 && dil_w == 1) { auto k = cl_dwconv_wgrad2_kernel<T, 5, 1, TW>; DLKA_LAUNCH(k, grid2, block256(), 0, st, a); }
-        else if (kw == 7 && dil_w == 3) { auto k = cl_dwconv_wgrad2_kernel<T, 7, 3, TW>; DLKA_LAUNCH(k, grid2, block256(), 0, st, a); }
-        else if (F32 && kw == 3 && dil_w == 1) { auto k = cl_dwconv_wgrad2_kernel<float, 3, 1, TW>; DLKA_LAUNCH(k, grid2, block256(), 0, st, a); }
-        else if (F32 && kw == 5 && dil_w == 3) { auto k = cl_dwconv_wgrad2_kernel<float, 5, 3, TW>; DLKA_LAUNCH(k, grid2, block256(), 0, st, a); }
-        else if (F32 && kw == 7 && dil_w == 1) { auto k = cl_dwconv_wgrad2_kernel<float, 7, 1, TW>; DLKA_LAUNCH(k, grid2, block256(), 0, st, a); }
-        else return DLKA_ERR_UNSUPPORTED;
+        if (!dispatch_kw_dil<F32>(kw, dil_w, [&](auto KW, auto DIL) { auto k = cl_dwconv_wgrad2_kernel<T, DLKA_V(KW), DLKA_V(DIL), TW>; DLKA_LAUNCH(k, grid2, block256(), 0, st, a); }))
+            return DLKA_ERR_UNSUPPORTED;
         DLKA_CHECK_LAUNCH();
         return DLKA_OK;
     }
     dim3 grid(xb, a.kd * a.kh, cdiv(a.C, cpb)), block(256);
-    if (kw == 5 && dil_w == 1) { auto k = cl_dwconv_wgrad_kernel<T, 5, 1, TW>; DLKA_LAUNCH(k, grid, block, 0, st, a); }
-    else if (kw == 7 && dil_w == 3) { auto k = cl_dwconv_wgrad_kernel<T, 7, 3, TW>; DLKA_LAUNCH(k, grid, block, 0, st, a); }
-    else if (F32 && kw == 3 && dil_w == 1) { auto k = cl_dwconv_wgrad_kernel<float, 3, 1, TW>; DLKA_LAUNCH(k, grid, block, 0, st, a); }
-    else if (F32 && kw == 5 && dil_w == 3) { auto k = cl_dwconv_wgrad_kernel<float, 5, 3, TW>; DLKA_LAUNCH(k, grid, block, 0, st, a); }
-    else if (F32 && kw == 7 && dil_w == 1) { auto k = cl_dwconv_wgrad_kernel<float, 7, 1, TW>; DLKA_LAUNCH(k, grid, block, 0, st, a); }
-    else return DLKA_ERR_UNSUPPORTED;
+    if (!dispatch_kw_dil<F32>(kw, dil_w, [&](auto KW, auto DIL) { auto k = cl_dwconv_wgrad_kernel<T, DLKA_V(KW), DLKA_V(DIL), TW>; DLKA_LAUNCH(k, grid, block, 0, st, a); }))
+        return DLKA_ERR_UNSUPPORTED;
     DLKA_CHECK_LAUNCH();
     return DLKA_OK;
 }

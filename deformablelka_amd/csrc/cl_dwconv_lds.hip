@@ -221,20 +221,21 @@ static bool dw_lds_plan(const DwArgs &a, int bd_max, int bh_max, int bw_max, DwL
 
 static std::atomic<long> g_dw_lds_launches{0};   // dlka_dwconv_lds_launch_count (include/dlka.h): diagnostics
 
-template <typename T, int KW, int DIL, int TW, int TH>
-static int dw_lds_launch(const DwArgs &a, DwLdsGeom g, size_t lds, int threads, hipStream_t st)
+// f(kernel<T, KW, DIL, TW, TH>) for variant 1 = 7^3 dil 3, classes of up to 11^3 (rows of 11); 2 = 7^3 dil 3, classes of up to 6^3; 3 = 5^3 (the
+// numbering of dw_lds_select); every (no selectors given): for all six members
+template <class F> static void dw_lds_family(F &&f, bool every = true, bool bf16 = false, int variant = 0)
 {
-    auto k = cl_dwconv_lds_kernel<T, KW, DIL, TW, TH>;
-#if !defined(HIPEMU)
-    static std::atomic<uint64_t> attr_done{0};   // dynamic LDS above 64 KB: per function and per device
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return DLKA_ERR_LAUNCH;
-    const uint64_t bit = 1ull << (dev & 63);
-    if (!(attr_done.load(std::memory_order_acquire) & bit)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return DLKA_ERR_LAUNCH;
-        attr_done.fetch_or(bit, std::memory_order_release);
-    }
-#endif
+    dispatch_act(bf16, [&](auto t) { dispatch_int<3, 1, 2>(variant, [&](auto v) {
+        constexpr int V = DLKA_V(v);
+        f(cl_dwconv_lds_kernel<DLKA_T(t), V == 3 ? 5 : 7, V == 3 ? 1 : 3, V == 1 ? 11 : V == 2 ? 6 : 8, 1>);
+    }, every); }, every);
+}
+
+static int dw_lds_launch(const DwArgs &a, int variant, DwLdsGeom g, size_t lds, int threads, hipStream_t st)
+{
+    const int DIL = variant == 3 ? 1 : 3;
+    static std::atomic<uint64_t> attr_done{0};
+    if (prepare_large_lds(attr_done, [](auto set) { dw_lds_family(set); }) != DLKA_OK) return DLKA_ERR_LAUNCH;
     if (!a.in_blocked) {   // the class-blocked copy of the input (DwArgs::blk); a preceding LDS-brick conv may have written it already
         const long pieces = (long)a.B * a.D * a.H * a.W * (a.C / DWL_CG);
         long blocks = cdivl(pieces, 256);
@@ -246,7 +247,7 @@ static int dw_lds_launch(const DwArgs &a, DwLdsGeom g, size_t lds, int threads, 
     DwArgs ax = a;
     dim3 grid((unsigned)g.nitems);
     if (xcd_swizzle_enabled() && g.nitems >= xcd_min_blocks()) { g.xcd_nx = g.nitems; grid.x = xcd_grid(g.nitems); }
-    DLKA_LAUNCH(k, grid, dim3(threads), lds, st, ax, g);
+    dw_lds_family([&](auto k) { DLKA_LAUNCH(k, grid, dim3(threads), lds, st, ax, g); }, false, a.act_bf16, variant);
     DLKA_CHECK_LAUNCH();
     g_dw_lds_launches.fetch_add(1, std::memory_order_relaxed);
     return DLKA_OK;
@@ -261,7 +262,6 @@ static int dw_lds_mode()
 }
 
 // variant of the launch: 0 = not this kernel; 1 = 7^3 dil 3, classes of up to 11^3 (rows of 11); 2 = 7^3 dil 3, classes of up to 6^3; 3 = 5^3
-template <typename T>
 static int dw_lds_select(const DwArgs &a, int kw, int dil_w, DwLdsGeom &g, size_t &lds, int &threads)
 {
     const int mode = dw_lds_mode();
@@ -287,23 +287,13 @@ static int dw_lds_select(const DwArgs &a, int kw, int dil_w, DwLdsGeom &g, size_
 }
 
 // Returns DLKA_ERR_UNSUPPORTED when this launch should stay on cl_dwconv_rowsN_kernel.
-template <typename T>
-static int launch_cl_dwconv_lds_t(const DwArgs &a, int kw, int dil_w, hipStream_t st)
+int launch_cl_dwconv_lds(const DwArgs &a, int kw, int dil_w, hipStream_t st)
 {
     DwLdsGeom g;
     size_t lds = 0;
     int threads = 0;
-    switch (dw_lds_select<T>(a, kw, dil_w, g, lds, threads)) {
-    case 1: return dw_lds_launch<T, 7, 3, 11, 1>(a, g, lds, threads, st);
-    case 2: return dw_lds_launch<T, 7, 3, 6, 1>(a, g, lds, threads, st);
-    case 3: return dw_lds_launch<T, 5, 1, 8, 1>(a, g, lds, threads, st);
-    default: return DLKA_ERR_UNSUPPORTED;
-    }
-}
-
-int launch_cl_dwconv_lds(const DwArgs &a, int kw, int dil_w, hipStream_t st)
-{
-    return a.act_bf16 ? launch_cl_dwconv_lds_t<bf16_t>(a, kw, dil_w, st) : launch_cl_dwconv_lds_t<float>(a, kw, dil_w, st);
+    const int variant = dw_lds_select(a, kw, dil_w, g, lds, threads);
+    return variant ? dw_lds_launch(a, variant, g, lds, threads, st) : DLKA_ERR_UNSUPPORTED;
 }
 
 // would launch_cl_dwconv take the LDS-brick kernel for this conv?  (the token path asks before it lets the PREVIOUS conv write the blocked copy)
@@ -312,7 +302,7 @@ bool cl_dwconv_lds_selected(const DwArgs &a, int kw, int dil_w)
     DwLdsGeom g;
     size_t lds = 0;
     int threads = 0;
-    return dw_lds_select<float>(a, kw, dil_w, g, lds, threads) != 0;
+    return dw_lds_select(a, kw, dil_w, g, lds, threads) != 0;
 }
 
 size_t cl_dwconv_blk_floats(int B, int C, int D, int H, int W, int dil) { return dw_blk_floats(B, C, D, H, W, dil); }

@@ -481,20 +481,8 @@ static int launch_igemm_nt(const IgemmArgs &a, int splits, hipStream_t st)
     IgemmArgs ax = a;
     ax.xcd_nx = 0;
     if (xcd_swizzle_enabled() && a.K > 1 && mblocks >= (unsigned)xcd_min_blocks()) { ax.xcd_nx = mblocks; grid.x = xcd_grid(mblocks); }
-#define DLKA_IG(NTV)                                              \
-    {                                                             \
-        auto k = cl_igemm_kernel<AMODE, OMODE, NTV, SPLIT, T>;    \
-        DLKA_LAUNCH(k, grid, block, 0, st, ax);            \
-    }
-    switch (NT) {
-        case 1: DLKA_IG(1) break;
-        case 2: DLKA_IG(2) break;
-        case 3: DLKA_IG(3) break;
-        case 4: DLKA_IG(4) break;
-        case 8: DLKA_IG(8) break;
-        default: return DLKA_ERR_UNSUPPORTED;
-    }
-#undef DLKA_IG
+    if (!dispatch_menu<1, 2, 3, 4, 8>(NT, [&](auto n) { auto k = cl_igemm_kernel<AMODE, OMODE, DLKA_V(n), SPLIT, T>; DLKA_LAUNCH(k, grid, block, 0, st, ax); }))
+        return DLKA_ERR_UNSUPPORTED;
     DLKA_CHECK_LAUNCH();
     return DLKA_OK;
 }
@@ -533,8 +521,7 @@ int launch_cl_igemm(int amode, int omode, IgemmArgs a, int splits, hipStream_t s
     if ((long)a.M * (amode == 2 ? a.CinReal : a.Cin) * 4 >= (1l << 31)) return DLKA_ERR_UNSUPPORTED;   // 32-bit buffer offsets
     a.units_per_split = cdiv(a.K * (a.CinP / 32), splits);
     splits = cdiv(a.K * (a.CinP / 32), a.units_per_split);
-    constexpr bool pw_v1 = false;
-    if (!pw_v1 && amode == 0 && omode == 0 && a.K == 1 && splits == 1 && !a.split_bf16) {
+    if (amode == 0 && omode == 0 && a.K == 1 && splits == 1 && !a.split_bf16) {
         const int rc = launch_cl_pointwise(a, st);
         if (rc != DLKA_ERR_UNSUPPORTED) return rc;
     }

@@ -559,17 +559,11 @@ int launch_cl_pointwise_chain(const PwPairArgs &a, hipStream_t st)
     unsigned blocks = (unsigned)cdiv(a.M, 32);
     if (const int rc = pair_zero_blocks(a, ax, blocks)) return rc;
     dim3 grid(blocks);
-#define DLKA_CHAIN(T, NTC, KW, KWW) do { auto k = cl_pointwise_chain_kernel<T, NTC, KW, KWW>; DLKA_LAUNCH(k, grid, dim3(64 * NTC * KWW), 0, st, ax); } while (0)
-    if (a.act_bf16) {
-        if (a.C == 64) DLKA_CHAIN(bf16_t, 2, 1, 1);
-        else if (a.C == 128) DLKA_CHAIN(bf16_t, 4, 4, 4);
-        else DLKA_CHAIN(bf16_t, 8, 4, 2);
-    } else {
-        if (a.C == 64) DLKA_CHAIN(float, 2, 1, 1);
-        else if (a.C == 128) DLKA_CHAIN(float, 4, 4, 4);
-        else DLKA_CHAIN(float, 8, 4, 2);
-    }
-#undef DLKA_CHAIN
+    dispatch_act(a.act_bf16, [&](auto t) { dispatch_int<256, 64, 128>(a.C, [&](auto c) {   // column tiles, slices, slice waves
+        constexpr int C = DLKA_V(c), NTC = C / 32, KW = C == 64 ? 1 : 4, KWW = C == 64 ? 1 : C == 128 ? 4 : 2;
+        auto k = cl_pointwise_chain_kernel<DLKA_T(t), NTC, KW, KWW>;
+        DLKA_LAUNCH(k, grid, dim3(64 * NTC * KWW), 0, st, ax);
+    }); });
     DLKA_CHECK_LAUNCH();
     g_pw_chain_launches.fetch_add(1, std::memory_order_relaxed);
     return DLKA_OK;

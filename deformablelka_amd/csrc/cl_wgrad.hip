@@ -848,16 +848,18 @@ int launch_cl_wgrad(int amode, int gmode, WgradArgs a, T *gw, T *gb, hipStream_t
     const bool wg = pl.waves > 1;
     a.CoutP = round_up(a.Cout, 32);
     a.CT = a.Cin / 32;
-    constexpr bool slow_addr = false;
-    a.w16 = (!slow_addr && (a.W & 15) == 0) ? 1 : 0;
+    a.w16 = (a.W & 15) == 0 ? 1 : 0;
     { const char *e = getenv("DLKA_WGRAD_WIN3"); a.no_win3 = (e && e[0] == '0') ? 1 : 0; }   // (read per launch: a parity test toggles it)
     const int OT = a.CoutP / 32;
     if ((long)a.M * a.Cin * 4 >= (1l << 31) || (long)a.M * a.Cout * 4 >= (1l << 31)) return DLKA_ERR_UNSUPPORTED;   // 32-bit buffer offsets
     a.bpart = gb ? a.part + (size_t)nchunks * a.K * a.CoutP * a.Cin : nullptr;
     dim3 block(64 * pl.waves);
+    dim3 grid;
+    auto go = [&](auto k) { DLKA_LAUNCH(k, grid, block, 0, st, a); };
+    const bool n16 = (a.N & 15) == 0;
     if (amode == 1) {
         if (gmode != 0 || a.K == 1) return DLKA_ERR_UNSUPPORTED;
-        dim3 grid(nchunks, OT * a.CT, cdiv(a.K, pl.tpw));
+        grid = dim3(nchunks, OT * a.CT, cdiv(a.K, pl.tpw));
         static const bool no_xcd = getenv("DLKA_NO_XCD_SWIZZLE") != nullptr;   // A/B switch
         if (!no_xcd && nchunks >= xcd_min_blocks()) {
             a.xcd_ny = grid.y; a.xcd_nz = grid.z; a.xcd_total = (int)(grid.x * grid.y * grid.z);
@@ -865,27 +867,18 @@ int launch_cl_wgrad(int amode, int gmode, WgradArgs a, T *gw, T *gb, hipStream_t
         }
         if (a.samp) {   // samples stored by the grad_offset kernel: dense stream, no gather
             if (pl.tpw != 3 || (long)a.K * a.M * a.Cin * (a.act_bf16 ? 2 : 4) >= (1l << 31)) return DLKA_ERR_UNSUPPORTED;   // 32-bit buffer offsets below DLKA_OOB
-            constexpr int WS = DLKA_WGRAD_W_SAMP;
-#define DLKA_WGS(...)                                                                                                     \
-    {                                                                                                                     \
-        if (wg) { auto k = cl_wgrad_samp_kernel<3, __VA_ARGS__, WS>; DLKA_LAUNCH(k, grid, block, 0, st, a); }             \
-        else { auto k = cl_wgrad_samp_kernel<3, __VA_ARGS__, 1>; DLKA_LAUNCH(k, grid, block, 0, st, a); }                 \
-    }
-            if (a.act_bf16) DLKA_WGS(bf16_t, false, false)
-            else if (a.samp_f16 && a.samp_b16mfma) DLKA_WGS(float, true, true)
-            else if (a.samp_f16) DLKA_WGS(float, true, false)
-            else DLKA_WGS(float, false, false)
-#undef DLKA_WGS
+            dispatch_bool(wg, [&](auto w) {
+                constexpr int WV = DLKA_V(w) ? DLKA_WGRAD_W_SAMP : 1;
+                if (a.act_bf16) go(cl_wgrad_samp_kernel<3, bf16_t, false, false, WV>);
+                else if (a.samp_f16 && a.samp_b16mfma) go(cl_wgrad_samp_kernel<3, float, true, true, WV>);
+                else if (a.samp_f16) go(cl_wgrad_samp_kernel<3, float, true, false, WV>);
+                else go(cl_wgrad_samp_kernel<3, float, false, false, WV>);
+            });
         }
         else if (pl.tpw != 3) return DLKA_ERR_UNSUPPORTED;   // (4 and 7 taps per wave measured slower: more registers, fewer waves)
-        else if (a.act_bf16) {
-            if (wg) { auto k = cl_wgrad_deform_kernel<3, bf16_t, DLKA_WGRAD_W_SAMP>; DLKA_LAUNCH(k, grid, block, 0, st, a); }
-            else { auto k = cl_wgrad_deform_kernel<3, bf16_t, 1>; DLKA_LAUNCH(k, grid, block, 0, st, a); }
-        }
-        else if (wg) { auto k = cl_wgrad_deform_kernel<3, float, DLKA_WGRAD_W_SAMP>; DLKA_LAUNCH(k, grid, block, 0, st, a); }
-        else { auto k = cl_wgrad_deform_kernel<3, float, 1>; DLKA_LAUNCH(k, grid, block, 0, st, a); }
+        else dispatch_act(a.act_bf16, [&](auto t) { dispatch_bool(wg, [&](auto w) { go(cl_wgrad_deform_kernel<3, DLKA_T(t), DLKA_V(w) ? DLKA_WGRAD_W_SAMP : 1>); }); });
     } else {
-        dim3 grid(nchunks, cdiv(OT, pl.cot) * a.CT, cdiv(a.K, pl.tpw));
+        grid = dim3(nchunks, cdiv(OT, pl.cot) * a.CT, cdiv(a.K, pl.tpw));
         static const bool no_xcd2 = getenv("DLKA_NO_XCD_SWIZZLE") != nullptr;
         if (!no_xcd2 && a.K > 1 && nchunks >= xcd_min_blocks()) {
             a.xcd_ny = grid.y; a.xcd_nz = grid.z; a.xcd_total = (int)(grid.x * grid.y * grid.z);
@@ -893,18 +886,15 @@ int launch_cl_wgrad(int amode, int gmode, WgradArgs a, T *gw, T *gb, hipStream_t
         }
         static const bool exact = getenv("DLKA_EXACT_FP32") != nullptr;
         const bool split = !exact && a.K > 1;   // MFMA-bound contractions: bf16 x3 split (see cl_igemm.hip)
-        if (a.g_cpad && !((a.N & 15) == 0 && split && gmode == 1)) return DLKA_ERR_UNSUPPORTED;   // packed g: split + N16 variant only
-        // (WV: the family's waves per workgroup, or 1 under DLKA_WGRAD_WAVES=1)
-#define DLKA_WG_W(GM, CO, TP, WV)                                                                                \
-    {                                                                                                            \
-        if ((a.N & 15) == 0 && split) { auto k = cl_wgrad_dense_kernel<GM, CO, TP, true, true, float, WV>; DLKA_LAUNCH(k, grid, block, 0, st, a); }  \
-        else if ((a.N & 15) == 0) { auto k = cl_wgrad_dense_kernel<GM, CO, TP, true, false, float, WV>; DLKA_LAUNCH(k, grid, block, 0, st, a); }  \
-        else { auto k = cl_wgrad_dense_kernel<GM, CO, TP, false, false, float, WV>; DLKA_LAUNCH(k, grid, block, 0, st, a); }              \
-    }
-#define DLKA_WG(GM, CO, TP)                                                                                      \
-    {                                                                                                            \
-        if (!wg) DLKA_WG_W(GM, CO, TP, 1) else if (a.K == 1) DLKA_WG_W(GM, CO, TP, DLKA_WGRAD_W_PW) else DLKA_WG_W(GM, CO, TP, DLKA_WGRAD_W_DENSE)   \
-    }
+        if (a.g_cpad && !(n16 && split && gmode == 1)) return DLKA_ERR_UNSUPPORTED;   // packed g: split + N16 variant only
+        // fp32 activations: kernel<GM, CO, TP>, with the family's waves per workgroup (that of K = 1 or of K > 1, or 1 under DLKA_WGRAD_WAVES=1)
+        auto dense = [&](auto gm, auto co, auto tp) {
+            dispatch_bool(wg, [&](auto w) { dispatch_bool(a.K == 1, [&](auto pw) { dispatch_bool(n16, [&](auto n) { dispatch_bool(n16 && split, [&](auto sp) {
+                constexpr int WV = !DLKA_V(w) ? 1 : DLKA_V(pw) ? DLKA_WGRAD_W_PW : DLKA_WGRAD_W_DENSE;
+                if constexpr (DLKA_V(n) || !DLKA_V(sp))
+                    go(cl_wgrad_dense_kernel<DLKA_V(gm), DLKA_V(co), DLKA_V(tp), DLKA_V(n), DLKA_V(sp), float, WV>);
+            }); }); }); });
+        };
         if (a.pad && a.K > 1 && gmode == 1 && split && !a.g_cpad && pl.tpw == 3 && (a.Cin * (a.act_bf16 ? 2 : 4)) % 16 == 0 &&
             cl_wgrad_pad_bytes(a.B, a.D, a.H, a.W, a.Cin, a.kd, a.kh, a.kw, a.dd, a.dh, a.dw, a.act_bf16) < ((size_t)1 << 31)) {
             // round 5: the zero-padded copy of the input first (one streaming pass), then the kernels that need no coordinate test
@@ -920,45 +910,25 @@ int launch_cl_wgrad(int amode, int gmode, WgradArgs a, T *gw, T *gb, hipStream_t
                 DLKA_LAUNCH(k, dim3(pgrid), dim3(256), 0, st, a.in, const_cast<float *>(a.pad), a.B, a.D, a.H, a.W, a.Cin, a.DP, a.HP, a.WP, a.pd, a.ph, a.pw);
             }
             DLKA_CHECK_LAUNCH();
-            const bool n16 = (a.N & 15) == 0;
-#define DLKA_WGP_W(CO, T_, WV)                                                                                             \
-    {                                                                                                                      \
-        if (n16) { auto k = cl_wgrad_dense_pad_kernel<CO, true, T_, WV>; DLKA_LAUNCH(k, grid, block, 0, st, a); }          \
-        else { auto k = cl_wgrad_dense_pad_kernel<CO, false, T_, WV>; DLKA_LAUNCH(k, grid, block, 0, st, a); }             \
-    }
-#define DLKA_WGP(CO, T_)                                                                                                   \
-    {                                                                                                                      \
-        if (wg) DLKA_WGP_W(CO, T_, DLKA_WGRAD_W_DENSE) else DLKA_WGP_W(CO, T_, 1)                                          \
-    }
-            if (a.act_bf16) { if (pl.cot == 3) DLKA_WGP(3, bf16_t) else if (pl.cot == 2) DLKA_WGP(2, bf16_t) else DLKA_WGP(1, bf16_t) }
-            else { if (pl.cot == 3) DLKA_WGP(3, float) else if (pl.cot == 2) DLKA_WGP(2, float) else DLKA_WGP(1, float) }
-#undef DLKA_WGP
-#undef DLKA_WGP_W
+            dispatch_act(a.act_bf16, [&](auto t) { dispatch_int<1, 2, 3>(pl.cot, [&](auto co) { dispatch_bool(wg, [&](auto w) { dispatch_bool(n16, [&](auto n) {
+                go(cl_wgrad_dense_pad_kernel<DLKA_V(co), DLKA_V(n), DLKA_T(t), DLKA_V(w) ? DLKA_WGRAD_W_DENSE : 1>);
+            }); }); }); });
         } else if (a.act_bf16) {   // DLKA_BF16 token path: only the offset-predict conv's weight gradient comes through here (planar fp32 g, bf16 in)
             if (a.K == 1 || gmode != 1 || !split || a.g_cpad || pl.tpw != 3) return DLKA_ERR_UNSUPPORTED;
-#define DLKA_WGB_W(CO, WV)                                                                                                                     \
-    {                                                                                                                                          \
-        if ((a.N & 15) == 0) { auto k = cl_wgrad_dense_kernel<1, CO, 3, true, true, bf16_t, WV>; DLKA_LAUNCH(k, grid, block, 0, st, a); }    \
-        else { auto k = cl_wgrad_dense_kernel<1, CO, 3, false, true, bf16_t, WV>; DLKA_LAUNCH(k, grid, block, 0, st, a); }                   \
-    }
-#define DLKA_WGB(CO)                                                                                                                           \
-    {                                                                                                                                          \
-        if (wg) DLKA_WGB_W(CO, DLKA_WGRAD_W_DENSE) else DLKA_WGB_W(CO, 1)                                                                      \
-    }
-            if (pl.cot == 3) DLKA_WGB(3) else if (pl.cot == 2) DLKA_WGB(2) else DLKA_WGB(1)
-#undef DLKA_WGB
-#undef DLKA_WGB_W
+            dispatch_int<1, 2, 3>(pl.cot, [&](auto co) { dispatch_bool(wg, [&](auto w) { dispatch_bool(n16, [&](auto n) {
+                go(cl_wgrad_dense_kernel<1, DLKA_V(co), 3, DLKA_V(n), true, bf16_t, DLKA_V(w) ? DLKA_WGRAD_W_DENSE : 1>);
+            }); }); });
         } else if (a.K == 1) {
             if (gmode != 0) return DLKA_ERR_UNSUPPORTED;
-            if (pl.cot == 2) DLKA_WG(0, 2, 1) else DLKA_WG(0, 1, 1)
+            dispatch_int<1, 2>(pl.cot, [&](auto co) { dense(int_c<0>{}, co, int_c<1>{}); });
         } else if (gmode == 1) {
-            if (pl.cot == 3 && pl.tpw == 1) DLKA_WG(1, 3, 1) else if (pl.cot == 3 && pl.tpw == 2) DLKA_WG(1, 3, 2)
-            else if (pl.cot == 3) DLKA_WG(1, 3, 3) else if (pl.cot == 2) DLKA_WG(1, 2, 3) else DLKA_WG(1, 1, 3)
+            dispatch_int<1, 2, 3>(pl.cot, [&](auto co) {
+                if constexpr (DLKA_V(co) == 3) dispatch_int<3, 1, 2>(pl.tpw, [&](auto tp) { dense(int_c<1>{}, co, tp); });
+                else dense(int_c<1>{}, co, int_c<3>{});
+            });
         } else {
-            if (pl.cot == 3) DLKA_WG(0, 3, 3) else if (pl.cot == 2) DLKA_WG(0, 2, 3) else DLKA_WG(0, 1, 3)
+            dispatch_int<1, 2, 3>(pl.cot, [&](auto co) { dense(int_c<0>{}, co, int_c<3>{}); });
         }
-#undef DLKA_WG
-#undef DLKA_WG_W
     }
     DLKA_CHECK_LAUNCH();
     const long n = (long)a.K * a.Cout * a.Cin + (gb ? a.Cout : 0);
@@ -999,19 +969,10 @@ int launch_cl_wgrad_pw3(const WgradArgs *jobs, float *const *gw, float *const *g
     }
     dim3 grid(nchunks, cdiv(OT, pl.cot) * CT, 3), block(64 * pl.waves);
     const bool n16 = (a0.N & 15) == 0;
-#define DLKA_PW3_W(CO, T_, WV)                                                                                  \
-    {                                                                                                           \
-        if (n16) { auto k = cl_wgrad_pw3_kernel<CO, true, T_, WV>; DLKA_LAUNCH(k, grid, block, 0, st, b); }     \
-        else { auto k = cl_wgrad_pw3_kernel<CO, false, T_, WV>; DLKA_LAUNCH(k, grid, block, 0, st, b); }        \
-    }
-#define DLKA_PW3(CO, T_)                                                                                        \
-    {                                                                                                           \
-        if (wg) DLKA_PW3_W(CO, T_, DLKA_WGRAD_W_PW) else DLKA_PW3_W(CO, T_, 1)                                  \
-    }
-    if (a0.act_bf16) { if (pl.cot == 2) DLKA_PW3(2, bf16_t) else DLKA_PW3(1, bf16_t) }
-    else { if (pl.cot == 2) DLKA_PW3(2, float) else DLKA_PW3(1, float) }
-#undef DLKA_PW3
-#undef DLKA_PW3_W
+    dispatch_act(a0.act_bf16, [&](auto t) { dispatch_int<1, 2>(pl.cot, [&](auto co) { dispatch_bool(wg, [&](auto w) { dispatch_bool(n16, [&](auto n) {
+        auto k = cl_wgrad_pw3_kernel<DLKA_V(co), DLKA_V(n), DLKA_T(t), DLKA_V(w) ? DLKA_WGRAD_W_PW : 1>;
+        DLKA_LAUNCH(k, grid, block, 0, st, b);
+    }); }); }); });
     DLKA_CHECK_LAUNCH();
     return DLKA_OK;
 }
@@ -1125,11 +1086,10 @@ __global__ __launch_bounds__(256) void cl_wgrad_finalize_table_kernel(const Fina
 // workgroups a job needs; sets the job's fold variant
 long cl_wgrad_finalize_plan_job(FinalizeJob &j)
 {
-    constexpr bool no_tr = false;
 #ifndef DLKA_FIN_TR_MAX_CHUNKS
 #define DLKA_FIN_TR_MAX_CHUNKS 16   // (compile-time for A/B builds; with four waves per workgroup the 16^3 stage's 13 partial sets come under it — profiles/r13_notes.md)
 #endif
-    j.tr = (!no_tr && j.kind == 0 && j.K > 1 && j.K <= 27 && j.chunks <= DLKA_FIN_TR_MAX_CHUNKS && j.Cin % 32 == 0 && (long)j.Cout * j.Cin >= 1024) ? 1 : 0;
+    j.tr = (j.kind == 0 && j.K > 1 && j.K <= 27 && j.chunks <= DLKA_FIN_TR_MAX_CHUNKS && j.Cin % 32 == 0 && (long)j.Cout * j.Cin >= 1024) ? 1 : 0;
     return j.tr ? (long)j.Cout * (j.Cin / 32) + (j.gb ? cdiv(j.Cout, 32) : 0) : cdivl(j.n, 32);
 }
 

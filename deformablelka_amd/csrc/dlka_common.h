@@ -5,6 +5,9 @@
 #include <stdint.h>
 #include <string.h>
 
+#include <atomic>
+#include <type_traits>
+
 #include "dlka.h"
 #include "dlka_intrin.h"
 
@@ -169,5 +172,64 @@ void trace_after_launch(const void *kernel_fn, hipStream_t st);
     do {                                                     \
         if (hipGetLastError() != hipSuccess) return DLKA_ERR_LAUNCH; \
     } while (0)
+
+// ---------------------------------------------------------------------------------------------
+// Run-time values -> template arguments.  Each helper calls the generic lambda `f` with a tag for the value that matched:
+//     dispatch_act(a.act_bf16, [&](auto t) { dispatch_int<0, 1, 2>(nkc, [&](auto nk) {
+//         auto k = some_kernel<DLKA_T(t), DLKA_V(nk)>; DLKA_LAUNCH(k, ...); }); });
+// With every = true they call `f` once per possible value instead: a kernel family that writes its ladder as ONE function of
+// (f, every = true, selectors...) is enumerated for prepare_large_lds() by the very code that picks the member to launch.
+// ---------------------------------------------------------------------------------------------
+template <typename T> struct type_tag { using type = T; };
+#define DLKA_V(tag) decltype(tag)::value
+#define DLKA_T(tag) typename decltype(tag)::type
+
+template <class F> void dispatch_bool(bool v, F &&f, bool every = false)
+{
+    if (every || v) f(std::integral_constant<bool, true>{});
+    if (every || !v) f(std::integral_constant<bool, false>{});
+}
+template <int V> using int_c = std::integral_constant<int, V>;
+// v from the menu: that value (the first match, should -D overrides make two entries equal); false, and no call, for any other v
+template <int... Menu, class F> bool dispatch_menu(int v, F &&f, bool every = false)
+{
+    bool hit = false;
+    (((every || (!hit && v == Menu)) ? (hit = true, (void)f(int_c<Menu>{})) : (void)0), ...);
+    return hit;
+}
+// ... any other v: Fallback
+template <int Fallback, int... Menu, class F> void dispatch_int(int v, F &&f, bool every = false)
+{
+    if (!dispatch_menu<Menu...>(v, f, every) || every) f(int_c<Fallback>{});
+}
+// activation storage: float | bf16_t
+template <class F> void dispatch_act(bool bf16, F &&f, bool every = false)
+{
+    if (every || bf16) f(type_tag<bf16_t>{});
+    if (every || !bf16) f(type_tag<float>{});
+}
+
+// Dynamic LDS above 64 KB has to be enabled per function AND per device (a process may drive several GPUs, e.g. nn.DataParallel in the
+// reference trainers).  On the first launch of any member of a family on a device, every member is prepared for that device — a warm-up
+// step therefore does all of it before a graph capture, whichever members it touches.  `done` (one static per family) holds one bit per
+// device, set only after every call succeeded.  each_member(g) calls g(kernel) for every instantiation: the family's own ladder with
+// every = true.
+constexpr size_t LARGE_LDS_BYTES = 160 * 1024;
+template <class Enumerate> int prepare_large_lds(std::atomic<uint64_t> &done, Enumerate &&each_member)
+{
+#if !defined(HIPEMU)
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return DLKA_ERR_LAUNCH;
+    const uint64_t bit = 1ull << (dev & 63);
+    if (done.load(std::memory_order_acquire) & bit) return DLKA_OK;
+    bool ok = true;
+    each_member([&](auto kernel) {
+        ok = ok && hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LARGE_LDS_BYTES) == hipSuccess;
+    });
+    if (!ok) return DLKA_ERR_LAUNCH;
+    done.fetch_or(bit, std::memory_order_release);
+#endif
+    return DLKA_OK;
+}
 
 }  // namespace dlka

@@ -222,17 +222,23 @@ def check_conv3d_cl(dev, B, C, Cout, dims, k, p, d, g, planar=False, seed=0):
     assert_close("conv3d_cl grad_bias", gb, br.grad, rtol=BWD_RTOL)
 
 
-def check_deform3d_cl(dev, B, C, Cout, dims, off_mode="normal", seed=0):
+def check_deform3d_cl(dev, B, C, Cout, dims, off_mode="normal", seed=0, dtype=torch.float32):
+    """dtype = torch.bfloat16: bf16 storage of x / out / grad_out (everything else fp32) against the oracle on the bf16-rounded activations, at the bf16
+    contract (BF16_RTOL of max |reference|, as tests/partial_grad_cases.py holds the same entry points to)."""
     x, off, w, b, go, (k3, s3, p3, d3) = make_deform3d(B, C, Cout, dims, 3, 1, 1, 1, 1, 1, off_mode, seed)
+    bf = dtype == torch.bfloat16
+    if bf:
+        x, go = x.bfloat16().float(), go.bfloat16().float()
+    fwd_tol, bwd_tol = (dict(rtol=BF16_RTOL), dict(rtol=BF16_RTOL)) if bf else (dict(atol=FWD_ATOL), dict(rtol=BWD_RTOL))
     ref = oracle.deform_conv3d_forward(x, w, b, off, 1, 1, 1, 1, 1)
-    out = ops.deform_conv3d_forward_cl(to_cl(x).to(dev), off.to(dev), w.to(dev), b.to(dev), 1, 1)
-    assert_close("deform3d_cl fwd", from_cl(out), ref, atol=FWD_ATOL)
+    out = ops.deform_conv3d_forward_cl(to_cl(x).to(dev).to(dtype), off.to(dev), w.to(dev), b.to(dev), 1, 1)
+    assert_close("deform3d_cl fwd", from_cl(out), ref, **fwd_tol)
     rgi, rgo, rgw, rgb = oracle.deform_conv3d_backward(x, w, b, off, go, 1, 1, 1, 1, 1, q1_literal=False)
-    gi, goff, gw, gb = ops.deform_conv3d_backward_cl(to_cl(x).to(dev), off.to(dev), w.to(dev), to_cl(go).to(dev), 1, 1)
-    assert_close("deform3d_cl grad_input", from_cl(gi), rgi, rtol=BWD_RTOL)
-    assert_close("deform3d_cl grad_offset", goff, rgo, rtol=BWD_RTOL)
-    assert_close("deform3d_cl grad_weight", gw, rgw, rtol=BWD_RTOL)
-    assert_close("deform3d_cl grad_bias", gb, rgb, rtol=BWD_RTOL)
+    gi, goff, gw, gb = ops.deform_conv3d_backward_cl(to_cl(x).to(dev).to(dtype), off.to(dev), w.to(dev), to_cl(go).to(dev).to(dtype), 1, 1)
+    assert_close("deform3d_cl grad_input", from_cl(gi), rgi, **bwd_tol)
+    assert_close("deform3d_cl grad_offset", goff, rgo, **bwd_tol)
+    assert_close("deform3d_cl grad_weight", gw, rgw, **bwd_tol)
+    assert_close("deform3d_cl grad_bias", gb, rgb, **bwd_tol)
 
 
 def check_deform3d_cl_gx_worst_case(dev, C, dims, B=1):

@@ -1229,3 +1229,91 @@ def test_dwconv_pipelined_row_pairs_equal_row_kernel(case, monkeypatch):
 def test_weight_preparation_tiled_equals_elementwise(bf):
     """cl_igemm.hip prep_job_tile (round 5): the LDS-tiled weight re-layout is bitwise the element-per-lane one — every prepared form of one block of each Synapse width."""
     parity.check_prep_tiled_equals_elementwise(DEV, ((32, (8, 8, 8), 1), (64, (4, 4, 4), 1), (128, (4, 4, 4), 1), (256, (4, 4, 4), 1)), torch.bfloat16 if bf else torch.float32)
+
+
+# ---- the large-LDS kernel families (dynamic LDS above 64 KB: prepared per family, csrc/dlka_common.h prepare_large_lds) -----------------------------------
+# The emulator never runs the preparation, so every member that a default code path can select has a case on the GPU; the library's launch trace names the
+# kernel that ran.
+def _kernels_launched(fn):
+    """fn() under the launch trace (include/dlka.h dlka_trace_*) -> the demangled names of the kernels the library launched, without the dlka:: prefix"""
+    from ctypes import create_string_buffer
+    from deformablelka_amd import _lib as L
+    lib = L.get_lib()
+    L.check(lib.dlka_trace_start(4096, torch.cuda.current_stream().cuda_stream), "trace_start")
+    try:
+        fn()
+    finally:
+        rc = lib.dlka_trace_stop()
+    L.check(rc, "trace_stop")
+    buf, names = create_string_buffer(512), set()
+    for i in range(lib.dlka_trace_count()):
+        L.check(lib.dlka_trace_get(i, buf, 512, None), "trace_get")
+        names.add(buf.value.decode().replace("void dlka::", "").replace("dlka::", "").split("(")[0])
+    return names
+
+
+@pytest.mark.parametrize("dims,window", [((8, 8, 16), "18, 10, 14"), ((4, 4, 32), "34, 10, 10")])
+@pytest.mark.parametrize("Cout,nkc,dtype", [(32, 1, torch.float32), (64, 2, torch.float32), (96, 0, torch.float32),
+                                            (32, 1, torch.bfloat16), (64, 2, torch.bfloat16), (128, 0, torch.bfloat16)])
+def test_deform3d_cl_gx_second_generation_members(Cout, nkc, dtype, dims, window):
+    """cl_deform_gx_fx2_kernel<SW, SH, SD, T, NKC, false> of the single-operator entry: both window shapes, fp32 and bf16 storage, one / two / any number of
+    32-wide grad_out chunks (C = 32 -> 32 | 64 | 96; bf16: 128 in place of 96, a width its FORWARD refuses) — forward and all four gradients against the
+    oracle, and the trace shows the member."""
+    names = _kernels_launched(lambda: parity.check_deform3d_cl(DEV, 1, 32, Cout, dims, off_mode="normal", seed=3, dtype=dtype))
+    t = "float" if dtype == torch.float32 else "bf16_t"
+    assert f"cl_deform_gx_fx2_kernel<{window}, {t}, {nkc}, false>" in names, sorted(n for n in names if "_gx_" in n)
+
+
+@pytest.mark.parametrize("case", [(1, 32, (2, 8, 16), None, "1, float, 8, 1"), (1, 32, (2, 8, 16), "4", "1, float, 4, 1"), (1, 32, (3, 8, 32), None, "1, float, 8, 1"),
+                                  (1, 64, (2, 32, 8), None, "2, float, 8, 1"), (1, 32, (4, 2, 32), "4", "1, float, 4, 1"), (1, 32, (2, 8, 32), "42", "1, float, 4, 2"),
+                                  (2, 64, (2, 4, 16), "4s", "2, float, 4, 1"), (1, 64, (2, 8, 16), "4", "2, float, 4, 1"), (1, 64, (2, 8, 32), "42", "2, float, 4, 2")])
+def test_conv_brick_data_gradient_members(case, monkeypatch):
+    """cl_conv_brick_kernel<NT, float, waves, row tiles> at the small volumes that DLKA_CONV_BRICK_MIN_WG=1 lets in (tests/test_parity_emu.py has the same ones on the
+    emulator): one and two column tiles on each of the three workgroup shapes, against the fp64 conv; the trace shows the member."""
+    B, C, dims, waves, member = case
+    monkeypatch.setenv("DLKA_CONV_BRICK_MIN_WG", "1")
+    monkeypatch.setenv("DLKA_CONV_BRICK", "2")   # the data gradient's brick kernel only
+    if waves == "4s":   # plane chunks split over workgroups
+        waves = "4"
+        monkeypatch.setenv("DLKA_CONV_BRICK_CSPLIT", "2")
+    if waves:
+        monkeypatch.setenv("DLKA_CONV_BRICK_WAVES", waves)
+    names = _kernels_launched(lambda: parity.check_conv3d_cl(DEV, B, C, 81, dims, 3, 1, 1, 1, planar=True, seed=3))
+    assert f"cl_conv_brick_kernel<{member}>" in names, sorted(n for n in names if "brick" in n)
+
+
+@pytest.mark.parametrize("case", [(1, 32, 32, (2, 8, 16), "1, 1"), (1, 64, 50, (2, 16, 8), "2, 2"), (2, 32, 81, (3, 8, 32), "3, 2")])
+def test_conv_brick_forward_members(case, monkeypatch):
+    """cl_conv_brick3_kernel<NT, row tiles per wave> for one, two and three column tiles of the planar output (DLKA_CONV_BRICK_MIN_WG=1), against the fp64 conv."""
+    B, C, Cout, dims, member = case
+    monkeypatch.setenv("DLKA_CONV_BRICK_MIN_WG", "1")
+    names = _kernels_launched(lambda: parity.check_conv3d_cl(DEV, B, C, Cout, dims, 3, 1, 1, 1, planar=True, seed=4))
+    assert f"cl_conv_brick3_kernel<{member}>" in names, sorted(n for n in names if "brick" in n)
+
+
+@pytest.mark.parametrize("dtype,member", [(torch.float32, "true, float"), (torch.bfloat16, "true, bf16_t")], ids=["f32", "bf16"])
+def test_deform3d_cl_gx_first_generation_fixed_point_members(dtype, member):
+    """cl_deform_gx_kernel<true, T>: the fixed-point window of the first generation, which a row longer than the second generation's widest window (W + 2 > 34) still
+    takes — a 3 x 4 x 40 volume, forward and all four gradients against the oracle."""
+    names = _kernels_launched(lambda: parity.check_deform3d_cl(DEV, 1, 32, 32, (3, 4, 40), off_mode="normal", seed=5, dtype=dtype))
+    assert f"cl_deform_gx_kernel<{member}>" in names, sorted(n for n in names if "_gx_" in n)
+
+
+@pytest.mark.parametrize("C,dims,waves,split,members", [
+    (32, (2, 8, 16), None, False, ("cl_conv_brick_kernel<1, bf16_t, 8, 1>",)), (64, (2, 8, 16), None, False, ("cl_conv_brick_kernel<2, bf16_t, 8, 1>",)),
+    (32, (2, 8, 16), "4", False, ("cl_conv_brick_kernel<1, bf16_t, 4, 1>",)), (64, (2, 8, 16), "4", False, ("cl_conv_brick_kernel<2, bf16_t, 4, 1>",)),
+    (32, (2, 8, 32), "42", False, ("cl_conv_brick_kernel<1, bf16_t, 4, 2>",)),
+    (64, (2, 8, 32), "42", False, ("cl_conv_brick_kernel<2, bf16_t, 4, 2>", "cl_deform_gx_fx2_kernel<34, 10, 10, bf16_t, 2, true>")),
+    (64, (2, 8, 16), "4", True, ("cl_conv_brick_kernel<2, float, 4, 1>",))])
+def test_lka3d_tokens_bf16_block_through_brick_kernels(C, dims, waves, split, members, monkeypatch):
+    """The bf16 token block on a small volume with the offset conv on the brick kernels (DLKA_CONV_BRICK_MIN_WG=1): the data gradient stores bf16 from each of the
+    three workgroup shapes, one and two column tiles, or (split) adds fp32 partial sums of the plane chunks into the accumulation buffer.  The 32-wide rows at C = 64
+    also take the grad_input scatter's wide window with bf16 rows."""
+    monkeypatch.setenv("DLKA_CONV_BRICK_MIN_WG", "1")
+    if waves:
+        monkeypatch.setenv("DLKA_CONV_BRICK_WAVES", waves)
+    if split:
+        monkeypatch.setenv("DLKA_CONV_BRICK_CSPLIT", "2")
+    names = _kernels_launched(lambda: parity.check_lka3d_tokens_bf16(DEV, 1, C, dims))
+    for m in members:
+        assert m in names, sorted(n for n in names if "brick" in n or "_gx_" in n)
