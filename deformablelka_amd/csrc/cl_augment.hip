@@ -23,13 +23,11 @@
 //             streaming pass; the mirror is a reversed store index of that pass.
 //
 // No atomics: every output cell is computed by one lane, and the reductions have a fixed shape, so two runs give the same bits.
-#include <atomic>
+#include "cl_pipeline.h"
 
-#include "dlka_common.h"
+DLKA_LAUNCH_COUNTER(g_aug_launches, dlka_augment_launch_count)
 
 namespace dlka {
-
-static std::atomic<long> g_aug_launches{0};   // dlka_augment_launch_count (include/dlka.h): diagnostics
 
 #define AUG_THREADS 256
 #define AUG_VPT 4                 // output voxels per lane along W
@@ -37,11 +35,7 @@ static std::atomic<long> g_aug_launches{0};   // dlka_augment_launch_count (incl
 #define AUG_STAT_BLOCKS_MAX 256   // workgroups per channel (at most)
 #define AUG_WROW (DLKA_AUG_RADIUS_MAX + 1)
 
-// ---- storage types ---------------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double aug_ld(const float *p, long i) { return (double)p[i]; }
-__device__ __forceinline__ double aug_ld(const double *p, long i) { return p[i]; }
-__device__ __forceinline__ double aug_ld(const bf16_t *p, long i) { return (double)bf16_value(p[i].v); }
-__device__ __forceinline__ double aug_ld(const int16_t *p, long i) { return (double)p[i]; }
+// ---- storage types (loads: cl_pipeline.h) -----------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void aug_st(float *p, long i, double v) { p[i] = (float)v; }
 __device__ __forceinline__ void aug_st(double *p, long i, double v) { p[i] = v; }
 __device__ __forceinline__ void aug_st(bf16_t *p, long i, double v) { p[i].v = bf16_bits((float)v); }   // through float, as torch converts
@@ -55,7 +49,7 @@ __device__ __forceinline__ double aug_round(double v)
 {
     T t;
     aug_st(&t, 0, v);
-    return aug_ld(&t, 0);
+    return ld_f64(&t, 0);
 }
 
 struct AugArgs {
@@ -72,18 +66,17 @@ struct AugLane {
 
 __device__ __forceinline__ bool aug_lane(const AugArgs &a, int channels, AugLane &l)
 {
-    const int wq = cdiv(a.out[2], AUG_VPT);
-    const long q = (long)blockIdx.x * AUG_THREADS + threadIdx.x;
-    if (q >= (long)a.B * channels * a.out[0] * a.out[1] * wq) return false;
-    long r = q / wq;
-    l.ox0 = (int)(q - r * wq) * AUG_VPT;
+    RowQuad q;
+    if (!row_quad<AUG_VPT, AUG_THREADS>((long)a.B * channels * a.out[0] * a.out[1], a.out[2], q)) return false;
+    long r = q.row;
+    l.ox0 = q.x0;
     l.oy = (int)(r % a.out[1]);
     r /= a.out[1];
     l.oz = (int)(r % a.out[0]);
     r /= a.out[0];
     l.c = (int)(r % channels);
     l.b = (int)(r / channels);
-    l.nv = min(AUG_VPT, a.out[2] - l.ox0);
+    l.nv = q.nv;
     return true;
 }
 
@@ -194,7 +187,7 @@ __global__ void __launch_bounds__(AUG_THREADS) dlka_augment_spatial_kernel(AugAr
                 for (int k1 = 0; k1 < TAPS; ++k1) {
                     const S *row = p + ((long)idx[0][k0] * e1 + idx[1][k1]) * e2;
                     for (int k2 = 0; k2 < TAPS; ++k2) {
-                        double coeff = aug_ld(row, idx[2][k2]);
+                        double coeff = ld_f64(row, idx[2][k2]);
                         if (ORDER > 0) {
                             if (RANK == 3) coeff = coeff * w[0][k0];
                             coeff = (coeff * w[1][k1]) * w[2][k2];
@@ -299,9 +292,9 @@ __global__ void __launch_bounds__(AUG_THREADS) dlka_augment_gaussian_kernel(cons
     const long s = axis == 0 ? (long)e1 * e2 : axis == 1 ? (long)e2 : 1L;
     const T *line = x + q - (long)pos * s;
     const double *w = weights + ch * AUG_WROW;
-    double tmp = aug_ld(line, (long)pos * s) * w[0];
+    double tmp = ld_f64(line, (long)pos * s) * w[0];
     for (int j = r; j >= 1; --j)
-        tmp = tmp + (aug_ld(line, (long)aug_reflect(pos - j, n) * s) + aug_ld(line, (long)aug_reflect(pos + j, n) * s)) * w[j];
+        tmp = tmp + (ld_f64(line, (long)aug_reflect(pos - j, n) * s) + ld_f64(line, (long)aug_reflect(pos + j, n) * s)) * w[j];
     aug_st(y, q, tmp);
 }
 
@@ -317,7 +310,7 @@ __global__ void __launch_bounds__(AUG_THREADS) dlka_augment_stats_kernel(const T
     const double mean = pass ? stats[4 * ch] / (double)cells : 0.0;
     double s = 0.0, mn = __builtin_inf(), mx = -__builtin_inf();
     for (long i = lo + tid; i < hi; i += AUG_THREADS) {
-        const double v = aug_ld(p, i), d = v - mean;
+        const double v = ld_f64(p, i), d = v - mean;
         s = s + (pass ? d * d : v);
         mn = fmin(mn, v);
         mx = fmax(mx, v);
@@ -379,29 +372,27 @@ __global__ void __launch_bounds__(AUG_THREADS) dlka_augment_pointwise_kernel(Aug
                                                                                 const double *st0, const double *st1, const int *flip)
 {
 #pragma clang fp contract(off)
-    const int wq = cdiv(a.e2, AUG_VPT);
-    const long q = (long)blockIdx.x * AUG_THREADS + threadIdx.x;
-    if (q >= (long)a.B * a.C * a.e0 * a.e1 * wq) return;
-    long r = q / wq;
-    const int x0 = (int)(q - r * wq) * AUG_VPT;
+    RowQuad q;
+    if (!row_quad<AUG_VPT, AUG_THREADS>((long)a.B * a.C * a.e0 * a.e1, a.e2, q)) return;
+    long r = q.row;
+    const int x0 = q.x0, nv = q.nv;
     const int iy = (int)(r % a.e1);
     r /= a.e1;
     const int iz = (int)(r % a.e0);
     const long ch = r / a.e0;
-    const int nv = min(AUG_VPT, a.e2 - x0);
     const int fl = flip ? flip[ch / a.C] : 0;
     const long in = ch * a.cells + ((long)iz * a.e1 + iy) * a.e2 + x0;
     const long orow = ch * a.cells + ((long)((fl & 1) ? a.e0 - 1 - iz : iz) * a.e1 + ((fl & 2) ? a.e1 - 1 - iy : iy)) * a.e2;
     const double *op = ops + ch * (DLKA_AUG_OPS_MAX * 6);
     const double n_cells = (double)a.cells;
     for (int v = 0; v < nv; ++v) {
-        double t = aug_ld(x, in + v);
+        double t = ld_f64(x, in + v);
         for (int k = 0; k < DLKA_AUG_OPS_MAX; ++k) {
             const double *o = op + 6 * k;
             const int code = (int)o[0];
             if (code == DLKA_AUG_OP_NONE) continue;
             if (code == DLKA_AUG_OP_NOISE) {
-                t = t + aug_ld(noise, in + v);
+                t = t + ld_f64(noise, in + v);
             } else if (code == DLKA_AUG_OP_SCALE_ADD) {
                 t = t * o[1] + o[2];
             } else if (code == DLKA_AUG_OP_CONTRAST) {
@@ -426,6 +417,9 @@ __global__ void __launch_bounds__(AUG_THREADS) dlka_augment_pointwise_kernel(Aug
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------------------------------
+static long aug_blocks(long rows, int W) { return row_quad_blocks(rows, W, AUG_VPT, AUG_THREADS); }
+static long aug_blocks(const AugArgs &a) { return aug_blocks((long)a.B * a.C * a.out[0] * a.out[1], a.out[2]); }
+
 // rank 2: the description's src[0..1] / out[0..1] are (H, W) and its third entries are 0; the kernels see a depth of one cell that is never
 // padded, and C planes per sample.
 static int aug_check(const dlka_augment_desc *d, AugArgs *a, int rank)
@@ -437,18 +431,12 @@ static int aug_check(const dlka_augment_desc *d, AugArgs *a, int rank)
     if (rank == 2 && (d->src[2] != 0 || d->out[2] != 0)) return DLKA_ERR_SHAPE;
     long sc = 1, ec = 1, oc = 1;
     a->src[0] = a->ext[0] = a->out[0] = 1;
-    for (int ax = 3 - rank; ax < 3; ++ax) {
-        const int64_t n_src = d->src[ax - (3 - rank)], n_out = d->out[ax - (3 - rank)];
-        if (n_src < 1 || n_out < 1) return DLKA_ERR_SHAPE;
-        if (n_src > 0x7fffffffL - 128 || n_out > 0x7fffffffL) return DLKA_ERR_UNSUPPORTED;
-        a->src[ax] = (int)n_src;
-        a->ext[ax] = (int)n_src + 2 * d->pad;
-        a->out[ax] = (int)n_out;
-        sc *= a->src[ax];
-        ec *= a->ext[ax];
-        oc *= a->out[ax];
-        if (sc > 0x7fffffffL || ec > 0x7fffffffL || oc > 0x7fffffffL) return DLKA_ERR_UNSUPPORTED;
-    }
+    const int64_t pad[3] = {d->pad, d->pad, d->pad};
+    const int o = 3 - rank;                   // the description's axes start at the kernels' axis o
+    const int rc = check_extents(rank, {{d->src, 0x7fffffffL - 128, a->src + o, &sc, nullptr},
+                                        {d->src, 0x7fffffffL - 128, a->ext + o, &ec, pad},
+                                        {d->out, 0x7fffffffL, a->out + o, &oc, nullptr}});
+    if (rc != DLKA_OK) return rc;
     a->B = d->B;
     a->C = d->C;
     a->order = d->order;
@@ -458,30 +446,9 @@ static int aug_check(const dlka_augment_desc *d, AugArgs *a, int rank)
     a->ext_cells = ec;
     a->out_cells = oc;
     a->cval = d->cval;
-    const long lanes = cdivl((long)a->B * a->C * a->out[0] * a->out[1] * cdiv(a->out[2], AUG_VPT), AUG_THREADS);
-    if (lanes > 0x7fffffffL) return DLKA_ERR_UNSUPPORTED;
+    if (aug_blocks(*a) > 0x7fffffffL) return DLKA_ERR_UNSUPPORTED;
     return DLKA_OK;
 }
-
-static unsigned aug_blocks(const AugArgs &a)
-{
-    return (unsigned)cdivl((long)a.B * a.C * a.out[0] * a.out[1] * cdiv(a.out[2], AUG_VPT), AUG_THREADS);
-}
-
-template <typename T, int RANK>
-static void aug_launch_spatial(const AugArgs &a, const void *x, const double *coef, void *y, const double *maps, const int32_t *plain,
-                               hipStream_t st)
-{
-    const dim3 grid(aug_blocks(a)), block(AUG_THREADS);
-    if (a.order == 0)
-        DLKA_LAUNCH((dlka_augment_spatial_kernel<T, T, 0, RANK>), grid, block, 0, st, a, (const T *)x, (const T *)x, (T *)y, maps, plain);
-    else if (a.order == 1)
-        DLKA_LAUNCH((dlka_augment_spatial_kernel<T, T, 1, RANK>), grid, block, 0, st, a, (const T *)x, (const T *)x, (T *)y, maps, plain);
-    else
-        DLKA_LAUNCH((dlka_augment_spatial_kernel<T, double, 3, RANK>), grid, block, 0, st, a, (const T *)x, coef, (T *)y, maps, plain);
-}
-
-static bool aug_dtype_ok(int dtype) { return dtype == DLKA_F32 || dtype == DLKA_BF16 || dtype == DLKA_F64 || dtype == DLKA_AUG_I16; }
 
 template <int RANK>
 static int aug_spatial(const void *x, const double *coef, void *y, const dlka_augment_desc *d, const double *maps, const int32_t *plain,
@@ -495,19 +462,20 @@ static int aug_spatial(const void *x, const double *coef, void *y, const dlka_au
     if (d->order != 0 && d->order != 1 && d->order != 3) return DLKA_ERR_UNSUPPORTED;
     if (d->order == 3 && !coef) return DLKA_ERR_NULL;
     if (d->order != 3 && d->pad != 0) return DLKA_ERR_UNSUPPORTED;
-    if (!aug_dtype_ok(d->dtype)) return DLKA_ERR_DTYPE;
-    g_aug_launches.fetch_add(1, std::memory_order_relaxed);
-    hipStream_t st = (hipStream_t)stream;
-    if (d->dtype == DLKA_F32)
-        aug_launch_spatial<float, RANK>(a, x, coef, y, maps, plain, st);
-    else if (d->dtype == DLKA_BF16)
-        aug_launch_spatial<bf16_t, RANK>(a, x, coef, y, maps, plain, st);
-    else if (d->dtype == DLKA_F64)
-        aug_launch_spatial<double, RANK>(a, x, coef, y, maps, plain, st);
-    else
-        aug_launch_spatial<int16_t, RANK>(a, x, coef, y, maps, plain, st);
-    DLKA_CHECK_LAUNCH();
-    return DLKA_OK;
+    return dispatch_storage<ST_ANY>(d->dtype, [&](auto t) -> int {
+        using T = DLKA_T(t);
+        g_aug_launches.add();
+        const dim3 grid((unsigned)aug_blocks(a)), block(AUG_THREADS);
+        hipStream_t st = (hipStream_t)stream;
+        if (a.order == 0)
+            DLKA_LAUNCH((dlka_augment_spatial_kernel<T, T, 0, RANK>), grid, block, 0, st, a, (const T *)x, (const T *)x, (T *)y, maps, plain);
+        else if (a.order == 1)
+            DLKA_LAUNCH((dlka_augment_spatial_kernel<T, T, 1, RANK>), grid, block, 0, st, a, (const T *)x, (const T *)x, (T *)y, maps, plain);
+        else
+            DLKA_LAUNCH((dlka_augment_spatial_kernel<T, double, 3, RANK>), grid, block, 0, st, a, (const T *)x, coef, (T *)y, maps, plain);
+        DLKA_CHECK_LAUNCH();
+        return DLKA_OK;
+    });
 }
 
 template <int RANK>
@@ -522,8 +490,8 @@ static int aug_spatial_labels(const int32_t *seg, int32_t *out, const dlka_augme
     if (d->order != 0 && d->order != 1) return DLKA_ERR_UNSUPPORTED;
     if (d->order == 1 && d->mode == DLKA_AUG_CONSTANT && !(d->cval < 0.5)) return DLKA_ERR_UNSUPPORTED;
     if (d->order == 0 && !(d->cval >= -2147483648.0 && d->cval <= 2147483647.0)) return DLKA_ERR_UNSUPPORTED;
-    g_aug_launches.fetch_add(1, std::memory_order_relaxed);
-    const dim3 grid(aug_blocks(a)), block(AUG_THREADS);
+    g_aug_launches.add();
+    const dim3 grid((unsigned)aug_blocks(a)), block(AUG_THREADS);
     if (d->order == 0)
         DLKA_LAUNCH((dlka_augment_labels_kernel<0, RANK>), grid, block, 0, (hipStream_t)stream, a, seg, out, maps, plain);
     else
@@ -566,33 +534,20 @@ extern "C" int dlka_augment_gaussian(const void *x, void *y, int dtype, int64_t 
     if (!x || !y || !ext || !radius || !weights) return DLKA_ERR_NULL;
     if (x == y) return DLKA_ERR_UNSUPPORTED;
     if (axis < 0 || axis > 2 || channels < 1) return DLKA_ERR_SHAPE;
-    if (!aug_dtype_ok(dtype)) return DLKA_ERR_DTYPE;
-    long cells = 1;
-    for (int ax = 0; ax < 3; ++ax) {
-        if (ext[ax] < 1) return DLKA_ERR_SHAPE;
-        if (ext[ax] > 0x3fffffffL) return DLKA_ERR_UNSUPPORTED;
-        cells *= ext[ax];
-        if (cells > 0x7fffffffL) return DLKA_ERR_UNSUPPORTED;
-    }
-    if (channels > 0x7fffffffL || cells * channels > 0x7fffffffL * (long)AUG_THREADS) return DLKA_ERR_UNSUPPORTED;
-    const long total = cells * channels;
-    g_aug_launches.fetch_add(1, std::memory_order_relaxed);
-    const dim3 grid((unsigned)cdivl(total, AUG_THREADS)), block(AUG_THREADS);
-    hipStream_t st = (hipStream_t)stream;
-    const int e0 = (int)ext[0], e1 = (int)ext[1], e2 = (int)ext[2];
-    if (dtype == DLKA_F32)
-        DLKA_LAUNCH(dlka_augment_gaussian_kernel<float>, grid, block, 0, st, (const float *)x, (float *)y, total, e0, e1, e2, axis, radius, weights);
-    else if (dtype == DLKA_BF16)
-        DLKA_LAUNCH(dlka_augment_gaussian_kernel<bf16_t>, grid, block, 0, st, (const bf16_t *)x, (bf16_t *)y, total, e0, e1, e2, axis, radius,
-                    weights);
-    else if (dtype == DLKA_F64)
-        DLKA_LAUNCH(dlka_augment_gaussian_kernel<double>, grid, block, 0, st, (const double *)x, (double *)y, total, e0, e1, e2, axis, radius,
-                    weights);
-    else
-        DLKA_LAUNCH(dlka_augment_gaussian_kernel<int16_t>, grid, block, 0, st, (const int16_t *)x, (int16_t *)y, total, e0, e1, e2, axis, radius,
-                    weights);
-    DLKA_CHECK_LAUNCH();
-    return DLKA_OK;
+    return dispatch_storage<ST_ANY>(dtype, [&](auto t) -> int {
+        using T = DLKA_T(t);
+        long cells = 1;
+        int e[3];
+        const int rc = check_extents(3, {{ext, 0x3fffffffL, e, &cells, nullptr}});
+        if (rc != DLKA_OK) return rc;
+        if (channels > 0x7fffffffL || cells * channels > 0x7fffffffL * (long)AUG_THREADS) return DLKA_ERR_UNSUPPORTED;
+        const long total = cells * channels;
+        g_aug_launches.add();
+        DLKA_LAUNCH(dlka_augment_gaussian_kernel<T>, dim3((unsigned)cdivl(total, AUG_THREADS)), dim3(AUG_THREADS), 0, (hipStream_t)stream,
+                    (const T *)x, (T *)y, total, e[0], e[1], e[2], axis, radius, weights);
+        DLKA_CHECK_LAUNCH();
+        return DLKA_OK;
+    });
 }
 
 static int aug_stat_blocks(long cells)
@@ -607,40 +562,29 @@ extern "C" size_t dlka_augment_stats_workspace_bytes(int64_t channels, int64_t c
     return (size_t)channels * (size_t)aug_stat_blocks(cells) * 3 * sizeof(double);
 }
 
-template <typename T>
-static void aug_launch_stats(const void *x, double *stats, double *partials, long channels, long cells, hipStream_t st)
-{
-    const int nblk = aug_stat_blocks(cells);
-    for (int pass = 0; pass < 2; ++pass) {
-        DLKA_LAUNCH(dlka_augment_stats_kernel<T>, dim3((unsigned)nblk, (unsigned)channels), dim3(AUG_THREADS), 0, st, (const T *)x,
-                    (const double *)stats, partials, cells, pass);
-        DLKA_LAUNCH(dlka_augment_stats_finish_kernel, dim3((unsigned)cdivl(channels, AUG_THREADS)), dim3(AUG_THREADS), 0, st,
-                    (const double *)partials, stats, (int)channels, nblk, pass);
-    }
-}
-
 extern "C" int dlka_augment_channel_stats(const void *x, double *stats, void *workspace, size_t workspace_bytes, int dtype, int64_t channels,
                                           int64_t cells, void *stream)
 {
     if (!x || !stats) return DLKA_ERR_NULL;
     if (channels < 1 || cells < 1) return DLKA_ERR_SHAPE;
     if (channels > 65535 || cells > 0x7fffffffL) return DLKA_ERR_UNSUPPORTED;
-    if (!aug_dtype_ok(dtype)) return DLKA_ERR_DTYPE;
-    if (!workspace || workspace_bytes < dlka_augment_stats_workspace_bytes(channels, cells)) return DLKA_ERR_WORKSPACE;
-    if (((uintptr_t)workspace & 7) != 0) return DLKA_ERR_WORKSPACE;
-    g_aug_launches.fetch_add(4, std::memory_order_relaxed);
-    hipStream_t st = (hipStream_t)stream;
-    double *partials = (double *)workspace;
-    if (dtype == DLKA_F32)
-        aug_launch_stats<float>(x, stats, partials, channels, cells, st);
-    else if (dtype == DLKA_BF16)
-        aug_launch_stats<bf16_t>(x, stats, partials, channels, cells, st);
-    else if (dtype == DLKA_F64)
-        aug_launch_stats<double>(x, stats, partials, channels, cells, st);
-    else
-        aug_launch_stats<int16_t>(x, stats, partials, channels, cells, st);
-    DLKA_CHECK_LAUNCH();
-    return DLKA_OK;
+    return dispatch_storage<ST_ANY>(dtype, [&](auto t) -> int {
+        using T = DLKA_T(t);
+        if (!workspace || workspace_bytes < dlka_augment_stats_workspace_bytes(channels, cells)) return DLKA_ERR_WORKSPACE;
+        if (((uintptr_t)workspace & 7) != 0) return DLKA_ERR_WORKSPACE;
+        g_aug_launches.add(4);
+        hipStream_t st = (hipStream_t)stream;
+        double *partials = (double *)workspace;
+        const int nblk = aug_stat_blocks(cells);
+        for (int pass = 0; pass < 2; ++pass) {
+            DLKA_LAUNCH(dlka_augment_stats_kernel<T>, dim3((unsigned)nblk, (unsigned)channels), dim3(AUG_THREADS), 0, st, (const T *)x,
+                        (const double *)stats, partials, (long)cells, pass);
+            DLKA_LAUNCH(dlka_augment_stats_finish_kernel, dim3((unsigned)cdivl(channels, AUG_THREADS)), dim3(AUG_THREADS), 0, st,
+                        (const double *)partials, stats, (int)channels, nblk, pass);
+        }
+        DLKA_CHECK_LAUNCH();
+        return DLKA_OK;
+    });
 }
 
 extern "C" int dlka_augment_pointwise(const void *x, const void *noise, void *y, int dtype, int64_t B, int64_t C, const int64_t *ext,
@@ -649,41 +593,25 @@ extern "C" int dlka_augment_pointwise(const void *x, const void *noise, void *y,
     if (!x || !y || !ext || !ops) return DLKA_ERR_NULL;
     if (x == y) return DLKA_ERR_UNSUPPORTED;
     if (B < 1 || C < 1) return DLKA_ERR_SHAPE;
-    if (!aug_dtype_ok(dtype)) return DLKA_ERR_DTYPE;
-    AugPw a;
-    long cells = 1;
-    for (int ax = 0; ax < 3; ++ax) {
-        if (ext[ax] < 1) return DLKA_ERR_SHAPE;
-        if (ext[ax] > 0x7fffffffL) return DLKA_ERR_UNSUPPORTED;
-        cells *= ext[ax];
-        if (cells > 0x7fffffffL) return DLKA_ERR_UNSUPPORTED;
-    }
-    if (B > 0x7fffffffL || C > 0x7fffffffL || B * C > 0x7fffffffL) return DLKA_ERR_UNSUPPORTED;
-    a.B = (int)B;
-    a.C = (int)C;
-    a.e0 = (int)ext[0];
-    a.e1 = (int)ext[1];
-    a.e2 = (int)ext[2];
-    a.cells = cells;
-    const long blocks = cdivl(B * C * a.e0 * a.e1 * cdiv(a.e2, AUG_VPT), AUG_THREADS);
-    if (blocks > 0x7fffffffL) return DLKA_ERR_UNSUPPORTED;
-    g_aug_launches.fetch_add(1, std::memory_order_relaxed);
-    const dim3 grid((unsigned)blocks), block(AUG_THREADS);
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == DLKA_F32)
-        DLKA_LAUNCH(dlka_augment_pointwise_kernel<float>, grid, block, 0, st, a, (const float *)x, (const float *)noise, (float *)y, ops, stats0,
-                    stats1, flip);
-    else if (dtype == DLKA_BF16)
-        DLKA_LAUNCH(dlka_augment_pointwise_kernel<bf16_t>, grid, block, 0, st, a, (const bf16_t *)x, (const bf16_t *)noise, (bf16_t *)y, ops,
-                    stats0, stats1, flip);
-    else if (dtype == DLKA_F64)
-        DLKA_LAUNCH(dlka_augment_pointwise_kernel<double>, grid, block, 0, st, a, (const double *)x, (const double *)noise, (double *)y, ops,
-                    stats0, stats1, flip);
-    else
-        DLKA_LAUNCH(dlka_augment_pointwise_kernel<int16_t>, grid, block, 0, st, a, (const int16_t *)x, (const int16_t *)noise, (int16_t *)y, ops,
-                    stats0, stats1, flip);
-    DLKA_CHECK_LAUNCH();
-    return DLKA_OK;
+    return dispatch_storage<ST_ANY>(dtype, [&](auto t) -> int {
+        using T = DLKA_T(t);
+        AugPw a;
+        int e[3];
+        a.cells = 1;
+        const int rc = check_extents(3, {{ext, 0x7fffffffL, e, &a.cells, nullptr}});
+        if (rc != DLKA_OK) return rc;
+        if (B > 0x7fffffffL || C > 0x7fffffffL || B * C > 0x7fffffffL) return DLKA_ERR_UNSUPPORTED;
+        a.B = (int)B;
+        a.C = (int)C;
+        a.e0 = e[0];
+        a.e1 = e[1];
+        a.e2 = e[2];
+        const long blocks = aug_blocks(B * C * a.e0 * a.e1, a.e2);
+        if (blocks > 0x7fffffffL) return DLKA_ERR_UNSUPPORTED;
+        g_aug_launches.add();
+        DLKA_LAUNCH(dlka_augment_pointwise_kernel<T>, dim3((unsigned)blocks), dim3(AUG_THREADS), 0, (hipStream_t)stream, a, (const T *)x,
+                    (const T *)noise, (T *)y, ops, stats0, stats1, flip);
+        DLKA_CHECK_LAUNCH();
+        return DLKA_OK;
+    });
 }
-
-extern "C" long dlka_augment_launch_count(void) { return g_aug_launches.load(std::memory_order_relaxed); }

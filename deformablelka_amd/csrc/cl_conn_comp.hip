@@ -30,13 +30,11 @@
 // Determinism: the partition is the transitive closure of the neighbour relation, whatever order the atomics land in; the root of a component is
 // its minimum raster index; sizes and root counts are integer sums; the per-entry maxima are maxima.  The tree SHAPES differ between runs, and
 // nothing derived from them is kept: parent[] is workspace.  Two runs give the same bits in every output.
-#include <atomic>
+#include "cl_pipeline.h"
 
-#include "dlka_common.h"
+DLKA_LAUNCH_COUNTER(g_cc_launches, dlka_cc_launch_count)
 
 namespace dlka {
-
-static std::atomic<long> g_cc_launches{0};   // dlka_cc_launch_count (include/dlka.h): diagnostics
 
 #define CC_THREADS 256
 #define CC_PER 8                          // cells per lane in the tile and block passes
@@ -296,31 +294,16 @@ __global__ __launch_bounds__(CC_THREADS) void dlka_cc_table_kernel(unsigned N, c
     owner[r] = ent[i];
 }
 
-static int cc_label_bytes(int dt)
-{
-    switch (dt) {
-        case DLKA_SD_U8: return 1;
-        case DLKA_SD_I16: return 2;
-        case DLKA_SD_I32: return 4;
-        case DLKA_SD_I64: return 8;
-        default: return 0;
-    }
-}
-
 static int cc_check(const dlka_cc_desc *d)
 {
     if (!d) return DLKA_ERR_NULL;
     if (d->rank < 1 || d->rank > 3) return DLKA_ERR_SHAPE;
     if (d->connectivity < 1 || d->connectivity > d->rank) return DLKA_ERR_UNSUPPORTED;
-    if (!cc_label_bytes(d->label_dtype)) return DLKA_ERR_DTYPE;
+    if (!label_bytes(d->label_dtype)) return DLKA_ERR_DTYPE;
     if (d->K < 1 || d->K > DLKA_CC_K_MAX) return DLKA_ERR_UNSUPPORTED;
-    long cells = 1;
-    for (int ax = 0; ax < 3; ++ax) {
-        if (d->ext[ax] < 1) return DLKA_ERR_SHAPE;
-        if (d->ext[ax] > 0x7fffffffL) return DLKA_ERR_UNSUPPORTED;
-        cells *= (long)d->ext[ax];
-        if (cells > 0x7fffffffL) return DLKA_ERR_UNSUPPORTED;   // (reversed indices and CC_NONE share 32 bits)
-    }
+    long cells = 1;                           // (below 2^31: reversed indices and CC_NONE share 32 bits)
+    const int rc = check_extents(3, {{d->ext, 0x7fffffffL, nullptr, &cells, nullptr}});
+    if (rc != DLKA_OK) return rc;
     for (int ax = 0; ax < 3 - d->rank; ++ax)
         if (d->ext[ax] != 1) return DLKA_ERR_SHAPE;
     if (d->mask_mode) {
@@ -377,7 +360,7 @@ static int cc_run(const CcArgs &a, const CcWs &w, const void *image, unsigned *l
     const long ntiles = cdivl(a.ext[2], 1L << a.lw) * cdivl(a.ext[1], 1L << a.lh) * cdivl(a.ext[0], 1L << a.ld);
     const unsigned cellgrid = (unsigned)cdivl((long)a.N, CC_THREADS);
     if (hipMemsetAsync(summary, 0, DLKA_CC_SUMMARY * sizeof(unsigned), st) != hipSuccess) return DLKA_ERR_LAUNCH;
-    g_cc_launches.fetch_add(6, std::memory_order_relaxed);
+    g_cc_launches.add(6);
     auto local = dlka_cc_local_kernel<L>;
     auto output = dlka_cc_output_kernel<L>;
     DLKA_LAUNCH(local, dim3((unsigned)ntiles), dim3(CC_THREADS), 0, st, a, (const L *)image, w.parent, w.ent, w.cnt);
@@ -419,12 +402,9 @@ extern "C" int dlka_cc_components(const void *image, const dlka_cc_desc *d, void
     const CcWs w = cc_ws(a, workspace);
     if (!workspace || workspace_bytes < w.bytes) return DLKA_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
-    switch (d->label_dtype) {
-        case DLKA_SD_U8: return cc_run<uint8_t>(a, w, image, (unsigned *)labels, filtered, (unsigned *)summary, st);
-        case DLKA_SD_I16: return cc_run<int16_t>(a, w, image, (unsigned *)labels, filtered, (unsigned *)summary, st);
-        case DLKA_SD_I32: return cc_run<int32_t>(a, w, image, (unsigned *)labels, filtered, (unsigned *)summary, st);
-        default: return cc_run<int64_t>(a, w, image, (unsigned *)labels, filtered, (unsigned *)summary, st);
-    }
+    return dispatch_label(d->label_dtype, [&](auto t) {
+        return cc_run<DLKA_T(t)>(a, w, image, (unsigned *)labels, filtered, (unsigned *)summary, st);
+    });
 }
 
 extern "C" int dlka_cc_component_table(const dlka_cc_desc *d, const void *workspace, size_t workspace_bytes, int64_t capacity, int64_t *sizes,
@@ -438,11 +418,9 @@ extern "C" int dlka_cc_component_table(const dlka_cc_desc *d, const void *worksp
     const CcArgs a = cc_args(d);
     const CcWs w = cc_ws(a, const_cast<void *>(workspace));
     if (!workspace || workspace_bytes < w.bytes) return DLKA_ERR_WORKSPACE;
-    g_cc_launches.fetch_add(1, std::memory_order_relaxed);
+    g_cc_launches.add();
     DLKA_LAUNCH(dlka_cc_table_kernel, dim3((unsigned)cdivl((long)a.N, CC_THREADS)), dim3(CC_THREADS), 0, (hipStream_t)stream, a.N,
                 (const unsigned char *)w.ent, (const int *)w.cnt, (const unsigned *)w.parent, (long)capacity, sizes, owner);
     DLKA_CHECK_LAUNCH();
     return DLKA_OK;
 }
-
-extern "C" long dlka_cc_launch_count(void) { return g_cc_launches.load(std::memory_order_relaxed); }

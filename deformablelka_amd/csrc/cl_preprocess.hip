@@ -21,13 +21,11 @@
 //
 // Determinism: minima, maxima and integer sums do not depend on the order the atomics land in; the float64 sums are folded in a fixed order
 // without atomics.  Two runs give the same bits in every output.
-#include <atomic>
+#include "cl_pipeline.h"
 
-#include "dlka_common.h"
+DLKA_LAUNCH_COUNTER(g_prep_launches, dlka_prep_launch_count)
 
 namespace dlka {
-
-static std::atomic<long> g_prep_launches{0};   // dlka_prep_launch_count (include/dlka.h): diagnostics
 
 #define PREP_THREADS 256
 #define PREP_PER 4
@@ -385,13 +383,9 @@ static int prep_check(const dlka_prep_desc *d)
     if (d->rank < 2 || d->rank > 3) return DLKA_ERR_SHAPE;
     if (d->C < 1) return DLKA_ERR_SHAPE;
     if (d->C > DLKA_PREP_C_MAX) return DLKA_ERR_UNSUPPORTED;
-    long cells = 1;
-    for (int ax = 0; ax < 3; ++ax) {
-        if (d->ext[ax] < 1) return DLKA_ERR_SHAPE;
-        if (d->ext[ax] > 0x7fffffffL) return DLKA_ERR_UNSUPPORTED;
-        cells *= (long)d->ext[ax];
-        if (cells > 0x7fffffffL) return DLKA_ERR_UNSUPPORTED;   // (component numbers and the box are 32-bit)
-    }
+    long cells = 1;                           // (below 2^31: component numbers and the box are 32-bit)
+    const int rc = check_extents(3, {{d->ext, 0x7fffffffL, nullptr, &cells, nullptr}});
+    if (rc != DLKA_OK) return rc;
     if (d->rank == 2 && d->ext[0] != 1) return DLKA_ERR_SHAPE;
     return DLKA_OK;
 }
@@ -455,7 +449,7 @@ extern "C" int dlka_prep_background(const float *data, const dlka_prep_desc *d, 
     if (rc != DLKA_OK) return rc;
     if (!data || !background) return DLKA_ERR_NULL;
     const PrepArgs a = prep_args(d);
-    g_prep_launches.fetch_add(1, std::memory_order_relaxed);
+    g_prep_launches.add();
     DLKA_LAUNCH(dlka_prep_background_kernel, dim3(prep_grid(a.N)), dim3(PREP_THREADS), 0, (hipStream_t)stream, data, (unsigned char *)background,
                 a.N, a.C);
     DLKA_CHECK_LAUNCH();
@@ -478,7 +472,7 @@ extern "C" int dlka_prep_fill_bbox(const uint8_t *background, const int32_t *lab
     if (!workspace || workspace_bytes < (size_t)a.N + 1) return DLKA_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     if (hipMemsetAsync(workspace, 0, (size_t)a.N + 1, st) != hipSuccess) return DLKA_ERR_LAUNCH;
-    g_prep_launches.fetch_add(3, std::memory_order_relaxed);
+    g_prep_launches.add(3);
     return prep_box_pass(background, labels, (const unsigned char *)workspace, mask, box, a, st);
 }
 
@@ -487,7 +481,7 @@ extern "C" int dlka_prep_mask_bbox(const uint8_t *mask, const dlka_prep_desc *d,
     const int rc = prep_check(d);
     if (rc != DLKA_OK) return rc;
     if (!mask || !box) return DLKA_ERR_NULL;
-    g_prep_launches.fetch_add(2, std::memory_order_relaxed);
+    g_prep_launches.add(2);
     return prep_box_pass(mask, nullptr, nullptr, nullptr, box, prep_args(d), (hipStream_t)stream);
 }
 
@@ -508,7 +502,7 @@ extern "C" int dlka_prep_crop(const float *data, const int32_t *seg, const uint8
         a.cext[ax] = (int)(d->hi[ax] - d->lo[ax]);
         a.NC *= (long)a.cext[ax];
     }
-    g_prep_launches.fetch_add(1, std::memory_order_relaxed);
+    g_prep_launches.add();
     DLKA_LAUNCH(dlka_prep_crop_kernel, dim3(prep_grid(a.NC)), dim3(PREP_THREADS), 0, (hipStream_t)stream, data, (const int *)seg,
                 (const unsigned char *)mask, out, (int *)seg_out, a);
     DLKA_CHECK_LAUNCH();
@@ -532,7 +526,7 @@ extern "C" int dlka_prep_channel_stats(const float *data, const int32_t *seg, co
     const int nblk = prep_stat_blocks(a.N);
     hipStream_t st = (hipStream_t)stream;
     double *partials = (double *)workspace;
-    g_prep_launches.fetch_add(4, std::memory_order_relaxed);
+    g_prep_launches.add(4);
     for (int pass = 0; pass < 2; ++pass) {
         DLKA_LAUNCH(dlka_prep_stats_kernel, dim3((unsigned)nblk, (unsigned)a.C), dim3(PREP_THREADS), 0, st, data, (const int *)seg,
                     (const double *)table, partials, a.N, pass);
@@ -550,11 +544,9 @@ extern "C" int dlka_prep_normalize(const float *data, const int32_t *seg, const 
     if (rc != DLKA_OK) return rc;
     if (!data || !seg || !table || !out) return DLKA_ERR_NULL;
     const PrepArgs a = prep_args(d);
-    g_prep_launches.fetch_add(1, std::memory_order_relaxed);
+    g_prep_launches.add();
     DLKA_LAUNCH(dlka_prep_normalize_kernel, dim3(prep_grid(a.N), (unsigned)a.C), dim3(PREP_THREADS), 0, (hipStream_t)stream, data,
                 (const int *)seg, table, out, a.N);
     DLKA_CHECK_LAUNCH();
     return DLKA_OK;
 }
-
-extern "C" long dlka_prep_launch_count(void) { return g_prep_launches.load(std::memory_order_relaxed); }

@@ -23,11 +23,10 @@
 //
 // No atomics, no reduction across lanes: every output cell is computed by one lane from the inputs alone, so two runs give the same bits.
 #include "cl_resample.h"
-#include "dlka_common.h"
+
+DLKA_LAUNCH_COUNTER(g_rs_launches, dlka_resample_launch_count)   // cl_spline.hip's launches count here too
 
 namespace dlka {
-
-std::atomic<long> g_rs_launches{0};   // dlka_resample_launch_count (include/dlka.h): diagnostics; cl_spline.hip's launches count here too
 
 #define RS_THREADS 256
 #define RS_VPT 4                          // output voxels per lane along the contiguous axis in the argmax / linear kernels
@@ -71,14 +70,12 @@ struct RsLane {
 template <typename T>
 __device__ __forceinline__ bool rs_lane(const RsArgs &a, const int *idx, const double *w, RsLane<T> &l)
 {
-    const int wq = cdiv(a.out[2], RS_VPT);
-    const long q = (long)blockIdx.x * RS_THREADS + threadIdx.x;
-    if (q >= (long)a.out[0] * a.out[1] * wq) return false;
-    const long r = q / wq;
-    l.ox0 = (int)(q - r * wq) * RS_VPT;
-    l.oy = (int)(r % a.out[1]);
-    l.oz = (int)(r / a.out[1]);
-    l.nv = min(RS_VPT, a.out[2] - l.ox0);
+    RowQuad q;
+    if (!row_quad<RS_VPT, RS_THREADS>((long)a.out[0] * a.out[1], a.out[2], q)) return false;
+    l.ox0 = q.x0;
+    l.oy = (int)(q.row % a.out[1]);
+    l.oz = (int)(q.row / a.out[1]);
+    l.nv = q.nv;
     for (int k = 0; k < 2; ++k) {
         l.i0[k] = idx[2 * (a.off[0] + l.oz) + k];
         l.w0[k] = (T)w[2 * (a.off[0] + l.oz) + k];
@@ -225,16 +222,12 @@ static int rs_check(const dlka_resample_desc *d, int tap_hi, RsArgs *a)
 {
     if (!d) return DLKA_ERR_NULL;
     if (d->C < 1) return DLKA_ERR_SHAPE;
-    long ic = 1, oc = 1, off = 0;
+    long ic = 1, oc = 1;
+    const int rc = check_extents(3, {{d->in, 0x7fffffffL, a->in, &ic, nullptr}, {d->out, 0x7fffffffL, a->out, &oc, nullptr}},
+                                 [&](int ax) { return d->taps[ax] != 1 && d->taps[ax] != tap_hi ? (int)DLKA_ERR_UNSUPPORTED : (int)DLKA_OK; });
+    if (rc != DLKA_OK) return rc;
+    long off = 0;
     for (int ax = 0; ax < 3; ++ax) {
-        if (d->in[ax] < 1 || d->out[ax] < 1) return DLKA_ERR_SHAPE;
-        if (d->in[ax] > 0x7fffffffL || d->out[ax] > 0x7fffffffL) return DLKA_ERR_UNSUPPORTED;
-        if (d->taps[ax] != 1 && d->taps[ax] != tap_hi) return DLKA_ERR_UNSUPPORTED;
-        ic *= d->in[ax];
-        oc *= d->out[ax];
-        if (ic > 0x7fffffffL || oc > 0x7fffffffL) return DLKA_ERR_UNSUPPORTED;
-        a->in[ax] = (int)d->in[ax];
-        a->out[ax] = (int)d->out[ax];
         a->taps[ax] = d->taps[ax];
         a->off[ax] = (int)off;
         off += d->out[ax];
@@ -245,20 +238,7 @@ static int rs_check(const dlka_resample_desc *d, int tap_hi, RsArgs *a)
     return DLKA_OK;
 }
 
-static unsigned rs_lane_blocks(const RsArgs &a) { return (unsigned)cdivl((long)a.out[0] * a.out[1] * cdiv(a.out[2], RS_VPT), RS_THREADS); }
-
-template <typename T>
-static void rs_launch_argmax(const RsArgs &a, const void *x, uint8_t *labels, const int32_t *idx, const double *w, const int32_t *region,
-                             hipStream_t st)
-{
-    const dim3 grid(rs_lane_blocks(a)), block(RS_THREADS);
-    if (a.taps[0] == 1 && a.taps[1] == 2 && a.taps[2] == 2)
-        DLKA_LAUNCH((dlka_resample_argmax_kernel<T, 1>), grid, block, 0, st, a, (const T *)x, labels, idx, w, region);
-    else if (a.taps[0] == 2 && a.taps[1] == 2 && a.taps[2] == 2)
-        DLKA_LAUNCH((dlka_resample_argmax_kernel<T, 2>), grid, block, 0, st, a, (const T *)x, labels, idx, w, region);
-    else
-        DLKA_LAUNCH((dlka_resample_argmax_kernel<T, 0>), grid, block, 0, st, a, (const T *)x, labels, idx, w, region);
-}
+static unsigned rs_lane_blocks(const RsArgs &a) { return (unsigned)row_quad_blocks((long)a.out[0] * a.out[1], a.out[2], RS_VPT, RS_THREADS); }
 
 }  // namespace dlka
 
@@ -271,15 +251,19 @@ extern "C" int dlka_resample_argmax(const void *x, uint8_t *labels, const dlka_r
     const int rc = rs_check(d, 2, &a);
     if (rc != DLKA_OK) return rc;
     if (!x || !labels || !idx || !w) return DLKA_ERR_NULL;
-    if (d->dtype != DLKA_F32 && d->dtype != DLKA_F64) return DLKA_ERR_DTYPE;
-    if (d->C > 256) return DLKA_ERR_UNSUPPORTED;   // a label is one byte
-    g_rs_launches.fetch_add(1, std::memory_order_relaxed);
-    if (d->dtype == DLKA_F32)
-        rs_launch_argmax<float>(a, x, labels, idx, w, region_class, (hipStream_t)stream);
-    else
-        rs_launch_argmax<double>(a, x, labels, idx, w, region_class, (hipStream_t)stream);
-    DLKA_CHECK_LAUNCH();
-    return DLKA_OK;
+    return dispatch_storage<ST_F32 | ST_F64>(d->dtype, [&](auto t) -> int {
+        using T = DLKA_T(t);
+        if (d->C > 256) return DLKA_ERR_UNSUPPORTED;   // a label is one byte
+        g_rs_launches.add();
+        // kernel MODE 1: taps (1, 2, 2); 2: (2, 2, 2); 0: anything else
+        const int mode = a.taps[1] == 2 && a.taps[2] == 2 ? a.taps[0] : 0;
+        dispatch_int<0, 1, 2>(mode, [&](auto m) {
+            DLKA_LAUNCH((dlka_resample_argmax_kernel<T, DLKA_V(m)>), dim3(rs_lane_blocks(a)), dim3(RS_THREADS), 0, (hipStream_t)stream, a,
+                        (const T *)x, labels, idx, w, region_class);
+        });
+        DLKA_CHECK_LAUNCH();
+        return DLKA_OK;
+    });
 }
 
 extern "C" int dlka_resample_linear(const void *x, void *y, const dlka_resample_desc *d, const int32_t *idx, const double *w, void *stream)
@@ -289,15 +273,14 @@ extern "C" int dlka_resample_linear(const void *x, void *y, const dlka_resample_
     if (rc != DLKA_OK) return rc;
     if (!x || !y || !idx || !w) return DLKA_ERR_NULL;
     if (x == y) return DLKA_ERR_UNSUPPORTED;
-    if (d->dtype != DLKA_F32 && d->dtype != DLKA_F64) return DLKA_ERR_DTYPE;
-    g_rs_launches.fetch_add(1, std::memory_order_relaxed);
-    const dim3 grid(rs_lane_blocks(a)), block(RS_THREADS);
-    if (d->dtype == DLKA_F32)
-        DLKA_LAUNCH(dlka_resample_linear_kernel<float>, grid, block, 0, (hipStream_t)stream, a, (const float *)x, (float *)y, idx, w);
-    else
-        DLKA_LAUNCH(dlka_resample_linear_kernel<double>, grid, block, 0, (hipStream_t)stream, a, (const double *)x, (double *)y, idx, w);
-    DLKA_CHECK_LAUNCH();
-    return DLKA_OK;
+    return dispatch_storage<ST_F32 | ST_F64>(d->dtype, [&](auto t) -> int {
+        using T = DLKA_T(t);
+        g_rs_launches.add();
+        DLKA_LAUNCH(dlka_resample_linear_kernel<T>, dim3(rs_lane_blocks(a)), dim3(RS_THREADS), 0, (hipStream_t)stream, a, (const T *)x, (T *)y,
+                    idx, w);
+        DLKA_CHECK_LAUNCH();
+        return DLKA_OK;
+    });
 }
 
 extern "C" int dlka_resample_labels(const int32_t *seg, int32_t *out, const dlka_resample_desc *d, const int32_t *idx, const double *w,
@@ -309,7 +292,7 @@ extern "C" int dlka_resample_labels(const int32_t *seg, int32_t *out, const dlka
     if (!seg || !out || !idx || !w) return DLKA_ERR_NULL;
     if (seg == out) return DLKA_ERR_UNSUPPORTED;
     if ((long)a.C * a.out_cells > 0x7fffffffL) return DLKA_ERR_UNSUPPORTED;
-    g_rs_launches.fetch_add(1, std::memory_order_relaxed);
+    g_rs_launches.add();
     DLKA_LAUNCH(dlka_resample_labels_kernel, dim3((unsigned)cdivl((long)a.C * a.out_cells, RS_THREADS)), dim3(RS_THREADS), 0,
                 (hipStream_t)stream, a, seg, out, idx, w, strict);
     DLKA_CHECK_LAUNCH();
@@ -325,11 +308,9 @@ extern "C" int dlka_resample_spline_eval(const double *coef, double *y, const dl
     if (!coef || !y || !start || !w4 || !lo || !hi) return DLKA_ERR_NULL;
     if (clip_axis > 2) return DLKA_ERR_SHAPE;
     if (d->C != 1) return DLKA_ERR_UNSUPPORTED;
-    g_rs_launches.fetch_add(1, std::memory_order_relaxed);
+    g_rs_launches.add();
     DLKA_LAUNCH(dlka_resample_spline_eval_kernel, dim3((unsigned)cdivl(a.out_cells, RS_THREADS)), dim3(RS_THREADS), 0, (hipStream_t)stream, a,
                 coef, y, start, w4, lo, hi, clip_axis);
     DLKA_CHECK_LAUNCH();
     return DLKA_OK;
 }
-
-extern "C" long dlka_resample_launch_count(void) { return g_rs_launches.load(std::memory_order_relaxed); }

@@ -15,14 +15,13 @@
 //
 // Memory-bound: the forward reads the logits and the labels once, the backward reads them once and writes the gradient once.  A label that is
 // not an integer in [0, K) decodes to -1, which matches no class and indexes nothing.
-#include <atomic>
 #include <math.h>
 
-#include "dlka_common.h"
+#include "cl_pipeline.h"
+
+DLKA_LAUNCH_COUNTER(g_seg_loss_launches, dlka_seg_loss_launch_count)
 
 namespace dlka {
-
-static std::atomic<long> g_seg_loss_launches{0};   // dlka_seg_loss_launch_count (include/dlka.h): diagnostics
 
 #define SEG_THREADS 256
 #define SEG_GROUPS (SEG_THREADS / 8)   // 8-lane groups per workgroup: rows of the LDS reduction
@@ -413,12 +412,13 @@ static void seg_launch_k(const SegArgs &a, const SegCall &c, int vec)
 
 static void seg_dispatch(const dlka_seg_loss_desc *d, const SegArgs &a, const SegCall &c, int vec)
 {
-    g_seg_loss_launches.fetch_add(1, std::memory_order_relaxed);
-    const bool bf = d->dtype == DLKA_BF16, i64 = d->label_dtype == DLKA_LABEL_I64;
-    if (bf && i64) seg_launch_k<bf16_t, int64_t>(a, c, vec);
-    else if (bf) seg_launch_k<bf16_t, float>(a, c, vec);
-    else if (i64) seg_launch_k<float, int64_t>(a, c, vec);
-    else seg_launch_k<float, float>(a, c, vec);
+    g_seg_loss_launches.add();
+    dispatch_storage<ST_F32 | ST_BF16>(d->dtype, [&](auto t) -> int {
+        dispatch_bool(d->label_dtype == DLKA_LABEL_I64, [&](auto i64) {
+            seg_launch_k<DLKA_T(t), std::conditional_t<DLKA_V(i64), int64_t, float>>(a, c, vec);
+        });
+        return DLKA_OK;
+    });
 }
 
 }  // namespace dlka
@@ -447,7 +447,7 @@ extern "C" int dlka_seg_loss_forward(const void *logits, const void *labels, con
     SegCall c = {SEG_FWD, logits, labels, workspace, nullptr, nullptr, dim3((unsigned)G, (unsigned)d->B), st};
     seg_dispatch(d, a, c, vec);
     DLKA_CHECK_LAUNCH();
-    g_seg_loss_launches.fetch_add(1, std::memory_order_relaxed);
+    g_seg_loss_launches.add();
     DLKA_LAUNCH(dlka_seg_loss_finish_kernel, dim3(1), dim3(SEG_THREADS), 0, st, a, (int)G, (const float *)workspace, loss, dc, stats, coef);
     DLKA_CHECK_LAUNCH();
     return DLKA_OK;
@@ -483,10 +483,8 @@ extern "C" int dlka_seg_eval_counts(const void *logits, const void *labels, cons
     SegCall c = {SEG_EVAL, logits, labels, workspace, nullptr, nullptr, dim3((unsigned)G, (unsigned)d->B), st};
     seg_dispatch(d, a, c, vec);
     DLKA_CHECK_LAUNCH();
-    g_seg_loss_launches.fetch_add(1, std::memory_order_relaxed);
+    g_seg_loss_launches.add();
     DLKA_LAUNCH(dlka_seg_eval_finish_kernel, dim3(1), dim3(64), 0, st, (int)d->B, (int)d->K, (int)G, (const int *)workspace, counts);
     DLKA_CHECK_LAUNCH();
     return DLKA_OK;
 }
-
-extern "C" long dlka_seg_loss_launch_count(void) { return g_seg_loss_launches.load(std::memory_order_relaxed); }

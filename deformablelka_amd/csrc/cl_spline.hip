@@ -10,7 +10,6 @@
 //
 // No atomics, no reduction across lanes: two runs give the same bits.
 #include "cl_resample.h"
-#include "dlka_common.h"
 
 namespace dlka {
 
@@ -85,26 +84,24 @@ using namespace dlka;
 extern "C" int dlka_spline_pad(const void *x, double *padded, int dtype, const int64_t *in, const int64_t *pad, void *stream)
 {
     if (!x || !padded || !in || !pad) return DLKA_ERR_NULL;
-    if (dtype != DLKA_F32 && dtype != DLKA_F64) return DLKA_ERR_DTYPE;
-    SplPad a;
-    a.cells = 1;
-    for (int ax = 0; ax < 3; ++ax) {
-        if (in[ax] < 1 || pad[ax] < 0) return DLKA_ERR_SHAPE;
-        if (pad[ax] > SPL_PAD_MAX || in[ax] > 0x7fffffffL - 2 * SPL_PAD_MAX) return DLKA_ERR_UNSUPPORTED;
-        a.in[ax] = (int)in[ax];
-        a.pad[ax] = (int)pad[ax];
-        a.ext[ax] = (int)(in[ax] + 2 * pad[ax]);
-        a.cells *= a.ext[ax];
-        if (a.cells > 0x7fffffffL) return DLKA_ERR_UNSUPPORTED;
-    }
-    g_rs_launches.fetch_add(1, std::memory_order_relaxed);
-    const dim3 grid((unsigned)cdivl(a.cells, SPL_THREADS)), block(SPL_THREADS);
-    if (dtype == DLKA_F32)
-        DLKA_LAUNCH(dlka_spline_pad_kernel<float>, grid, block, 0, (hipStream_t)stream, a, (const float *)x, padded);
-    else
-        DLKA_LAUNCH(dlka_spline_pad_kernel<double>, grid, block, 0, (hipStream_t)stream, a, (const double *)x, padded);
-    DLKA_CHECK_LAUNCH();
-    return DLKA_OK;
+    return dispatch_storage<ST_F32 | ST_F64>(dtype, [&](auto t) -> int {
+        using T = DLKA_T(t);
+        SplPad a;
+        a.cells = 1;
+        const int rc = check_extents(3, {{in, 0x7fffffffL - 2 * SPL_PAD_MAX, a.ext, &a.cells, pad}}, [&](int ax) {
+            return pad[ax] < 0 ? (int)DLKA_ERR_SHAPE : pad[ax] > SPL_PAD_MAX ? (int)DLKA_ERR_UNSUPPORTED : (int)DLKA_OK;
+        });
+        if (rc != DLKA_OK) return rc;
+        for (int ax = 0; ax < 3; ++ax) {
+            a.in[ax] = (int)in[ax];
+            a.pad[ax] = (int)pad[ax];
+        }
+        g_rs_launches.add();
+        DLKA_LAUNCH(dlka_spline_pad_kernel<T>, dim3((unsigned)cdivl(a.cells, SPL_THREADS)), dim3(SPL_THREADS), 0, (hipStream_t)stream, a,
+                    (const T *)x, padded);
+        DLKA_CHECK_LAUNCH();
+        return DLKA_OK;
+    });
 }
 
 extern "C" int dlka_spline_prefilter(double *coef, const int64_t *ext, int axis, int boundary, void *stream)
@@ -113,20 +110,14 @@ extern "C" int dlka_spline_prefilter(double *coef, const int64_t *ext, int axis,
     if (axis < 0 || axis > 2) return DLKA_ERR_SHAPE;
     if (boundary != DLKA_SPLINE_REFLECT && boundary != DLKA_SPLINE_MIRROR) return DLKA_ERR_UNSUPPORTED;
     long cells = 1;
-    for (int ax = 0; ax < 3; ++ax) {
-        if (ext[ax] < 1) return DLKA_ERR_SHAPE;
-        if (ext[ax] > 0x7fffffffL) return DLKA_ERR_UNSUPPORTED;
-        cells *= ext[ax];
-        if (cells > 0x7fffffffL) return DLKA_ERR_UNSUPPORTED;
-    }
-    g_rs_launches.fetch_add(1, std::memory_order_relaxed);
-    const dim3 grid((unsigned)cdivl(cells / ext[axis], SPL_THREADS)), block(SPL_THREADS);
-    if (boundary == DLKA_SPLINE_MIRROR)
-        DLKA_LAUNCH(dlka_spline_prefilter_kernel<DLKA_SPLINE_MIRROR>, grid, block, 0, (hipStream_t)stream, coef, (int)ext[0], (int)ext[1],
-                    (int)ext[2], axis);
-    else
-        DLKA_LAUNCH(dlka_spline_prefilter_kernel<DLKA_SPLINE_REFLECT>, grid, block, 0, (hipStream_t)stream, coef, (int)ext[0], (int)ext[1],
-                    (int)ext[2], axis);
+    int e[3];
+    const int rc = check_extents(3, {{ext, 0x7fffffffL, e, &cells, nullptr}});
+    if (rc != DLKA_OK) return rc;
+    g_rs_launches.add();
+    dispatch_menu<DLKA_SPLINE_MIRROR, DLKA_SPLINE_REFLECT>(boundary, [&](auto b) {
+        DLKA_LAUNCH(dlka_spline_prefilter_kernel<DLKA_V(b)>, dim3((unsigned)cdivl(cells / e[axis], SPL_THREADS)), dim3(SPL_THREADS), 0,
+                    (hipStream_t)stream, coef, e[0], e[1], e[2], axis);
+    });
     DLKA_CHECK_LAUNCH();
     return DLKA_OK;
 }

@@ -22,14 +22,13 @@
 // kernels return SQUARED distances; the square root is the caller's (IEEE on the host for the values a metric returns).
 // Cropping to the box of a | b is exact: outside it both masks are 0, which is what the array's outside counts as, and no border cell
 // lies outside it.  No atomics; every output cell is written by exactly one lane: two runs give the same bits.
-#include <atomic>
 #include <math.h>
 
-#include "dlka_common.h"
+#include "cl_pipeline.h"
+
+DLKA_LAUNCH_COUNTER(g_sd_launches, dlka_sd_launch_count)
 
 namespace dlka {
-
-static std::atomic<long> g_sd_launches{0};   // dlka_sd_launch_count (include/dlka.h): diagnostics
 
 #define SD_THREADS 256
 #define SD_KC 4          // classes per workgroup of the stats pass
@@ -272,30 +271,18 @@ __global__ __launch_bounds__(SD_THREADS) void dlka_sd_axis_kernel(const SdArgs a
         if (inb && i[r] < n) out[base + (long)i[r] * S] = SAMPLE ? (need[r] ? acc[r] : -1.0) : acc[r];
 }
 
-static int sd_label_bytes(int dt)
-{
-    switch (dt) {
-        case DLKA_SD_U8: return 1;
-        case DLKA_SD_I16: return 2;
-        case DLKA_SD_I32: return 4;
-        case DLKA_SD_I64: return 8;
-        default: return 0;
-    }
-}
-
 static int sd_check(const dlka_sd_desc *d)
 {
     if (!d) return DLKA_ERR_NULL;
     if (d->rank != 2 && d->rank != 3) return DLKA_ERR_SHAPE;
     if (d->connectivity < 1 || d->connectivity > d->rank) return DLKA_ERR_UNSUPPORTED;
-    if (!sd_label_bytes(d->label_dtype)) return DLKA_ERR_DTYPE;
+    if (!label_bytes(d->label_dtype)) return DLKA_ERR_DTYPE;
     if (d->K < 1 || d->K > DLKA_SD_K_MAX) return DLKA_ERR_UNSUPPORTED;
     long cells = 1;
-    for (int ax = 0; ax < 3; ++ax) {
-        if (d->ext[ax] < 1 || d->ext[ax] > 0x7fffffffL) return DLKA_ERR_SHAPE;
-        cells *= (long)d->ext[ax];
-        if (cells > 0x7fffffffL) return DLKA_ERR_UNSUPPORTED;
-    }
+    // (an extent over 2^31 - 1 is a bad shape here, not an unsupported one)
+    const int rc = check_extents(3, {{d->ext, 0x7fffffffL, nullptr, &cells, nullptr}},
+                                 [&](int ax) { return d->ext[ax] > 0x7fffffffL ? (int)DLKA_ERR_SHAPE : (int)DLKA_OK; });
+    if (rc != DLKA_OK) return rc;
     if (d->rank == 2 && d->ext[0] != 1) return DLKA_ERR_SHAPE;
     if (d->ext[2] > SD_MAX_W) return DLKA_ERR_UNSUPPORTED;
     for (int ax = 3 - d->rank; ax < 3; ++ax)
@@ -346,22 +333,15 @@ static long sd_stat_groups(const dlka_sd_desc *d)
     return rows < 1024 ? rows : 1024;
 }
 
-template <typename L>
-static void sd_launch(const dlka_sd_desc *d, const SdArgs &a, int what, const void *p, const void *q, int *ws, dim3 grid, hipStream_t st)
-{
-    g_sd_launches.fetch_add(1, std::memory_order_relaxed);
-    if (what == 0) { auto k = dlka_sd_stats_kernel<L>; DLKA_LAUNCH(k, grid, dim3(SD_THREADS), 0, st, a, (const L *)p, (const L *)q, ws); }
-    else { auto k = dlka_sd_line_kernel<L>; DLKA_LAUNCH(k, grid, dim3(SD_THREADS), 0, st, a, (const L *)p, (const L *)q, ws); }
-}
-
 static void sd_dispatch(const dlka_sd_desc *d, const SdArgs &a, int what, const void *p, const void *q, int *ws, dim3 grid, hipStream_t st)
 {
-    switch (d->label_dtype) {
-        case DLKA_SD_U8: sd_launch<uint8_t>(d, a, what, p, q, ws, grid, st); break;
-        case DLKA_SD_I16: sd_launch<int16_t>(d, a, what, p, q, ws, grid, st); break;
-        case DLKA_SD_I32: sd_launch<int32_t>(d, a, what, p, q, ws, grid, st); break;
-        default: sd_launch<int64_t>(d, a, what, p, q, ws, grid, st); break;
-    }
+    dispatch_label(d->label_dtype, [&](auto t) -> int {
+        using L = DLKA_T(t);
+        g_sd_launches.add();
+        if (what == 0) { auto k = dlka_sd_stats_kernel<L>; DLKA_LAUNCH(k, grid, dim3(SD_THREADS), 0, st, a, (const L *)p, (const L *)q, ws); }
+        else { auto k = dlka_sd_line_kernel<L>; DLKA_LAUNCH(k, grid, dim3(SD_THREADS), 0, st, a, (const L *)p, (const L *)q, ws); }
+        return DLKA_OK;
+    });
 }
 
 }  // namespace dlka
@@ -386,7 +366,7 @@ extern "C" int dlka_sd_label_stats(const void *prediction, const void *label, co
     hipStream_t st = (hipStream_t)stream;
     sd_dispatch(d, a, 0, prediction, label, (int *)workspace, dim3((unsigned)G, (unsigned)cdivl(d->K, SD_KC)), st);
     DLKA_CHECK_LAUNCH();
-    g_sd_launches.fetch_add(1, std::memory_order_relaxed);
+    g_sd_launches.add();
     DLKA_LAUNCH(dlka_sd_stats_finish_kernel, dim3(1), dim3(SD_THREADS), 0, st, (int)d->K, (int)G, (const int *)workspace, stats);
     DLKA_CHECK_LAUNCH();
     return DLKA_OK;
@@ -421,7 +401,7 @@ extern "C" int dlka_sd_distances(const void *prediction, const void *label, cons
     const unsigned M = 2u * (unsigned)d->K;
     sd_dispatch(d, a, 1, prediction, label, dw, dim3((unsigned)lines, M), st);
     DLKA_CHECK_LAUNCH();
-    g_sd_launches.fetch_add(2, std::memory_order_relaxed);
+    g_sd_launches.add(2);
     auto along_h = dlka_sd_axis_kernel<true, false>;
     auto along_d = dlka_sd_axis_kernel<false, true>;
     DLKA_LAUNCH(along_h, dim3((unsigned)tiles1, M), dim3(SD_THREADS), 0, st, a, 1, (const int *)dw, (const double *)nullptr, g2);
@@ -430,5 +410,3 @@ extern "C" int dlka_sd_distances(const void *prediction, const void *label, cons
     DLKA_CHECK_LAUNCH();
     return DLKA_OK;
 }
-
-extern "C" long dlka_sd_launch_count(void) { return g_sd_launches.load(std::memory_order_relaxed); }

@@ -16,14 +16,13 @@
 // workgroup, so every load and store of a wave covers consecutive words (in reverse lane order where z is flipped: the same lines).
 // The per-row index arithmetic (divisions by the extents) is wave-uniform and paid once per row.  Softmax over K runs in registers:
 // K is bucketed into a compile-time bound (4 / 8 / 16 / 32) so that the per-class arrays stay in VGPRs.
-#include <atomic>
 #include <math.h>
 
-#include "dlka_common.h"
+#include "cl_pipeline.h"
+
+DLKA_LAUNCH_COUNTER(g_tiles_launches, dlka_tiles_launch_count)
 
 namespace dlka {
-
-static std::atomic<long> g_tiles_launches{0};   // dlka_tiles_launch_count (include/dlka.h): diagnostics
 
 struct TilesArgs {
     int T, M, C, K;
@@ -38,6 +37,7 @@ struct TilesArgs {
 };
 
 #define TILES_ROWS 4   // z-rows (waves) per workgroup
+static long tiles_blocks(long rows) { return cdivl(rows, TILES_ROWS); }
 
 __global__ __launch_bounds__(64 * TILES_ROWS) void dlka_tiles_gather_kernel(const TilesArgs a, const float *__restrict__ x,
                                                                           float *__restrict__ out, long nrows)
@@ -215,9 +215,9 @@ extern "C" int dlka_tiles_gather(const float *x, int C, int X, int Y, int Z, con
     if (rc != DLKA_OK) return rc;
     a.C = C; a.X = X; a.Y = Y; a.Z = Z; a.lx = pad_x; a.ly = pad_y; a.lz = pad_z; a.pad_value = pad_value;
     const long nrows = (long)T * M * C * pd * ph;
-    const long blocks = (nrows + TILES_ROWS - 1) / TILES_ROWS;
+    const long blocks = tiles_blocks(nrows);
     if (blocks > 0x7fffffffL) return DLKA_ERR_UNSUPPORTED;
-    g_tiles_launches.fetch_add(1, std::memory_order_relaxed);
+    g_tiles_launches.add();
     DLKA_LAUNCH(dlka_tiles_gather_kernel, dim3((unsigned)blocks), dim3(64, TILES_ROWS), 0, (hipStream_t)stream, a, x, out, nrows);
     DLKA_CHECK_LAUNCH();
     return DLKA_OK;
@@ -228,31 +228,30 @@ extern "C" int dlka_tiles_blend(const void *logits, int dtype, int K, int nonlin
                                 void *stream)
 {
     if (!logits || !score || !weight) return DLKA_ERR_NULL;
-    if (dtype != DLKA_F32 && dtype != DLKA_BF16) return DLKA_ERR_DTYPE;
-    if (K <= 0 || Xp <= 0 || Yp <= 0 || Zp <= 0) return DLKA_ERR_SHAPE;
-    if (K > DLKA_TILES_K_MAX || nonlin < DLKA_TILES_IDENTITY || nonlin > DLKA_TILES_SIGMOID) return DLKA_ERR_UNSUPPORTED;
-    TilesArgs a = {};
-    const int rc = tiles_chunk_args(a, origins, T, masks, M, pd, ph, pw);
-    if (rc != DLKA_OK) return rc;
-    a.K = K; a.Xp = Xp; a.Yp = Yp; a.Zp = Zp; a.scale = mirror_scale;
-    int lo[3] = {Xp, Yp, Zp}, hi[3] = {0, 0, 0};
-    const int ext[3] = {Xp, Yp, Zp}, p[3] = {pd, ph, pw};
-    for (int t = 0; t < T; ++t)
-        for (int d = 0; d < 3; ++d) {
-            const int o = origins[3 * t + d];
-            if (o < 0 || o + p[d] > ext[d]) return DLKA_ERR_SHAPE;   // every tile lies inside the score map
-            lo[d] = o < lo[d] ? o : lo[d];
-            hi[d] = o + p[d] > hi[d] ? o + p[d] : hi[d];
-        }
-    a.bx0 = lo[0]; a.by0 = lo[1]; a.bz0 = lo[2];
-    a.bxn = hi[0] - lo[0]; a.byn = hi[1] - lo[1]; a.bzn = hi[2] - lo[2];
-    const long blocks = ((long)a.bxn * a.byn + TILES_ROWS - 1) / TILES_ROWS;
-    g_tiles_launches.fetch_add(1, std::memory_order_relaxed);
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == DLKA_BF16) launch_blend_t<bf16_t>(a, nonlin, (const bf16_t *)logits, gauss, score, weight, (unsigned)blocks, st);
-    else launch_blend_t<float>(a, nonlin, (const float *)logits, gauss, score, weight, (unsigned)blocks, st);
-    DLKA_CHECK_LAUNCH();
-    return DLKA_OK;
+    return dispatch_storage<ST_F32 | ST_BF16>(dtype, [&](auto tag) -> int {
+        if (K <= 0 || Xp <= 0 || Yp <= 0 || Zp <= 0) return DLKA_ERR_SHAPE;
+        if (K > DLKA_TILES_K_MAX || nonlin < DLKA_TILES_IDENTITY || nonlin > DLKA_TILES_SIGMOID) return DLKA_ERR_UNSUPPORTED;
+        TilesArgs a = {};
+        const int rc = tiles_chunk_args(a, origins, T, masks, M, pd, ph, pw);
+        if (rc != DLKA_OK) return rc;
+        a.K = K; a.Xp = Xp; a.Yp = Yp; a.Zp = Zp; a.scale = mirror_scale;
+        int lo[3] = {Xp, Yp, Zp}, hi[3] = {0, 0, 0};
+        const int ext[3] = {Xp, Yp, Zp}, p[3] = {pd, ph, pw};
+        for (int t = 0; t < T; ++t)
+            for (int d = 0; d < 3; ++d) {
+                const int o = origins[3 * t + d];
+                if (o < 0 || o + p[d] > ext[d]) return DLKA_ERR_SHAPE;   // every tile lies inside the score map
+                lo[d] = o < lo[d] ? o : lo[d];
+                hi[d] = o + p[d] > hi[d] ? o + p[d] : hi[d];
+            }
+        a.bx0 = lo[0]; a.by0 = lo[1]; a.bz0 = lo[2];
+        a.bxn = hi[0] - lo[0]; a.byn = hi[1] - lo[1]; a.bzn = hi[2] - lo[2];
+        g_tiles_launches.add();
+        launch_blend_t(a, nonlin, (const DLKA_T(tag) *)logits, gauss, score, weight, (unsigned)tiles_blocks((long)a.bxn * a.byn),
+                       (hipStream_t)stream);
+        DLKA_CHECK_LAUNCH();
+        return DLKA_OK;
+    });
 }
 
 extern "C" int dlka_tiles_finalize(const float *score, const float *weight, int K, int Xp, int Yp, int Zp, int pad_x, int pad_y, int pad_z, int X,
@@ -263,11 +262,8 @@ extern "C" int dlka_tiles_finalize(const float *score, const float *weight, int 
     if (pad_x + X > Xp || pad_y + Y > Yp || pad_z + Z > Zp) return DLKA_ERR_SHAPE;
     TilesArgs a = {};
     a.K = K; a.Xp = Xp; a.Yp = Yp; a.Zp = Zp; a.lx = pad_x; a.ly = pad_y; a.lz = pad_z; a.X = X; a.Y = Y; a.Z = Z;
-    const long blocks = ((long)X * Y + TILES_ROWS - 1) / TILES_ROWS;
-    g_tiles_launches.fetch_add(1, std::memory_order_relaxed);
-    DLKA_LAUNCH(dlka_tiles_finalize_kernel, dim3((unsigned)blocks), dim3(64, TILES_ROWS), 0, (hipStream_t)stream, a, score, weight, probs, seg);
+    g_tiles_launches.add();
+    DLKA_LAUNCH(dlka_tiles_finalize_kernel, dim3((unsigned)tiles_blocks((long)X * Y)), dim3(64, TILES_ROWS), 0, (hipStream_t)stream, a, score, weight, probs, seg);
     DLKA_CHECK_LAUNCH();
     return DLKA_OK;
 }
-
-extern "C" long dlka_tiles_launch_count(void) { return g_tiles_launches.load(std::memory_order_relaxed); }

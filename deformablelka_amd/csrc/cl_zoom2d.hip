@@ -20,13 +20,11 @@
 //
 // No atomics, no reduction across lanes: every output cell is computed by one lane from the inputs alone, so two runs give the same bits.  Tap
 // and source indices are mirrored / range-checked in the lane, so no table can make a kernel read outside its input.
-#include <atomic>
+#include "cl_pipeline.h"
 
-#include "dlka_common.h"
+DLKA_LAUNCH_COUNTER(g_zm_launches, dlka_zoom2d_launch_count)
 
 namespace dlka {
-
-static std::atomic<long> g_zm_launches{0};   // dlka_zoom2d_launch_count (include/dlka.h): diagnostics
 
 #define ZM_THREADS 256
 #define ZM_VPT 4                             // output pixels per lane along W
@@ -42,14 +40,7 @@ struct ZmArgs {
     float mean, std;
 };
 
-// ---- storage types ---------------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double zm_ld(const double *p, long i) { return p[i]; }
-__device__ __forceinline__ double zm_ld(const float *p, long i) { return (double)p[i]; }
-__device__ __forceinline__ double zm_ld(const bf16_t *p, long i) { return (double)bf16_value(p[i].v); }
-__device__ __forceinline__ double zm_ld(const int16_t *p, long i) { return (double)p[i]; }
-__device__ __forceinline__ float zm_ldf(const float *p, long i) { return p[i]; }
-__device__ __forceinline__ float zm_ldf(const bf16_t *p, long i) { return bf16_value(p[i].v); }
-
+// ---- storage types (loads: cl_pipeline.h) -----------------------------------------------------------------------------------------------------
 // The float64 sum of one pixel in its storage type.
 __device__ __forceinline__ float zm_f32(double t, const ZmArgs &a)
 {
@@ -148,7 +139,7 @@ __global__ void __launch_bounds__(ZM_THREADS) dlka_zoom2d_spline_kernel(ZmArgs a
             double t = 0.0;                                    // cval
             if (rin && cin[v]) {
                 for (int kr = 0; kr < TAPS; ++kr)
-                    for (int kc = 0; kc < TAPS; ++kc) t = t + (zm_ld(p, ro[kr] + ci[v][kc]) * rw[kr]) * cw[v][kc];
+                    for (int kc = 0; kc < TAPS; ++kc) t = t + (ld_f64(p, ro[kr] + ci[v][kc]) * rw[kr]) * cw[v][kc];
             }
             zm_finish(&res[v], t, a);
         }
@@ -163,14 +154,12 @@ struct ZmLane {
 
 __device__ __forceinline__ bool zm_lane(const ZmArgs &a, ZmLane &l)
 {
-    const int wq = cdiv(a.ow, ZM_VPT);
-    const long q = (long)blockIdx.x * ZM_THREADS + threadIdx.x;
-    if (q >= (long)a.N * a.oh * wq) return false;
-    const long r = q / wq;
-    l.ox0 = (int)(q - r * wq) * ZM_VPT;
-    l.oy = (int)(r % a.oh);
-    l.n = (int)(r / a.oh);
-    l.nv = min(ZM_VPT, a.ow - l.ox0);
+    RowQuad q;
+    if (!row_quad<ZM_VPT, ZM_THREADS>((long)a.N * a.oh, a.ow, q)) return false;
+    l.ox0 = q.x0;
+    l.oy = (int)(q.row % a.oh);
+    l.n = (int)(q.row / a.oh);
+    l.nv = q.nv;
     return true;
 }
 
@@ -208,10 +197,10 @@ __global__ void __launch_bounds__(ZM_THREADS) dlka_zoom2d_argmax_kernel(ZmArgs a
             const int sc = idx[a.oh + l.ox0 + v];
             if ((unsigned)sc >= (unsigned)a.iw) continue;      // outside: 0
             if (sc != prev) {
-                float best = zm_ldf(p, sc);
+                float best = act_load1(p, sc);
                 int lab = 0;
                 for (int c = 1; c < a.K; ++c) {
-                    const float val = zm_ldf(p, (long)c * plane + sc);
+                    const float val = act_load1(p, (long)c * plane + sc);
                     if (val > best) {                          // the first maximum
                         best = val;
                         lab = c;
@@ -231,19 +220,15 @@ static int zm_check(const dlka_zoom2d_desc *d, ZmArgs *a)
 {
     if (!d) return DLKA_ERR_NULL;
     if (d->N < 1) return DLKA_ERR_SHAPE;
-    long ic = d->N, oc = d->N;
-    for (int ax = 0; ax < 2; ++ax) {
-        if (d->in[ax] < 1 || d->out[ax] < 1) return DLKA_ERR_SHAPE;
-        if (d->in[ax] > 0x3fffffffL || d->out[ax] > 0x3fffffffL || d->N > 0x7fffffffL) return DLKA_ERR_UNSUPPORTED;
-        ic *= d->in[ax];
-        oc *= d->out[ax];
-        if (ic > 0x7fffffffL || oc > 0x7fffffffL) return DLKA_ERR_UNSUPPORTED;
-    }
+    long ic = d->N, oc = d->N;                // (an N over 2^31 - 1 is refused as a cell count, after the first axis' extents)
+    int in[2], out[2];
+    const int rc = check_extents(2, {{d->in, 0x3fffffffL, in, &ic, nullptr}, {d->out, 0x3fffffffL, out, &oc, nullptr}});
+    if (rc != DLKA_OK) return rc;
     a->N = (int)d->N;
-    a->ih = (int)d->in[0];
-    a->iw = (int)d->in[1];
-    a->oh = (int)d->out[0];
-    a->ow = (int)d->out[1];
+    a->ih = in[0];
+    a->iw = in[1];
+    a->oh = out[0];
+    a->ow = out[1];
     a->ctiles = cdiv(a->ow, ZM_COLS);
     a->rtiles = cdiv(a->oh, ZM_TILE_ROWS);
     a->K = 1;
@@ -253,14 +238,7 @@ static int zm_check(const dlka_zoom2d_desc *d, ZmArgs *a)
     return DLKA_OK;
 }
 
-static unsigned zm_lane_blocks(const ZmArgs &a) { return (unsigned)cdivl((long)a.N * a.oh * cdiv(a.ow, ZM_VPT), ZM_THREADS); }
-
-template <typename S, typename O, int TAPS>
-static void zm_launch_spline(const ZmArgs &a, const void *src, void *y, const int32_t *start, const double *w4, hipStream_t st)
-{
-    const dim3 grid((unsigned)((long)a.N * a.rtiles * a.ctiles)), block(ZM_THREADS);
-    DLKA_LAUNCH((dlka_zoom2d_spline_kernel<S, O, TAPS>), grid, block, 0, st, a, (const S *)src, (O *)y, start, w4);
-}
+static unsigned zm_lane_blocks(const ZmArgs &a) { return (unsigned)row_quad_blocks((long)a.N * a.oh, a.ow, ZM_VPT, ZM_THREADS); }
 
 }  // namespace dlka
 
@@ -285,27 +263,21 @@ extern "C" int dlka_zoom2d_spline(const void *src, void *y, const dlka_zoom2d_de
         return DLKA_ERR_UNSUPPORTED;
     }
     if (a.normalize && (out == DLKA_ZOOM2D_I16 || !(d->std == d->std) || d->std == 0.f)) return DLKA_ERR_UNSUPPORTED;
-    g_zm_launches.fetch_add(1, std::memory_order_relaxed);
-    hipStream_t st = (hipStream_t)stream;
-    if (d->taps == 4) {
-        if (out == DLKA_F32)
-            zm_launch_spline<double, float, 4>(a, src, y, start, w4, st);
-        else if (out == DLKA_BF16)
-            zm_launch_spline<double, bf16_t, 4>(a, src, y, start, w4, st);
-        else
-            zm_launch_spline<double, int16_t, 4>(a, src, y, start, w4, st);
-    } else if (in == DLKA_F32) {
-        if (out == DLKA_F32)
-            zm_launch_spline<float, float, 2>(a, src, y, start, w4, st);
-        else
-            zm_launch_spline<float, bf16_t, 2>(a, src, y, start, w4, st);
-    } else if (in == DLKA_BF16) {
-        zm_launch_spline<bf16_t, bf16_t, 2>(a, src, y, start, w4, st);
-    } else {
-        zm_launch_spline<int16_t, int16_t, 2>(a, src, y, start, w4, st);
-    }
-    DLKA_CHECK_LAUNCH();
-    return DLKA_OK;
+    g_zm_launches.add();
+    const dim3 grid((unsigned)((long)a.N * a.rtiles * a.ctiles)), block(ZM_THREADS);
+    auto launch = [&](auto s, auto o, auto taps) -> int {
+        using S = DLKA_T(s);
+        using O = DLKA_T(o);
+        DLKA_LAUNCH((dlka_zoom2d_spline_kernel<S, O, DLKA_V(taps)>), grid, block, 0, (hipStream_t)stream, a, (const S *)src, (O *)y, start, w4);
+        DLKA_CHECK_LAUNCH();
+        return DLKA_OK;
+    };
+    if (d->taps == 4) return dispatch_storage<ST_F32 | ST_BF16 | ST_I16>(out, [&](auto o) { return launch(type_tag<double>{}, o, int_c<4>{}); });
+    return dispatch_storage<ST_F32 | ST_BF16 | ST_I16>(in, [&](auto s) {      // two taps: the output has the input's type, or float -> bf16
+        if constexpr (std::is_same<DLKA_T(s), float>::value)
+            if (out == DLKA_BF16) return launch(s, type_tag<bf16_t>{}, int_c<2>{});
+        return launch(s, s, int_c<2>{});
+    });
 }
 
 extern "C" int dlka_zoom2d_nearest(const void *x, void *y, const dlka_zoom2d_desc *d, int elem_bytes, const int32_t *idx, void *stream)
@@ -315,20 +287,15 @@ extern "C" int dlka_zoom2d_nearest(const void *x, void *y, const dlka_zoom2d_des
     if (rc != DLKA_OK) return rc;
     if (!x || !y || !idx) return DLKA_ERR_NULL;
     if (x == y) return DLKA_ERR_UNSUPPORTED;
-    if (elem_bytes != 1 && elem_bytes != 2 && elem_bytes != 4 && elem_bytes != 8) return DLKA_ERR_DTYPE;
-    g_zm_launches.fetch_add(1, std::memory_order_relaxed);
-    const dim3 grid(zm_lane_blocks(a)), block(ZM_THREADS);
-    hipStream_t st = (hipStream_t)stream;
-    if (elem_bytes == 1)
-        DLKA_LAUNCH(dlka_zoom2d_nearest_kernel<uint8_t>, grid, block, 0, st, a, (const uint8_t *)x, (uint8_t *)y, idx);
-    else if (elem_bytes == 2)
-        DLKA_LAUNCH(dlka_zoom2d_nearest_kernel<uint16_t>, grid, block, 0, st, a, (const uint16_t *)x, (uint16_t *)y, idx);
-    else if (elem_bytes == 4)
-        DLKA_LAUNCH(dlka_zoom2d_nearest_kernel<uint32_t>, grid, block, 0, st, a, (const uint32_t *)x, (uint32_t *)y, idx);
-    else
-        DLKA_LAUNCH(dlka_zoom2d_nearest_kernel<uint64_t>, grid, block, 0, st, a, (const uint64_t *)x, (uint64_t *)y, idx);
-    DLKA_CHECK_LAUNCH();
-    return DLKA_OK;
+    // an element of 1, 2, 4 or 8 bytes moves as the unsigned integer of the label type of that size
+    const int code = elem_bytes == 1 ? DLKA_SD_U8 : elem_bytes == 2 ? DLKA_SD_I16 : elem_bytes == 4 ? DLKA_SD_I32 : elem_bytes == 8 ? DLKA_SD_I64 : -1;
+    return dispatch_label(code, [&](auto t) -> int {
+        using U = std::make_unsigned_t<DLKA_T(t)>;
+        g_zm_launches.add();
+        DLKA_LAUNCH(dlka_zoom2d_nearest_kernel<U>, dim3(zm_lane_blocks(a)), dim3(ZM_THREADS), 0, (hipStream_t)stream, a, (const U *)x, (U *)y, idx);
+        DLKA_CHECK_LAUNCH();
+        return DLKA_OK;
+    });
 }
 
 extern "C" int dlka_zoom2d_argmax(const void *logits, uint8_t *labels, const dlka_zoom2d_desc *d, int K, const int32_t *idx, void *stream)
@@ -339,16 +306,12 @@ extern "C" int dlka_zoom2d_argmax(const void *logits, uint8_t *labels, const dlk
     if (!logits || !labels || !idx) return DLKA_ERR_NULL;
     if (K < 1) return DLKA_ERR_SHAPE;
     if (K > DLKA_ZOOM2D_K_MAX) return DLKA_ERR_UNSUPPORTED;   // a label is one byte
-    if (d->in_dtype != DLKA_F32 && d->in_dtype != DLKA_BF16) return DLKA_ERR_DTYPE;
     a.K = K;
-    g_zm_launches.fetch_add(1, std::memory_order_relaxed);
-    const dim3 grid(zm_lane_blocks(a)), block(ZM_THREADS);
-    if (d->in_dtype == DLKA_F32)
-        DLKA_LAUNCH(dlka_zoom2d_argmax_kernel<float>, grid, block, 0, (hipStream_t)stream, a, (const float *)logits, labels, idx);
-    else
-        DLKA_LAUNCH(dlka_zoom2d_argmax_kernel<bf16_t>, grid, block, 0, (hipStream_t)stream, a, (const bf16_t *)logits, labels, idx);
-    DLKA_CHECK_LAUNCH();
-    return DLKA_OK;
+    return dispatch_storage<ST_F32 | ST_BF16>(d->in_dtype, [&](auto t) -> int {
+        using T = DLKA_T(t);
+        g_zm_launches.add();
+        DLKA_LAUNCH(dlka_zoom2d_argmax_kernel<T>, dim3(zm_lane_blocks(a)), dim3(ZM_THREADS), 0, (hipStream_t)stream, a, (const T *)logits, labels, idx);
+        DLKA_CHECK_LAUNCH();
+        return DLKA_OK;
+    });
 }
-
-extern "C" long dlka_zoom2d_launch_count(void) { return g_zm_launches.load(std::memory_order_relaxed); }

@@ -2,6 +2,7 @@
 from __future__ import annotations
 
 import ctypes
+import math
 from ctypes import byref
 from typing import Optional, Sequence, Tuple
 
@@ -1086,6 +1087,13 @@ def seg_loss_launch_count() -> int:
 _SD_DTYPES = {torch.uint8: L.DLKA_SD_U8, torch.bool: L.DLKA_SD_U8, torch.int16: L.DLKA_SD_I16, torch.int32: L.DLKA_SD_I32, torch.int64: L.DLKA_SD_I64}
 
 
+def _rank_padded_ext(d, shape):
+    """d.rank and d.ext of a description whose kernels always see three axes: the leading extents of a lower rank are 1."""
+    d.rank = len(shape)
+    for ax in range(3):
+        d.ext[ax] = 1 if ax < 3 - d.rank else int(shape[ax - (3 - d.rank)])
+
+
 def _sd_desc(prediction, label, class_ids=None, voxelspacing=None, connectivity=1):
     """Checks of the pair of maps and the description of the call; ``class_ids=None``: the maps are masks (value != 0)."""
     L.require_device(prediction, label)
@@ -1120,9 +1128,9 @@ def _sd_desc(prediction, label, class_ids=None, voxelspacing=None, connectivity=
     if not 1 <= len(ids) <= L.DLKA_SD_K_MAX:
         raise RuntimeError(f"surface distances: between 1 and {L.DLKA_SD_K_MAX} classes per call, got {len(ids)}")
     d = L.SurfaceDistDesc()
-    d.rank, d.connectivity, d.label_dtype, d.K, d.mask_mode = rank, connectivity, _SD_DTYPES[prediction.dtype], len(ids), int(class_ids is None)
+    d.connectivity, d.label_dtype, d.K, d.mask_mode = connectivity, _SD_DTYPES[prediction.dtype], len(ids), int(class_ids is None)
+    _rank_padded_ext(d, prediction.shape)
     for ax in range(3):
-        d.ext[ax] = 1 if ax < 3 - rank else int(prediction.shape[ax - (3 - rank)])
         d.spacing[ax] = 1.0 if ax < 3 - rank else spacing[ax - (3 - rank)]
     for k, c in enumerate(ids):
         d.class_id[k] = c
@@ -1188,9 +1196,8 @@ def _cc_desc(image, entries=None, connectivity=1, min_counts=None):
     if not 1 <= connectivity <= rank:
         raise RuntimeError(f"connected components: connectivity must be between 1 and the rank ({rank}), got {connectivity}")
     d = L.ConnCompDesc()
-    d.rank, d.connectivity, d.label_dtype, d.mask_mode = rank, connectivity, _SD_DTYPES[image.dtype], int(entries is None)
-    for ax in range(3):
-        d.ext[ax] = 1 if ax < 3 - rank else int(image.shape[ax - (3 - rank)])
+    d.connectivity, d.label_dtype, d.mask_mode = connectivity, _SD_DTYPES[image.dtype], int(entries is None)
+    _rank_padded_ext(d, image.shape)
     if entries is None:
         d.K, d.n_ids = 1, 0
     else:
@@ -1386,36 +1393,83 @@ def resample_launch_count() -> int:
 _AUG_DTYPES = {torch.float32: L.DLKA_F32, torch.bfloat16: L.DLKA_BF16, torch.float64: L.DLKA_F64, torch.int16: L.DLKA_AUG_I16}
 
 
-def _aug_volume(x, what):
+# rank 3: volumes (b, c, x, y, z).  rank 2, the dummy-2D branch: (b, p, y, z), p the planes of a sample (channels x depth slices); the
+# description's third extents are 0.  The words the messages of a rank use:
+_AUG_WORDS = {3: ("(b, c, x, y, z)", "channel", "three", "volumes"), 2: ("(b, p, y, z)", "plane", "two", "planes")}
+
+
+def _aug_volume(x, what, rank=3):
     L.require_device(x)
-    if x.ndim != 5 or x.numel() == 0:
-        raise RuntimeError(f"augment: {what} is (b, c, x, y, z) with no empty axis, got {tuple(x.shape)}")
+    if x.ndim != 2 + rank or x.numel() == 0:
+        raise RuntimeError(f"augment: {what} is {_AUG_WORDS[rank][0]} with no empty axis, got {tuple(x.shape)}")
     if x[0, 0].numel() >= 2 ** 31:
-        raise RuntimeError("augment: fewer than 2^31 cells per channel")
+        raise RuntimeError(f"augment: fewer than 2^31 cells per {_AUG_WORDS[rank][1]}")
     return x.contiguous()
 
 
+def _aug_data(x, rank=3):
+    x = _aug_volume(x, "data", rank)
+    if x.dtype not in _AUG_DTYPES:
+        raise RuntimeError(f"augment: float32, bfloat16, float64 or int16 {_AUG_WORDS[rank][3]}, got {x.dtype}")
+    return x
+
+
 def _aug_desc(x, out, order, mode, cval, pad=0, dtype=L.DLKA_F32):
+    rank = x.ndim - 2
     out = tuple(int(v) for v in out)
-    if len(out) != 3 or min(out) < 1 or out[0] * out[1] * out[2] >= 2 ** 31:
-        raise RuntimeError(f"augment: three positive patch extents below 2^31 cells, got {out}")
+    if len(out) != rank or min(out) < 1 or math.prod(out) >= 2 ** 31:
+        raise RuntimeError(f"augment: {_AUG_WORDS[rank][2]} positive patch extents below 2^31 cells, got {out}")
     d = L.AugmentDesc()
     d.B, d.C, d.dtype, d.order, d.mode, d.pad, d.cval = int(x.shape[0]), int(x.shape[1]), dtype, int(order), int(mode), int(pad), float(cval)
     for ax in range(3):
-        d.src[ax], d.out[ax] = int(x.shape[2 + ax]), out[ax]
+        d.src[ax], d.out[ax] = (int(x.shape[2 + ax]), out[ax]) if ax < rank else (0, 0)
     return d, out
 
 
 def _aug_sample_tables(x, out, maps, plain):
-    """maps (B, 3, 4) float64 and plain (B, 4) int (flag, lb0, lb1, lb2) on the device.  The kernels trust the boxes: checked here."""
-    maps = np.ascontiguousarray(np.asarray(maps, dtype=np.float64).reshape(-1, 12))
-    plain = np.ascontiguousarray(np.asarray(plain, dtype=np.int32).reshape(-1, 4))
+    """maps (B, rank, rank + 1) float64 and plain (B, 1 + rank) int (flag, lower bound per axis) on the device.  The kernels trust the boxes:
+    checked here."""
+    rank = x.ndim - 2
+    maps = np.ascontiguousarray(np.asarray(maps, dtype=np.float64).reshape(-1, rank * (rank + 1)))
+    plain = np.ascontiguousarray(np.asarray(plain, dtype=np.int32).reshape(-1, 1 + rank))
     if maps.shape[0] != x.shape[0] or plain.shape[0] != x.shape[0]:
         raise RuntimeError(f"augment: one map and one crop record per sample ({x.shape[0]})")
     for b in range(plain.shape[0]):
-        if plain[b, 0] and any(plain[b, 1 + ax] < 0 or plain[b, 1 + ax] + out[ax] > x.shape[2 + ax] for ax in range(3)):
+        if plain[b, 0] and any(plain[b, 1 + ax] < 0 or plain[b, 1 + ax] + out[ax] > x.shape[2 + ax] for ax in range(rank)):
             raise RuntimeError(f"augment: the crop of sample {b} at {plain[b, 1:].tolist()} leaves the source {tuple(x.shape[2:])}")
     return torch.from_numpy(maps).to(x.device), torch.from_numpy(plain).to(x.device)
+
+
+def _aug_spline_source(x, mode):
+    """What the prefilter reads (float32 / float64), and scipy's padding and start values for ``mode``."""
+    src = x if x.dtype in _RS_DTYPES else x.to(torch.float64 if x.dtype == torch.int16 else torch.float32)
+    return (src, L.DLKA_RESAMPLE_SPLINE_PAD, L.DLKA_SPLINE_REFLECT) if mode == L.DLKA_AUG_NEAREST else (src, 0, L.DLKA_SPLINE_MIRROR)
+
+
+def _aug_spatial(x, out, maps, plain, order, mode, cval, rank):
+    x = _aug_data(x, rank)
+    coefficients, entry = ((augment_spline_coefficients, "augment_spatial") if rank == 3
+                           else (augment_spline_coefficients2d, "augment_spatial2d"))
+    coef, pad = (coefficients(x, mode) if order == 3 and not all(int(p[0]) for p in np.asarray(plain).reshape(-1, 1 + rank)) else (None, 0))
+    if order == 3 and coef is None:
+        order = 0                                            # every sample is a plain crop: nothing is interpolated
+    d, out = _aug_desc(x, out, order, mode, cval, pad, _AUG_DTYPES[x.dtype])
+    m, p = _aug_sample_tables(x, out, maps, plain)
+    y = torch.empty(tuple(x.shape[:2]) + out, dtype=x.dtype, device=x.device)
+    L.check(getattr(L.get_lib(), "dlka_" + entry)(L.ptr(x), L.ptr(coef), L.ptr(y), ctypes.byref(d), L.ptr(m), L.ptr(p), L.stream_ptr(x)), entry)
+    return y
+
+
+def _aug_spatial_labels(seg, out, maps, plain, order, mode, cval, rank):
+    seg = _aug_volume(seg, "seg", rank)
+    if seg.dtype != torch.int32:
+        raise RuntimeError(f"augment: int32 label maps, got {seg.dtype}")
+    d, out = _aug_desc(seg, out, order, mode, cval)
+    m, p = _aug_sample_tables(seg, out, maps, plain)
+    y = torch.empty(tuple(seg.shape[:2]) + out, dtype=torch.int32, device=seg.device)
+    entry = "augment_spatial_labels" if rank == 3 else "augment_spatial2d_labels"
+    L.check(getattr(L.get_lib(), "dlka_" + entry)(L.ptr(seg), L.ptr(y), ctypes.byref(d), L.ptr(m), L.ptr(p), L.stream_ptr(seg)), entry)
+    return y
 
 
 def augment_spline_coefficients(x, mode):
@@ -1423,8 +1477,7 @@ def augment_spline_coefficients(x, mode):
     'nearest' pads DLKA_RESAMPLE_SPLINE_PAD edge samples and filters with the 'reflect' start values, 'constant' filters the array itself
     with the 'mirror' ones.  Returns (coefficients (b, c, x + 2 pad, ...), pad)."""
     x = _aug_volume(x, "data")
-    src = x if x.dtype in _RS_DTYPES else x.to(torch.float64 if x.dtype == torch.int16 else torch.float32)
-    pad, boundary = (L.DLKA_RESAMPLE_SPLINE_PAD, L.DLKA_SPLINE_REFLECT) if mode == L.DLKA_AUG_NEAREST else (0, L.DLKA_SPLINE_MIRROR)
+    src, pad, boundary = _aug_spline_source(x, mode)
     ext = [int(n) + 2 * pad for n in x.shape[2:]]
     if ext[0] * ext[1] * ext[2] >= 2 ** 31:
         raise RuntimeError("augment: fewer than 2^31 cells per padded channel")
@@ -1438,67 +1491,13 @@ def augment_spline_coefficients(x, mode):
 def augment_spatial(x, out, maps, plain, order, mode, cval):
     """``x`` (b, c, x, y, z; float32, bfloat16, float64, int16) sampled at the per-sample affine ``maps`` with scipy's map_coordinates rules
     (orders 0, 1, 3; mode DLKA_AUG_CONSTANT / DLKA_AUG_NEAREST); samples whose ``plain`` flag is set are copied boxes."""
-    x = _aug_volume(x, "data")
-    if x.dtype not in _AUG_DTYPES:
-        raise RuntimeError(f"augment: float32, bfloat16, float64 or int16 volumes, got {x.dtype}")
-    coef, pad = (augment_spline_coefficients(x, mode) if order == 3 and not all(int(p[0]) for p in np.asarray(plain).reshape(-1, 4))
-                 else (None, 0))
-    if order == 3 and coef is None:
-        order = 0                                            # every sample is a plain crop: nothing is interpolated
-    d, out = _aug_desc(x, out, order, mode, cval, pad, _AUG_DTYPES[x.dtype])
-    m, p = _aug_sample_tables(x, out, maps, plain)
-    y = torch.empty(tuple(x.shape[:2]) + out, dtype=x.dtype, device=x.device)
-    L.check(L.get_lib().dlka_augment_spatial(L.ptr(x), L.ptr(coef), L.ptr(y), ctypes.byref(d), L.ptr(m), L.ptr(p), L.stream_ptr(x)),
-            "augment_spatial")
-    return y
+    return _aug_spatial(x, out, maps, plain, order, mode, cval, 3)
 
 
 def augment_spatial_labels(seg, out, maps, plain, order, mode, cval):
     """int32 label maps (b, c, x, y, z) at the same coordinates: order 0 the nearest cell, order 1 the largest label whose trilinear weight is
     >= 0.5, else 0."""
-    seg = _aug_volume(seg, "seg")
-    if seg.dtype != torch.int32:
-        raise RuntimeError(f"augment: int32 label maps, got {seg.dtype}")
-    d, out = _aug_desc(seg, out, order, mode, cval)
-    m, p = _aug_sample_tables(seg, out, maps, plain)
-    y = torch.empty(tuple(seg.shape[:2]) + out, dtype=torch.int32, device=seg.device)
-    L.check(L.get_lib().dlka_augment_spatial_labels(L.ptr(seg), L.ptr(y), ctypes.byref(d), L.ptr(m), L.ptr(p), L.stream_ptr(seg)),
-            "augment_spatial_labels")
-    return y
-
-
-# the dummy-2D branch: (b, p, h, w), p the planes of a sample (channels x depth slices)
-def _aug_planes(x, what):
-    L.require_device(x)
-    if x.ndim != 4 or x.numel() == 0:
-        raise RuntimeError(f"augment: {what} is (b, p, y, z) with no empty axis, got {tuple(x.shape)}")
-    if x[0, 0].numel() >= 2 ** 31:
-        raise RuntimeError("augment: fewer than 2^31 cells per plane")
-    return x.contiguous()
-
-
-def _aug_desc2d(x, out, order, mode, cval, pad=0, dtype=L.DLKA_F32):
-    out = tuple(int(v) for v in out)
-    if len(out) != 2 or min(out) < 1 or out[0] * out[1] >= 2 ** 31:
-        raise RuntimeError(f"augment: two positive patch extents below 2^31 cells, got {out}")
-    d = L.AugmentDesc()
-    d.B, d.C, d.dtype, d.order, d.mode, d.pad, d.cval = int(x.shape[0]), int(x.shape[1]), dtype, int(order), int(mode), int(pad), float(cval)
-    for ax in range(2):
-        d.src[ax], d.out[ax] = int(x.shape[2 + ax]), out[ax]
-    d.src[2] = d.out[2] = 0
-    return d, out
-
-
-def _aug_sample_tables2d(x, out, maps, plain):
-    """maps (B, 2, 3) float64 and plain (B, 3) int (flag, lb_y, lb_x) on the device.  The kernels trust the boxes: checked here."""
-    maps = np.ascontiguousarray(np.asarray(maps, dtype=np.float64).reshape(-1, 6))
-    plain = np.ascontiguousarray(np.asarray(plain, dtype=np.int32).reshape(-1, 3))
-    if maps.shape[0] != x.shape[0] or plain.shape[0] != x.shape[0]:
-        raise RuntimeError(f"augment: one map and one crop record per sample ({x.shape[0]})")
-    for b in range(plain.shape[0]):
-        if plain[b, 0] and any(plain[b, 1 + ax] < 0 or plain[b, 1 + ax] + out[ax] > x.shape[2 + ax] for ax in range(2)):
-            raise RuntimeError(f"augment: the crop of sample {b} at {plain[b, 1:].tolist()} leaves the source {tuple(x.shape[2:])}")
-    return torch.from_numpy(maps).to(x.device), torch.from_numpy(plain).to(x.device)
+    return _aug_spatial_labels(seg, out, maps, plain, order, mode, cval, 3)
 
 
 def augment_spline_coefficients2d(x, mode):
@@ -1506,9 +1505,8 @@ def augment_spline_coefficients2d(x, mode):
     array: the in-plane axes alone are padded (mode 'nearest': DLKA_RESAMPLE_SPLINE_PAD edge samples, 'reflect' start values; 'constant': no
     padding, 'mirror') and filtered.  The batch's stack of planes is ONE volume (b p, y, z) filtered along its axes 1 and 2: three launches
     whatever b and p are; a stack of 2^31 padded cells or more goes sample by sample.  Returns (coefficients (b, p, y + 2 pad, z + 2 pad), pad)."""
-    x = _aug_planes(x, "data")
-    src = x if x.dtype in _RS_DTYPES else x.to(torch.float64 if x.dtype == torch.int16 else torch.float32)
-    pad, boundary = (L.DLKA_RESAMPLE_SPLINE_PAD, L.DLKA_SPLINE_REFLECT) if mode == L.DLKA_AUG_NEAREST else (0, L.DLKA_SPLINE_MIRROR)
+    x = _aug_volume(x, "data", 2)
+    src, pad, boundary = _aug_spline_source(x, mode)
     B, P = int(x.shape[0]), int(x.shape[1])
     ext = [int(n) + 2 * pad for n in x.shape[2:]]
     if P * ext[0] * ext[1] >= 2 ** 31:
@@ -1526,41 +1524,19 @@ def augment_spatial2d(x, out, maps, plain, order, mode, cval):
     """``x`` (b, p, y, z; float32, bfloat16, float64, int16): every plane of sample b sampled at the in-plane affine ``maps[b]`` (2, 3) with
     scipy's 2-D map_coordinates rules (orders 0, 1, 3: 1 / 4 / 16 taps; mode DLKA_AUG_CONSTANT / DLKA_AUG_NEAREST); samples whose ``plain``
     flag is set are copied in-plane boxes.  batchgenerators' augment_spatial with dim == 2 on the planes the dummy-2D branch makes."""
-    x = _aug_planes(x, "data")
-    if x.dtype not in _AUG_DTYPES:
-        raise RuntimeError(f"augment: float32, bfloat16, float64 or int16 planes, got {x.dtype}")
-    coef, pad = (augment_spline_coefficients2d(x, mode) if order == 3 and not all(int(p[0]) for p in np.asarray(plain).reshape(-1, 3))
-                 else (None, 0))
-    if order == 3 and coef is None:
-        order = 0                                            # every sample is a plain crop: nothing is interpolated
-    d, out = _aug_desc2d(x, out, order, mode, cval, pad, _AUG_DTYPES[x.dtype])
-    m, p = _aug_sample_tables2d(x, out, maps, plain)
-    y = torch.empty(tuple(x.shape[:2]) + out, dtype=x.dtype, device=x.device)
-    L.check(L.get_lib().dlka_augment_spatial2d(L.ptr(x), L.ptr(coef), L.ptr(y), ctypes.byref(d), L.ptr(m), L.ptr(p), L.stream_ptr(x)),
-            "augment_spatial2d")
-    return y
+    return _aug_spatial(x, out, maps, plain, order, mode, cval, 2)
 
 
 def augment_spatial2d_labels(seg, out, maps, plain, order, mode, cval):
     """int32 label planes (b, p, y, z) at the same coordinates: order 0 the nearest cell, order 1 the largest label whose bilinear weight over
     the 4 in-plane neighbours is >= 0.5, else 0."""
-    seg = _aug_planes(seg, "seg")
-    if seg.dtype != torch.int32:
-        raise RuntimeError(f"augment: int32 label maps, got {seg.dtype}")
-    d, out = _aug_desc2d(seg, out, order, mode, cval)
-    m, p = _aug_sample_tables2d(seg, out, maps, plain)
-    y = torch.empty(tuple(seg.shape[:2]) + out, dtype=torch.int32, device=seg.device)
-    L.check(L.get_lib().dlka_augment_spatial2d_labels(L.ptr(seg), L.ptr(y), ctypes.byref(d), L.ptr(m), L.ptr(p), L.stream_ptr(seg)),
-            "augment_spatial2d_labels")
-    return y
+    return _aug_spatial_labels(seg, out, maps, plain, order, mode, cval, 2)
 
 
 def augment_gaussian(x, radius, weights):
     """scipy.ndimage.gaussian_filter of every channel of ``x`` (b, c, x, y, z), one launch per axis: ``radius`` (b * c,) int, < 0 = the channel
     is copied; ``weights`` (b * c, DLKA_AUG_RADIUS_MAX + 1) float64, centre first."""
-    x = _aug_volume(x, "data")
-    if x.dtype not in _AUG_DTYPES:
-        raise RuntimeError(f"augment: float32, bfloat16, float64 or int16 volumes, got {x.dtype}")
+    x = _aug_data(x)
     n = x.shape[0] * x.shape[1]
     radius = np.ascontiguousarray(np.asarray(radius, dtype=np.int32).reshape(-1))
     weights = np.ascontiguousarray(np.asarray(weights, dtype=np.float64))
@@ -1577,9 +1553,7 @@ def augment_gaussian(x, radius, weights):
 
 def augment_channel_stats(x):
     """(b * c, 4) float64 on the device: sum, sum of squares about the mean, min, max of every channel of ``x`` (b, c, x, y, z)."""
-    x = _aug_volume(x, "data")
-    if x.dtype not in _AUG_DTYPES:
-        raise RuntimeError(f"augment: float32, bfloat16, float64 or int16 volumes, got {x.dtype}")
+    x = _aug_data(x)
     n, cells = x.shape[0] * x.shape[1], x[0, 0].numel()
     if n > 65535:
         raise RuntimeError("augment: at most 65535 channels in a batch")
@@ -1595,9 +1569,7 @@ def augment_channel_stats(x):
 def augment_pointwise(x, steps, noise=None, stats0=None, stats1=None, flip=None):
     """One streaming pass over ``x`` (b, c, x, y, z): ``steps`` (b * c, k <= DLKA_AUG_OPS_MAX, 6) float64 rows (code, p0 .. p4) applied in turn
     per channel; ``flip`` (b,) int, bit a reverses spatial axis a of the stored result."""
-    x = _aug_volume(x, "data")
-    if x.dtype not in _AUG_DTYPES:
-        raise RuntimeError(f"augment: float32, bfloat16, float64 or int16 volumes, got {x.dtype}")
+    x = _aug_data(x)
     n = x.shape[0] * x.shape[1]
     steps = np.asarray(steps, dtype=np.float64)
     if steps.ndim != 3 or steps.shape[0] != n or steps.shape[1] > L.DLKA_AUG_OPS_MAX or steps.shape[2] != 6:
@@ -1650,9 +1622,8 @@ def _prep_desc(data, what="data"):
     if data.shape[0] > L.DLKA_PREP_C_MAX:
         raise RuntimeError(f"preprocessing: at most {L.DLKA_PREP_C_MAX} channels, got {data.shape[0]}")
     d = L.PrepDesc()
-    d.rank, d.C = data.ndim - 1, data.shape[0]
-    for ax in range(3):
-        d.ext[ax] = 1 if ax < 3 - d.rank else int(data.shape[1 + ax - (3 - d.rank)])
+    d.C = data.shape[0]
+    _rank_padded_ext(d, data.shape[1:])
     return d, data.contiguous()
 
 
@@ -1686,9 +1657,8 @@ def prep_mask_bbox(mask):
         raise RuntimeError(f"preprocessing: a uint8 mask of rank 2 or 3 with fewer than 2^31 cells, got {mask.dtype} {tuple(mask.shape)}")
     mask = mask.contiguous()
     d = L.PrepDesc()
-    d.rank, d.C = mask.ndim, 1
-    for ax in range(3):
-        d.ext[ax] = 1 if ax < 3 - d.rank else int(mask.shape[ax - (3 - d.rank)])
+    d.C = 1
+    _rank_padded_ext(d, mask.shape)
     box = torch.empty(8, dtype=torch.int32, device=mask.device)
     L.check(L.get_lib().dlka_prep_mask_bbox(L.ptr(mask), ctypes.byref(d), L.ptr(box), L.stream_ptr(mask)), "prep_mask_bbox")
     return box

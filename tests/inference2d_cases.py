@@ -214,6 +214,20 @@ def check_normalize_and_bf16(case, order, dev):
         assert bool((zn.cpu()[:, -1, :] == want[0, -1, 0]).all()) and float(want[0, -1, 0]) == float(np.float32(-mean) / np.float32(std))
 
 
+BF16_ZOOMS = (((2, 5, 7), (4, 6)), ((2, 5, 6), (5, 8)))      # output rows of 6 (the last lane holds 2 pixels) and 8 (whole quads)
+
+
+def check_bf16_slices_two_taps(dev):
+    """Bitwise, as check_normalize_and_bf16: order 1 of bfloat16 slices is order 1 of the same values held in float32 (checked against scipy
+    above) with the bfloat16 store; the sum is float64 of identical inputs either way."""
+    from deformablelka_amd import inference2d as I2
+    for salt, (shape, size) in enumerate(BF16_ZOOMS):
+        x = torch.from_numpy(e2e_image(shape, 53 + salt)).to(torch.bfloat16).to(dev)
+        out = I2.zoom_slices(x, size, order=1)
+        assert out.dtype == torch.bfloat16 and tuple(out.shape) == (shape[0],) + size
+        assert torch.equal(out.cpu(), I2.zoom_slices(x.float(), size, order=1, dtype=torch.bfloat16).cpu())
+
+
 # ---- argmax fused with the zoom back ---------------------------------------------------------------------------------------------------------
 def run_argmax(call, dev):
     from deformablelka_amd import inference2d as I2, ops

@@ -244,6 +244,22 @@ def check_fused_equals_unfused(call, dev):
     assert torch.equal(S.resample_and_argmax(x, SHAPES[case][1], **kw).long(), full.argmax(0))
 
 
+# float64 probabilities through the fused kernel: output rows of 6 (the last lane holds 2 voxels) and 8 (whole quads); linear on every axis, an
+# unchanged axis (one tap), and in-plane linear with nearest z
+F64_ARGMAX_CALLS = [("f64_o1_w6", (2, 3, 4, 5), (4, 5, 6), dict(order=1)), ("f64_o1_w8_x_unchanged", (2, 3, 4, 7), (3, 5, 8), dict(order=1)),
+                    ("f64_sep_w8", (2, 3, 4, 5), (4, 5, 8), _sep(0, 1, 0))]
+
+
+def check_fused_equals_unfused_f64(call, dev):
+    """As check_fused_equals_unfused: bit for bit the argmax of the float64 channels that the unfused kernel writes."""
+    from deformablelka_amd import resampling as S
+    _, shape, out, kw = call
+    x = torch.from_numpy(np.asarray(noise(shape, 23), dtype=np.float64)).to(dev)
+    full = S.resample_data_or_seg(x, out, False, **kw)
+    assert full.dtype == torch.float64
+    assert torch.equal(S.resample_and_argmax(x, out, **kw).long(), full.argmax(0))
+
+
 def check_regions(fx, call, dev):
     from deformablelka_amd import resampling as S
     cid, kind, case, ch, kw, regions = call

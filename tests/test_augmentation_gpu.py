@@ -44,6 +44,21 @@ def test_pointwise_stage(stage):
     C.check_point(FX, stage, DEV)
 
 
+@pytest.mark.parametrize("dt", C.STORAGE_DTYPES)
+def test_gaussian_blur_storage_types(dt):
+    C.check_blur_storage(dt, DEV)
+
+
+@pytest.mark.parametrize("dt", C.STORAGE_DTYPES)
+def test_channel_statistics_storage_types(dt):
+    C.check_stats_storage(dt, DEV)
+
+
+@pytest.mark.parametrize("dt", ["float64", "bfloat16"])
+def test_pointwise_storage_types(dt):
+    C.check_point_storage(dt, DEV)
+
+
 def test_mirror_every_subset_of_axes():
     C.check_mirror(DEV)
 

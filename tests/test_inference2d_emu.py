@@ -42,6 +42,10 @@ def test_fused_normalize_and_bf16_store_are_bitwise(case, order):
     C.check_normalize_and_bf16(case, order, "cpu")
 
 
+def test_bf16_slices_through_two_taps_are_bitwise():
+    C.check_bf16_slices_two_taps("cpu")
+
+
 @pytest.mark.parametrize("call", C.ARGMAX_CALLS, ids=ids(C.ARGMAX_CALLS))
 def test_argmax_fused_with_the_zoom_back(call):
     C.check_argmax(FX, call, "cpu")

@@ -34,6 +34,11 @@ def test_fused_equals_unfused(call):
     C.check_fused_equals_unfused(call, DEV)
 
 
+@pytest.mark.parametrize("call", C.F64_ARGMAX_CALLS, ids=ids(C.F64_ARGMAX_CALLS))
+def test_fused_equals_unfused_float64(call):
+    C.check_fused_equals_unfused_f64(call, DEV)
+
+
 @pytest.mark.parametrize("call", C.REGION_CALLS, ids=ids(C.REGION_CALLS))
 def test_regions_overwrite_in_order(call):
     C.check_regions(FX, call, DEV)
