@@ -37,6 +37,7 @@ DLKA_AUG_RADIUS_MAX, DLKA_AUG_OPS_MAX = 32, 4
 DLKA_PREP_C_MAX, DLKA_PREP_REC = 32, 8                                  # include/dlka.h: dlka_prep_*
 DLKA_PREP_CT, DLKA_PREP_CT2, DLKA_PREP_NONCT = 0, 1, 2
 DLKA_ZOOM2D_I16, DLKA_ZOOM2D_K_MAX, DLKA_ZOOM2D_OUTSIDE = 3, 255, -2 ** 31   # include/dlka.h: dlka_zoom2d_*
+DLKA_OPTIM_TENSORS_PER_LAUNCH, DLKA_OPTIM_CHUNK = 120, 4096               # include/dlka.h: dlka_optim_*
 (DLKA_AUG_OP_NONE, DLKA_AUG_OP_NOISE, DLKA_AUG_OP_SCALE_ADD, DLKA_AUG_OP_CONTRAST, DLKA_AUG_OP_GAMMA, DLKA_AUG_OP_RETAIN,
  DLKA_AUG_OP_REPLACE) = range(7)
 
@@ -116,6 +117,12 @@ class Zoom2dDesc(ctypes.Structure):
                 ("in_", c_int64 * 2), ("out", c_int64 * 2), ("mean", ctypes.c_float), ("std", ctypes.c_float)]
 
 
+class OptimDesc(ctypes.Structure):
+    """``dlka_optim_desc`` (include/dlka.h)."""
+    _fields_ = [("n_tensors", c_int32), ("dtype", c_int32), ("nesterov", c_int32), ("has_momentum", c_int32), ("clip", c_int32),
+                ("momentum", ctypes.c_float), ("weight_decay", ctypes.c_float), ("max_norm", ctypes.c_float), ("lr_index", c_int32)]
+
+
 # name -> (restype, argtypes); every symbol include/dlka.h declares
 _G = POINTER(ConvGeom)
 _SD = POINTER(SegLossDesc)
@@ -125,6 +132,8 @@ _RSD = POINTER(ResampleDesc)
 _AGD = POINTER(AugmentDesc)
 _PPD = POINTER(PrepDesc)
 _ZMD = POINTER(Zoom2dDesc)
+_OPD = POINTER(OptimDesc)
+_PTRS, _I64S = POINTER(c_void_p), POINTER(c_int64)
 SIGNATURES = {
     "dlka_abi_version": (c_int, []),
     "dlka_status_string": (c_char_p, [c_int]),
@@ -293,6 +302,11 @@ SIGNATURES = {
     "dlka_zoom2d_nearest": (c_int, [c_void_p, c_void_p, _ZMD, c_int, c_void_p, c_void_p]),
     "dlka_zoom2d_argmax": (c_int, [c_void_p, c_void_p, _ZMD, c_int, c_void_p, c_void_p]),
     "dlka_zoom2d_launch_count": (ctypes.c_long, []),
+    "dlka_optim_workspace_bytes": (c_size_t, [_I64S, c_int64]),
+    "dlka_optim_grad_norm": (c_int, [_PTRS, _I64S, c_int64, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "dlka_optim_scale": (c_int, [_PTRS, _I64S, c_int64, c_int, c_void_p, ctypes.c_float, c_void_p]),
+    "dlka_optim_sgd_step": (c_int, [_PTRS, _PTRS, _PTRS, _I64S, _OPD, c_void_p, c_void_p, c_void_p]),
+    "dlka_optim_launch_count": (ctypes.c_long, []),
     "dlka_trace_start": (c_int, [c_int, c_void_p]),
     "dlka_trace_mark": (c_int, [c_void_p]),
     "dlka_trace_stop": (c_int, []),

@@ -60,6 +60,13 @@ __device__ __forceinline__ float sum8(float x)
     return x;
 }
 __device__ __forceinline__ void sched_fence() {}
+// float64 sum over the 64 lanes of a full wave (result in all lanes; every lane must call it), in the GPU branch's order of additions
+__device__ __forceinline__ double wave_sum_f64(double x)
+{
+    for (int m = 1; m <= 8; m <<= 1) x += hipemu::shfl_any(x, (hipemu::F().lin & 63) ^ m);
+    const double r0 = hipemu::shfl_any(x, 0), r1 = hipemu::shfl_any(x, 16), r2 = hipemu::shfl_any(x, 32), r3 = hipemu::shfl_any(x, 48);
+    return ((r0 + r1) + r2) + r3;
+}
 // sum over the 4 lanes that share lane >> 2 (result in all 4)
 __device__ __forceinline__ float sum4(float x)
 {
@@ -257,6 +264,29 @@ __device__ __forceinline__ float sum8(float x)
 // nothing moves across it in the instruction scheduler (keeps register live ranges short where the scheduler would otherwise interleave two
 // independent register-hungry sections)
 __device__ __forceinline__ void sched_fence() { __builtin_amdgcn_sched_barrier(0); }
+// float64 sum over the 64 lanes of a full wave (result in all lanes): the three DPP steps of sum8 and row_mirror (0x140, lane k <-> 15-k inside
+// each row of 16) on both halves of the value, then the four row sums read as scalars (v_readlane_b32) and added in row order
+template <int CTRL> __device__ __forceinline__ double dpp_f64(double x)
+{
+    const unsigned long long b = __builtin_bit_cast(unsigned long long, x);
+    const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)b, CTRL, 0xF, 0xF, false);
+    const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)(b >> 32), CTRL, 0xF, 0xF, false);
+    return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
+}
+__device__ __forceinline__ double readlane_f64(double x, int l)
+{
+    const unsigned long long b = __builtin_bit_cast(unsigned long long, x);
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)b, l), hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(b >> 32), l);
+    return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
+}
+__device__ __forceinline__ double wave_sum_f64(double x)
+{
+    x += dpp_f64<0xB1>(x);
+    x += dpp_f64<0x4E>(x);
+    x += dpp_f64<0x141>(x);
+    x += dpp_f64<0x140>(x);
+    return ((readlane_f64(x, 0) + readlane_f64(x, 16)) + readlane_f64(x, 32)) + readlane_f64(x, 48);
+}
 // sum over the 4 lanes that share lane >> 2 (result in all 4): the two quad_perm steps of sum8
 __device__ __forceinline__ float sum4(float x)
 {

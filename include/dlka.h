@@ -991,6 +991,51 @@ int dlka_zoom2d_argmax(const void *logits, uint8_t *labels, const dlka_zoom2d_de
 long dlka_zoom2d_launch_count(void);
 
 /* =======================================================================================
+ * The trainers' optimizer step: gradient clipping + SGD, learning rate in device memory — csrc/cl_optim.hip
+ * =======================================================================================
+ * Every reference trainer ends its iteration with SGD: the 3-D trainer with momentum 0.99, Nesterov, weight decay 3e-5
+ * (3D/d_lka_former/training/network_training/d_lka_former_trainer_synapse.py:197-205) after clip_grad_norm_(parameters, 12) (:291-309), its
+ * learning rate set per epoch by poly_lr (:451); the 2-D trainer with momentum 0.9, weight decay 1e-4 (2D/trainer_MaxViT_deform_LKA.py:114)
+ * and a new learning rate every iteration (:145-147); the pancreas trainer likewise (3D/train_pancreas.py:127, :172-175).
+ *
+ * Multi-tensor entries: host arrays of n per-tensor device pointers and int64 element counts, float32 (DLKA_F32) throughout.  The arrays
+ * are read before the entry returns; they are cut into launches of up to DLKA_OPTIM_TENSORS_PER_LAUNCH tensors whose addresses travel in
+ * the kernel arguments (a stream capture therefore records them in the kernel nodes: no copy or memset node is added).  A workgroup owns
+ * one chunk of DLKA_OPTIM_CHUNK elements of one tensor; the map depends on the counts only.  16-byte accesses where every pointer of a
+ * tensor is 16-byte aligned, scalar accesses of the same elements by the same lanes otherwise: both give the same bits.  A tensor is n
+ * consecutive elements in memory; zero-element tensors are skipped (their pointers may be NULL).
+ *
+ * dlka_optim_grad_norm  norm_out[0] (device) = (float)sqrt(sum of squares over all tensors): squares and sums in float64, one partial per
+ *                       chunk in `workspace` (dlka_optim_workspace_bytes, 8-byte aligned), added in a fixed order by a finishing launch.  No
+ *                       atomics, no host read: bitwise reproducible.  What clip_grad_norm_ returns.
+ * dlka_optim_scale      g *= min(1, max_norm / (norm_dev[0] + 1e-6)), the coefficient in float32 as torch forms it; the multiplication always
+ *                       happens, so a non-finite norm propagates (torch's error_if_nonfinite=False).  The second half of clip_grad_norm_.
+ * dlka_optim_sgd_step   per element, in torch.optim.SGD's order:  g_c = clip ? g * coef : g;  d = g_c + weight_decay * p (weight_decay != 0);
+ *                       has_momentum: buf = momentum * buf + d,  u = nesterov ? d + momentum * buf : buf;  else u = d (bufs may be NULL);
+ *                       p -= lr_dev[lr_index] * u.  coef as in dlka_optim_scale from norm_dev[0], max_norm.  The gradient is NOT written back.
+ *                       Buffers start as zeros (dampening 0: momentum * 0 + d is torch's first-step buf = d); no other dampening.
+ * Return codes, in this order, nothing launched before the checks pass: DLKA_ERR_NULL (a table, the descriptor, lr_dev, norm_out, bufs with
+ * has_momentum, norm_dev with clip), DLKA_ERR_SHAPE (n < 0, a negative count or lr_index), DLKA_ERR_DTYPE, DLKA_ERR_UNSUPPORTED (a count or
+ * the chunk total above 2^31 - 1), DLKA_ERR_NULL (a NULL address of a tensor with elements), DLKA_ERR_WORKSPACE (NULL, too small, not 8-byte
+ * aligned).  n == 0 is DLKA_OK without a launch. */
+#define DLKA_OPTIM_TENSORS_PER_LAUNCH 120
+#define DLKA_OPTIM_CHUNK 4096
+typedef struct dlka_optim_desc {
+    int32_t n_tensors, dtype, nesterov, has_momentum, clip;
+    float momentum, weight_decay, max_norm;
+    int32_t lr_index;
+} dlka_optim_desc;
+/* bytes of `workspace` for dlka_optim_grad_norm of this list (0 for an invalid or empty one) */
+size_t dlka_optim_workspace_bytes(const int64_t *counts, int64_t n);
+int dlka_optim_grad_norm(const void *const *grads, const int64_t *counts, int64_t n, int dtype, void *workspace, size_t workspace_bytes,
+                         float *norm_out, void *stream);
+int dlka_optim_scale(void *const *grads, const int64_t *counts, int64_t n, int dtype, const float *norm_dev, float max_norm, void *stream);
+int dlka_optim_sgd_step(void *const *params, const void *const *grads, void *const *bufs, const int64_t *counts, const dlka_optim_desc *d,
+                        const float *lr_dev, const float *norm_dev, void *stream);
+/* Diagnostics: kernel launches so far (this process) of the entries above. */
+long dlka_optim_launch_count(void);
+
+/* =======================================================================================
  * Launch trace — measurement aid (no reference counterpart; the reference has no profiling hooks)
  * =======================================================================================
  * Between dlka_trace_start and dlka_trace_stop every kernel launch of the library is followed by a HIP timing event on the
