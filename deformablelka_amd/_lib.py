@@ -235,6 +235,7 @@ SIGNATURES = {
     "dlka_pw_chain_launch_count": (ctypes.c_long, []),
     "dlka_dwconv_2p_launch_count": (ctypes.c_long, []),
     "dlka_conv_kw_launch_count": (ctypes.c_long, []),
+    "dlka_conv_kw_applies": (c_int, [c_int] * 8),
     "dlka_lka3d_tokens_supported_v": (c_int, [c_int] * 7),
     "dlka_lka3d_tokens_saved_bytes_v": (c_size_t, [c_int] * 7),
     "dlka_lka3d_tokens_workspace_bytes_v": (c_size_t, [c_int] * 7),

@@ -173,7 +173,7 @@ struct TokBwdWs {
     // dtypes: gta and the split scratch ARE fp32
     float *gg1, *ga1, *gf, *gta, *gt, *gt1, *ga2, *gh;
     float *goff, *scratch;
-    float *samp;         // ALWAYS carved at its capacity: the layout behind it does not depend on the gather switch
+    float *samp;         // ALWAYS carved at its capacity: the layout behind it does not depend on the gather switch (halves use its first half and one word behind: samp_f16_maxbits)
     float *blkA, *blkB;
     float *padt;         // the zero-padded copy of t the offset conv's weight gradient reads (null when the workspace was sized without it: the unpadded kernels)
 };

@@ -467,6 +467,9 @@ int dlka::tokens_backward_impl(const void *x_, const dlka_lka3d_params *p, const
     if (dense_backward_data_splits(G.pw, 0) > 1) zb.add(gf, G.E);
     if (dense_backward_data_splits(G.offc, 3) > 1) zb.add(bf ? ga2 : gt, G.E);   // bf16: split partial sums land in the fp32 scratch ga2
     if (dense_backward_data_splits(G.pw, 3) > 1) zb.add(gx, G.E);
+    // the word the half hand-over's max |t| is accumulated into (fp32 path; cl_absmax_bits_kernel): zeroed with the rest instead of by a launch of its own
+    float *samp_max = (samp && !bf) ? samp + (size_t)G.dcn.K * G.dcn.M * G.dcn.Cin / 2 : nullptr;
+    zb.add(samp_max, 1);
     if (zb.overflow) return DLKA_ERR_WORKSPACE;
     // (the zero fills ride in the first kernel below: one dependent node less per block)
 
@@ -499,7 +502,7 @@ int dlka::tokens_backward_impl(const void *x_, const dlka_lka3d_params *p, const
         DLKA_TRY(deform_backward(G.dcn, t, off, N0, gf, gta, nullptr, nullptr, nullptr, PW.dcn_b, nullptr, scratch, lease.stream(1), nullptr, true, false, 0, nullptr, PW.dcn_b16));
         gx_forked = true;
     }
-    DLKA_P1(deform_backward(G.dcn, t, off, N0, gf, nullptr, goff, nullptr, nullptr, PW.dcn_b, nullptr, scratch, st, nullptr, false, true, goff_cpad, samp, PW.dcn_b16));
+    DLKA_P1(deform_backward(G.dcn, t, off, N0, gf, nullptr, goff, nullptr, nullptr, PW.dcn_b, nullptr, scratch, st, nullptr, false, true, goff_cpad, samp, PW.dcn_b16, samp_max != nullptr));
     if (samp)
         DLKA_P2(deform_backward(G.dcn, t, off, N0, gf, nullptr, nullptr, (float *)gr->deform_w, (float *)gr->deform_b, PW.dcn_b, part_dcn, scratch, st,
                                 &fb.j[fb.njobs++], false, false, 0, samp));

@@ -211,6 +211,11 @@ struct DeformBwdArgs {
                         //   stage-0 launch, the same read back by cl_wgrad_samp_kernel).  A sample is an interpolated activation: rounding it to 11 significant bits moves a
                         //   weight-gradient element by ~3e-4 of its own magnitude at worst over 65 536 random-sign terms (bf16's 8 bits would sit ON the 1e-3 contract);
                         //   grad_out and the accumulation stay fp32.  DLKA_SAMP_F16=0 / DLKA_EXACT_FP32 keep fp32 samples
+                        //   What the hand-over guarantees: the halves are  sample * 2^e  with ONE e per call, max |in| * 2^e in [2^14, 2^15) (samp_pow2; max |in| is left in
+                        //   the word behind the halves by cl_absmax_bits_kernel, the reader divides it out) — no sample saturates, none that matters is subnormal, whatever
+                        //   the scale of the activations; a non-finite max gives e = 0 and a plain IEEE conversion, so Inf / NaN samples reach the weight gradient.
+                        //   `samp` therefore always has the size of K * M * C FP32 samples (TokGeom::samp_capacity_floats)
+    int samp_max_zeroed;   // 1: the caller has already zero-filled the word cl_absmax_bits_kernel accumulates into (samp_f16_maxbits): no fill launch of its own
     int goff_cpad;      // > 0: goff is written as pack_split2() words with goff_cpad channel planes per batch (planes >= 3K zero) for the
                         //      split-MFMA consumers (offset-conv data / weight gradient); 0: plain fp32 [B][3K][N]
 };

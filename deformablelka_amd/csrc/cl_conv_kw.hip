@@ -199,6 +199,7 @@ bool cl_conv_kw_applies(int amode, int omode, int split_bf16, int K, int epi, in
 {
     static const bool off = [] { const char *e = getenv("DLKA_CONV_KW"); return e && e[0] == '0'; }();   // (A/B: 0 = the tap split over gridDim.y with fp32 atomics, rounds 1 - 5)
     if (off || !volume || K <= 1 || (epi != 0 && epi != 3) || NP % 32) return false;
+    if (epi == 3 && omode == 1) return false;   // the planar store (OMODE 1) has no aux add: such a launch would drop the epilogue
     if (act_bf16) return split_bf16 == 2 && ((amode == 0 && omode == 1) || (amode == 2 && omode == 0));   // the two 27-tap convs of the bf16 token path
     if (split_bf16 == 3) return amode == 0 && (omode == 0 || omode == 1);
     if (split_bf16 == 2) return (amode == 0 && (omode == 0 || omode == 1)) || (amode == 2 && omode == 0);
@@ -246,3 +247,7 @@ int launch_cl_conv_kw(int amode, int omode, const IgemmArgs &a, hipStream_t st)
 }  // namespace dlka
 
 extern "C" long dlka_conv_kw_launch_count(void) { return dlka::g_conv_kw_launches.load(std::memory_order_relaxed); }
+extern "C" int dlka_conv_kw_applies(int amode, int omode, int split_bf16, int K, int epi, int NP, int act_bf16, int volume)
+{
+    return dlka::cl_conv_kw_applies(amode, omode, split_bf16, K, epi, NP, act_bf16 != 0, volume != 0) ? 1 : 0;
+}

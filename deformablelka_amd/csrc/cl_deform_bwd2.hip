@@ -35,6 +35,37 @@ constexpr int TG = 8;     // taps per MFMA row group (TG * CS = 32 MFMA rows)
 
 }  // namespace
 
+// ---------------------------------------------------------------------------------------------------------------------
+// The half hand-over (DeformBwdArgs::samp_f16) is scale-free: before the grad_offset launch this kernel leaves the bits of max |in| in the word behind the
+// halves (samp_f16_maxbits; zeroed first), the writers store  sample * 2^e  with the e that samp_pow2 derives from it, cl_wgrad_samp_kernel multiplies its
+// sums by 2^-e.  |x| as unsigned bits orders like the value, with Inf above every finite number and NaN above Inf.  16-byte loads, a wave-wide maximum by
+// shuffles, one atomicMax per wave.
+// ---------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void cl_absmax_bits_kernel(const float *x, long n4, unsigned *out)
+{
+    unsigned m = 0;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+        const f32x4 v = *reinterpret_cast<const f32x4 *>(x + 4 * i);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const unsigned u = __float_as_uint(v[e]) & 0x7fffffffu;
+            m = u > m ? u : m;
+        }
+    }
+    for (int s = 32; s > 0; s >>= 1) {
+        const unsigned o = (unsigned)__shfl_xor((int)m, s);
+        m = o > m ? o : m;
+    }
+    if ((threadIdx.x & 63) == 0 && m) atomicMax(out, m);
+}
+
+// the factor a grad_offset kernel multiplies its samples by before they become halves (1 when they stay fp32)
+template <bool HALVES> __device__ __forceinline__ float samp_f16_scale(const DeformBwdArgs &p)
+{
+    if (!HALVES || !p.samp_f16) return 1.f;
+    return samp_pow2(*samp_f16_maxbits(p.samp, (size_t)p.K * p.M * p.C), false);
+}
+
 // =====================================================================================================================
 // grad_offset
 // =====================================================================================================================
@@ -93,6 +124,7 @@ __global__ __launch_bounds__(256, 2) void cl_deform_goff2_kernel(DeformBwdArgs p
     // (S has the storage type of the activations: fp32, or bf16 on the DLKA_BF16 path)
     const BufRsrc rsamp = make_rsrc(p.samp, SAMP ? (size_t)p.K * p.M * p.C * XB : 0);
     const unsigned samp_v0 = (unsigned)((mbase + gr) * p.C + GG::PE * gp) * XB;
+    const float samp_mul = samp_f16_scale<SAMP && XB == 4>(p);   // halves: every sample times the call's 2^e (samp_pow2)
     const bool tile_full = mbase + 32 <= p.M;   // wave-uniform: only the last tile of a ragged M needs per-row checks
 
     if (p.goff_cpad && blockIdx.y == 0 && blockIdx.z == 0 && h == 0 && row_ok) {   // the zero planes 3K .. goff_cpad-1 of the packed layout
@@ -312,7 +344,12 @@ __global__ __launch_bounds__(256, 2) void cl_deform_goff2_kernel(DeformBwdArgs p
                     *reinterpret_cast<f32x4 *>(dst + 2 * 32 * SROW) = dw;
                     if (SAMP && XB == 4) {
                         const unsigned so = (unsigned)((tap * p.M + GG::RPI * g) * p.C + cc * 32 + 4 * v);   // element offset beyond this lane's (row, piece)
-                        if (p.samp_f16) buf_store_f16x4(rsamp, srow ? (samp_v0 >> 1) + so * 2u : DLKA_OOB, s4);   // (uniform) halves: samp_v0 is a byte offset of fp32 elements
+                        if (p.samp_f16) {   // (uniform) halves: samp_v0 is a byte offset of fp32 elements
+                            f32x4 sh;
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) sh[e] = s4[e] * samp_mul;
+                            buf_store_f16x4(rsamp, srow ? (samp_v0 >> 1) + so * 2u : DLKA_OOB, sh);
+                        }
                         else buf_store_f32x4(rsamp, srow ? samp_v0 + so * 4u : DLKA_OOB, s4);
                     }
                     if (SAMP && XB == 2) { if (v == 0) s4_lo = s4; else buf_store_bf16x8(rsamp, srow ? samp_v0 + (unsigned)((tap * p.M + GG::RPI * g) * p.C + cc * 32) * 2u : DLKA_OOB, s4_lo, s4); }
@@ -420,6 +457,7 @@ __global__ __launch_bounds__(64 * WAVES, OCC) void cl_deform_goff16_kernel(Defor
         if (mr < p.M && gp == 0) { const int br = mr / p.N; gbyte = (unsigned)(br * 3 * p.K * p.N + (mr - br * p.N)) * 4u; }
     }
     const unsigned samp_v0 = (mbase + gr < p.M) ? (unsigned)((mbase + gr) * p.C + PE * gp) * XB : DLKA_OOB;   // S[tap][m][c]: + (tap M C + channel) bytes
+    const float samp_mul = samp_f16_scale<SAMP && XB == 4>(p);   // halves: every sample times the call's 2^e (samp_pow2)
 
     GatherPiece<T> xr[8];   // corner pieces of the unit (tap, pass) in flight
     float onx[3] = {0.f, 0.f, 0.f};
@@ -555,9 +593,12 @@ __global__ __launch_bounds__(64 * WAVES, OCC) void cl_deform_goff16_kernel(Defor
                     sraw[2 * vv + 1] = __uint_as_float((unsigned)bf16_bits(sv[2]) | ((unsigned)bf16_bits(sv[3]) << 16));
                 }
             }
-            if (SAMP && XB == 4 && p.samp_f16)   // (uniform) the fp32 path's samples as halves: 8 bytes per lane and pass
-                buf_store_f16x4(rsamp, samp_v0 == DLKA_OOB ? DLKA_OOB : (samp_v0 >> 1) + (unsigned)(tap * p.M * p.C + CPP * pass) * 2u, sraw);
-            else if (SAMP) buf_store_f32x4(rsamp, samp_v0 == DLKA_OOB ? DLKA_OOB : samp_v0 + (unsigned)(tap * p.M * p.C + CPP * pass) * XB, sraw);
+            if (SAMP && XB == 4 && p.samp_f16) {   // (uniform) the fp32 path's samples as halves, times the call's 2^e: 8 bytes per lane and pass
+                f32x4 sh;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) sh[e] = sraw[e] * samp_mul;
+                buf_store_f16x4(rsamp, samp_v0 == DLKA_OOB ? DLKA_OOB : (samp_v0 >> 1) + (unsigned)(tap * p.M * p.C + CPP * pass) * 2u, sh);
+            } else if (SAMP) buf_store_f32x4(rsamp, samp_v0 == DLKA_OOB ? DLKA_OOB : samp_v0 + (unsigned)(tap * p.M * p.C + CPP * pass) * XB, sraw);
             // the next unit's corner loads go out now: in flight under the reduction below, the next staging and the next MFMAs
             sched_fence();   // (the scheduler would hoist these loads above the interpolation into a SECOND set of piece registers — and spill)
             if (pass + 1 < NPASS) issue(tap, pass + 1);
@@ -1390,6 +1431,16 @@ int launch_cl_deform_bwd2(const DeformBwdArgs &a, float *scratch, hipStream_t st
         ag.cc_per_block = cdiv(a.C / 32, ccsplit);
         if (a.goff_cpad && ccsplit > 1) return DLKA_ERR_UNSUPPORTED;   // the packed layout needs the single-writer path
         if (ccsplit > 1 && !a.goff_zeroed && launch_zero(a.goff, (size_t)a.B * 3 * a.K * a.N * 4, st) != DLKA_OK) return DLKA_ERR_LAUNCH;
+        if (a.samp && a.samp_f16) {   // the half hand-over's common exponent: max |in| as bits, behind the halves (cl_absmax_bits_kernel)
+            if (a.act_bf16 || ((uintptr_t)a.in & 15)) return DLKA_ERR_UNSUPPORTED;
+            unsigned *mb = const_cast<unsigned *>(samp_f16_maxbits(a.samp, (size_t)a.K * a.M * a.C));
+            if (!a.samp_max_zeroed && launch_zero(mb, 4, st) != DLKA_OK) return DLKA_ERR_LAUNCH;
+            const long n4 = (long)a.M * a.C / 4;   // C % 32 == 0
+            long nb = cdivl(n4, 256 * 4);
+            if (nb > 1024) nb = 1024;
+            DLKA_LAUNCH(cl_absmax_bits_kernel, dim3((unsigned)nb), dim3(256), 0, st, a.in, n4, mb);
+            DLKA_CHECK_LAUNCH();
+        }
         // 16-row waves where the stage is large and one 32-channel chunk wide (stage 0).  DLKA_GOFF16_MIN_ROWS lowers the row threshold so that small
         // test shapes take this kernel too (not cached: tests toggle it).
         bool done16 = false;

@@ -137,7 +137,7 @@ void fill_deform_bwd(DeformBwdArgs &a, const SameConv &s);
 size_t deform_scratch_floats(const SameConv &s);
 int deform_backward(const SameConv &s, const float *x, const float *off, const float *w, const float *gout, float *gx, float *goff,
                     float *gw, float *gb, float *wp, float *part, float *scratch, hipStream_t st, FinalizeJob *defer = nullptr, bool gx_zeroed = false,
-                    bool goff_zeroed = false, int goff_cpad = 0, float *samp = nullptr, const float *wp16 = nullptr);
+                    bool goff_zeroed = false, int goff_cpad = 0, float *samp = nullptr, const float *wp16 = nullptr, bool samp_max_zeroed = false);
 int pointwise_pair(const SameConv &s, int bwd, const float *in, const float *wp1, const float *bias1, const float *wp2, const float *bias2,
                    const float *a, const float *b, float *out1, float *out1b, float *out2, hipStream_t st, const ZeroBatch *ride = nullptr);
 bool wgrad_gather();

@@ -385,7 +385,7 @@ static bool samp_f16(const SameConv &s)
 
 int deform_backward(const SameConv &s, const float *x, const float *off, const float *w, const float *gout, float *gx, float *goff,
                     float *gw, float *gb, float *wp, float *part, float *scratch, hipStream_t st, FinalizeJob *defer, bool gx_zeroed,
-                    bool goff_zeroed, int goff_cpad, float *samp, const float *wp16)
+                    bool goff_zeroed, int goff_cpad, float *samp, const float *wp16, bool samp_max_zeroed)
 {
     // samp ([K][M][C] fp32): a grad_offset call stores the trilinear samples there, a weight-gradient call reads them instead of gathering again
     if (gx || goff) {
@@ -395,6 +395,7 @@ int deform_backward(const SameConv &s, const float *x, const float *off, const f
         a.in = x; a.off = off; a.g = gout; a.wp = wp; a.gx = gx; a.goff = goff; a.gx_zeroed = gx_zeroed ? 1 : 0; a.goff_zeroed = goff_zeroed ? 1 : 0; a.goff_cpad = goff_cpad;
         a.samp = goff ? samp : nullptr;
         a.samp_f16 = (a.samp && samp_f16(s)) ? 1 : 0;
+        a.samp_max_zeroed = samp_max_zeroed ? 1 : 0;
         a.wp16 = deform_b16() ? wp16 : nullptr;   // (prepared by the caller: two-term bf16 records, mode 2 | 8) — both dtypes: bf16 rows as they are, fp32 rows split
         DLKA_TRY(launch_cl_deform_bwd2(a, scratch, st));
     }

@@ -336,6 +336,8 @@ __global__ __launch_bounds__(64 * WV, 2) void cl_wgrad_samp_kernel(WgradArgs p)
     }
     wg_sum_tiles<WV, TPW, 1>(acc, &bsum, red, wave, lane);
     if (wave != 0) return;
+    // S16: the halves are  sample * 2^e  with one e per backward call (samp_pow2; the writers and this kernel read the same word) — an exact power of two, taken out of the sums here
+    const float unscale = S16 ? samp_pow2(*samp_f16_maxbits(p.samp, (size_t)p.K * p.M * p.Cin), true) : 1.f;
 #pragma unroll
     for (int t = 0; t < TPW; ++t) {
         const int tap = tap0 + t;
@@ -343,7 +345,7 @@ __global__ __launch_bounds__(64 * WV, 2) void cl_wgrad_samp_kernel(WgradArgs p)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
-            p.part[(((long)chunk * p.K + tap) * p.CoutP + ot * 32 + row) * p.Cin + ct * 32 + i] = acc[t][r];
+            p.part[(((long)chunk * p.K + tap) * p.CoutP + ot * 32 + row) * p.Cin + ct * 32 + i] = S16 ? acc[t][r] * unscale : acc[t][r];
         }
     }
     if (want_bias) {

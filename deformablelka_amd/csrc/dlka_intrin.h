@@ -138,15 +138,11 @@ __device__ __forceinline__ void buf_store_bf16x8(BufRsrc r, unsigned off, f32x4 
     for (int e = 0; e < 4; ++e) { h[e] = hipemu::hipemu_f32_to_bf16(lo[e]); h[4 + e] = hipemu::hipemu_f32_to_bf16(hi[e]); }
     memcpy(const_cast<unsigned char *>(r.base) + off, h, 16);
 }
-// fp16 (IEEE half) <-> float: the stored-sample hand-over of the fp32 path keeps its samples as halves (cl_deform_bwd2.hip / cl_wgrad.hip, round 6); values beyond the
-// half range saturate at +-65504 instead of becoming infinite
-__device__ __forceinline__ unsigned short f16_bits(float x)
-{
-    const float c = fminf(fmaxf(x, -65504.f), 65504.f);
-    return __builtin_bit_cast(unsigned short, (_Float16)c);
-}
+// fp16 (IEEE half) <-> float: the stored-sample hand-over of the fp32 path keeps its samples as halves (cl_deform_bwd2.hip / cl_wgrad.hip, round 6).  A plain IEEE
+// conversion: the writers pre-scale by samp_pow2() so that no finite sample leaves the half range, and Inf / NaN stay what they are
+__device__ __forceinline__ unsigned short f16_bits(float x) { return __builtin_bit_cast(unsigned short, (_Float16)x); }
 __device__ __forceinline__ float f16_value(unsigned short b) { return (float)__builtin_bit_cast(_Float16, b); }
-// 4 floats -> 4 halves (round to nearest even, saturating), one 8-byte store, dropped when the offset is out of range (DLKA_OOB)
+// 4 floats -> 4 halves (round to nearest even), one 8-byte store, dropped when the offset is out of range (DLKA_OOB)
 __device__ __forceinline__ void buf_store_f16x4(BufRsrc r, unsigned off, f32x4 v)
 {
     if (!(off < r.bytes) || (size_t)off + 8 > r.bytes) return;
@@ -342,15 +338,11 @@ __device__ __forceinline__ void buf_store_bf16x8(BufRsrc r, unsigned off, f32x4 
     w[2] = (unsigned)bf16_bits(hi[0]) | ((unsigned)bf16_bits(hi[1]) << 16); w[3] = (unsigned)bf16_bits(hi[2]) | ((unsigned)bf16_bits(hi[3]) << 16);
     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(raw128_t, w), r, off, 0, 0);
 }
-// fp16 (IEEE half) <-> float: the stored-sample hand-over of the fp32 path keeps its samples as halves (cl_deform_bwd2.hip / cl_wgrad.hip, round 6); values beyond the
-// half range saturate at +-65504 instead of becoming infinite
-__device__ __forceinline__ unsigned short f16_bits(float x)
-{
-    const float c = fminf(fmaxf(x, -65504.f), 65504.f);
-    return __builtin_bit_cast(unsigned short, (_Float16)c);
-}
+// fp16 (IEEE half) <-> float: the stored-sample hand-over of the fp32 path keeps its samples as halves (cl_deform_bwd2.hip / cl_wgrad.hip, round 6).  A plain IEEE
+// conversion: the writers pre-scale by samp_pow2() so that no finite sample leaves the half range, and Inf / NaN stay what they are
+__device__ __forceinline__ unsigned short f16_bits(float x) { return __builtin_bit_cast(unsigned short, (_Float16)x); }
 __device__ __forceinline__ float f16_value(unsigned short b) { return (float)__builtin_bit_cast(_Float16, b); }
-// 4 floats -> 4 halves (round to nearest even, saturating), one 8-byte store (whole offset in the VGPR: see the note above)
+// 4 floats -> 4 halves (round to nearest even), one 8-byte store (whole offset in the VGPR: see the note above)
 __device__ __forceinline__ void buf_store_f16x4(BufRsrc r, unsigned off, f32x4 v)
 {
     typedef unsigned u2_t __attribute__((ext_vector_type(2)));
@@ -412,4 +404,18 @@ __device__ __forceinline__ void unpack_split2x8(const float *w, bf16x8 &hi, bf16
     extern __shared__ __attribute__((aligned(16))) unsigned char dlka_dyn_lds[]; \
     type *name = reinterpret_cast<type *>(dlka_dyn_lds)
 #endif
+// The half hand-over's common exponent.  `maxbits` = the bits of max |t| over the deformable conv's input (cl_absmax_bits_kernel; 0x7f800000 and above: an Inf or a
+// NaN somewhere).  Returns 2^e (inverse: 2^-e) with max |t| * 2^e in [2^14, 2^15): a sample is a convex combination of elements of t, so no scaled sample leaves the
+// half range, and one that falls into the subnormal halves is below 2^-28 of the largest.  e is kept inside [-126, 126] so that both powers are normal floats; a
+// non-finite or all-zero t gets e = 0 (the plain conversion: Inf and NaN propagate).
+__device__ __forceinline__ float samp_pow2(unsigned maxbits, bool inverse)
+{
+    if (maxbits >= 0x7f800000u || maxbits == 0u) return 1.f;
+    int e = 14 - ((int)(maxbits >> 23) - 127);
+    e = e > 126 ? 126 : (e < -126 ? -126 : e);
+    return __uint_as_float((unsigned)((inverse ? -e : e) + 127) << 23);
+}
+// ... and where a call keeps those bits: the hand-over buffer always has the size of `kmc` = K * M * C fp32 samples (TokGeom::samp_capacity_floats), the halves fill
+// its first half, the word right behind them is this one
+__host__ __device__ __forceinline__ const unsigned *samp_f16_maxbits(const float *samp, size_t kmc) { return reinterpret_cast<const unsigned *>(samp) + (kmc >> 1); }
 }  // namespace dlka

@@ -30,6 +30,14 @@ def _pair(v) -> Tuple[int, int]:
     return v
 
 
+def _require_input_dtype(input, **named):
+    """The general operators hand EVERY pointer to the library as the type of `input` (float32, bfloat16 or float64): a tensor of another dtype would be read at
+    the wrong element size — past its end when it is the narrower one.  The reference's op raises a scalar-type mismatch there; so does this, before any launch."""
+    for name, t in named.items():
+        if t is not None and t.dtype != input.dtype:
+            raise RuntimeError(f"expected `{name}` to have the dtype of `input` ({input.dtype}), got {t.dtype}")
+
+
 def _geom(x_shape, cout, k, s, p, d, group, dg=1, im2col_step=64) -> L.ConvGeom:
     B, C, D, H, W = (int(v) for v in x_shape)
     return L.ConvGeom(B, C, D, H, W, int(cout), *k, *s, *p, *d, int(group), int(dg), int(im2col_step))
@@ -52,6 +60,7 @@ def deform_conv3d_forward(input, weight, bias, offset, kernel_size, stride, padd
     if not weight.is_contiguous():
         raise RuntimeError("weight tensor has to be contiguous")
     L.require_device(input, weight, bias, offset)
+    _require_input_dtype(input, weight=weight, bias=bias, offset=offset)
     k, s, p, d = _triple(kernel_size), _triple(stride), _triple(padding), _triple(dilation)
     if tuple(weight.shape[2:5]) != k:  # deform_conv_cuda.cu:72-73
         raise RuntimeError(f"Input shape and kernel shape wont match: ({k} vs {tuple(weight.shape[2:5])}).")
@@ -85,6 +94,7 @@ def deform_conv3d_backward(input, weight, bias, offset, grad_output, kernel_size
     if not weight.is_contiguous():
         raise RuntimeError("weight tensor has to be contiguous")
     L.require_device(input, weight, bias, offset, grad_output)
+    _require_input_dtype(input, weight=weight, bias=bias, offset=offset, grad_output=grad_output)
     k, s, p, d = _triple(kernel_size), _triple(stride), _triple(padding), _triple(dilation)
     offset = offset.contiguous()
     grad_output = grad_output.contiguous()  # reference: permute(...).contiguous() copies, deform_conv_cuda.cu:228
@@ -142,6 +152,7 @@ def _geom2d(x_shape, weight_shape, s, p, d, offset_channels):
 
 def deform_conv2d_forward(input, offset, weight, bias=None, stride=1, padding=0, dilation=1):
     L.require_device(input, offset, weight, bias)
+    _require_input_dtype(input, offset=offset, weight=weight, bias=bias)
     s, p, d = _pair(stride), _pair(padding), _pair(dilation)
     input, offset, weight = input.contiguous(), offset.contiguous(), weight.contiguous()
     bias = None if bias is None else bias.contiguous()
@@ -163,6 +174,7 @@ def deform_conv2d_forward(input, offset, weight, bias=None, stride=1, padding=0,
 def deform_conv2d_backward(input, offset, weight, grad_output, stride=1, padding=0, dilation=1, with_bias=False,
                            need=(True, True, True)):
     L.require_device(input, offset, weight, grad_output)
+    _require_input_dtype(input, offset=offset, weight=weight, grad_output=grad_output)
     s, p, d = _pair(stride), _pair(padding), _pair(dilation)
     input, offset, weight, grad_output = input.contiguous(), offset.contiguous(), weight.contiguous(), grad_output.contiguous()
     g = _geom2d(input.shape, weight.shape, s, p, d, offset.shape[1])
@@ -245,6 +257,7 @@ def deform_dwconv2d_backward_cl(x, offset, weight, grad_out, padding, dilation=1
 # ------------------------------------------------------------------------------------------------------------
 def conv3d_forward(input, weight, bias=None, stride=1, padding=0, dilation=1, groups=1):
     L.require_device(input, weight, bias)
+    _require_input_dtype(input, weight=weight, bias=bias)
     s, p, d = _triple(stride), _triple(padding), _triple(dilation)
     input, weight = input.contiguous(), weight.contiguous()
     bias = None if bias is None else bias.contiguous()
@@ -263,6 +276,7 @@ def conv3d_forward(input, weight, bias=None, stride=1, padding=0, dilation=1, gr
 
 def conv3d_backward(input, weight, grad_output, stride=1, padding=0, dilation=1, groups=1, need=(True, True, True)):
     L.require_device(input, weight, grad_output)
+    _require_input_dtype(input, weight=weight, grad_output=grad_output)
     s, p, d = _triple(stride), _triple(padding), _triple(dilation)
     input, weight, grad_output = input.contiguous(), weight.contiguous(), grad_output.contiguous()
     g = _geom(input.shape, weight.shape[0], tuple(weight.shape[2:5]), s, p, d, groups)

@@ -209,16 +209,21 @@ class WgradOverlap:
         return not ctx.wgrad_shared[0]
 
 
+# module -> weak references to its not-yet-differentiated applications.  Kept here, not on the module: a weakref in module.__dict__ makes
+# pickle.dumps(model) / torch.save(model) fail after the first training step.
+_WGRAD_LIVE = weakref.WeakKeyDictionary()
+
+
 def _note_application(mod, ctx):
     """Marks every not-yet-differentiated application of `mod` (incl. this one) as shared when there is more than one: see WgradOverlap.eligible."""
-    live = [r for r in getattr(mod, "_wgrad_live", ()) if r() is not None and not r().wgrad_done[0]]
+    live = [r for r in _WGRAD_LIVE.get(mod, ()) if r() is not None and not r().wgrad_done[0]]
     ctx.wgrad_shared, ctx.wgrad_done = [False], [False]
     if live:
         ctx.wgrad_shared[0] = True
         for r in live:
             r().wgrad_shared[0] = True
     live.append(weakref.ref(ctx))
-    mod._wgrad_live = live
+    _WGRAD_LIVE[mod] = live
 
 
 class _TBlock3dFn(Function):
@@ -294,8 +299,12 @@ class TransformerBlock_3D_single_deform_LKA(nn.Module):
     def _draw_drop_mask(self, B, C, dtype, device):
         """conv8[0] = Dropout3d: the same draw F.dropout3d makes for its (B, C, 1, 1, 1) noise tensor, bernoulli(1 - p) / (1 - p),
         from the device's generator.  The kernels only consume the [B, C] multipliers.  Drawn directly (two launches) rather than as dropout3d(ones) (four:
-        fill, draw, scale, multiply — 42 launches of ~4.7 us per 21-block step); same generator consumption, same values (tests/test_nets.py, GPU suite)."""
-        keep = 1.0 - self.conv8[0].p
+        fill, draw, scale, multiply — 42 launches of ~4.7 us per 21-block step); same generator consumption, same values for every p in [0, 1] (tests/test_nets.py,
+        tests/test_small_fixes.py)."""
+        p = self.conv8[0].p
+        if p >= 1 or p <= 0:   # as F.dropout3d: everything dropped (zeros, not 0 / 0) / nothing dropped, and no draw from the generator either way
+            return torch.full((B, C), 0.0 if p >= 1 else 1.0, dtype=dtype, device=device)
+        keep = 1.0 - p
         return torch.empty(B, C, 1, 1, 1, dtype=dtype, device=device).bernoulli_(keep).div_(keep).view(B, C)
 
     def wrapper_params(self):

@@ -295,7 +295,8 @@ int dlka_ndhwc_to_ncdhw(const void *src, void *dst, int B, int C, int N, int dty
  *     DLKA_F32   everything fp32 storage and fp32 accumulation (the parity path: 1e-4 forward, 1e-3 gradients against the reference).  ARITHMETIC of the contractions:
  *                the FORWARD deformable conv and the pointwise convs run on the fp32-input MFMA (exact fp32 products); the forward offset-predict conv as a THREE-term
  *                bf16 split (six products per fp32 product: fp32-equivalent — its output decides floor()); the BACKWARD contractions of the deformable conv (Col of
- *                grad_offset / grad_input), its WEIGHT gradient (fp32 grad_out x the samples grad_offset handed over as IEEE halves — a half is exactly two bf16 terms)
+ *                grad_offset / grad_input), its WEIGHT gradient (fp32 grad_out x the samples grad_offset handed over as IEEE halves — a half is exactly two bf16 terms; the halves are
+ *                sample * 2^e with one e per call taken from max |t|, so the hand-over does not depend on the activations' scale, and Inf / NaN samples propagate)
  *                and the offset conv's data / weight gradients as TWO-term bf16 splits (three products, fp32 accumulation, ~1e-5 relative: inside the 1e-3 gradient
  *                contract).  DLKA_EXACT_FP32=1 (environment, read once) puts every contraction on the fp32-input MFMA (and keeps the samples fp32);
  *     DLKA_BF16  x, y, grad_y, grad_x and every saved / intermediate activation are bf16 STORAGE; parameters (dlka_lka3d_params), their
@@ -518,6 +519,10 @@ long dlka_pw_chain_launch_count(void);
  * 16^3 / 8^3 / 4^3 stages — with the contraction split over the waves of ONE workgroup and summed in wave order in LDS: bitwise reproducible, no global atomics;
  * DLKA_CONV_KW=0 restores the tap split over the grid) and of the deformable forward's workgroup-split variants.  Tests assert which kernel ran. */
 long dlka_conv_kw_launch_count(void);
+/* Diagnostics: would a conv of this form take cl_conv_kw_kernel (1) or not (0)?  amode: 0 channels-last input, 2 planar gradient input; omode: 0 channels-last, 1 planar
+ * output; split_bf16: 0 exact fp32, 2 / 3 two- / three-term operands; K taps; epi: 0 none, 3 "+ aux"; NP: output columns padded to 32; volume: D > 1.  The planar store
+ * has no aux add, so epi = 3 with omode = 1 is refused (tests/test_small_fixes.py). */
+int dlka_conv_kw_applies(int amode, int omode, int split_bf16, int K, int epi, int NP, int act_bf16, int volume);
 /* launches so far of the opt-in software-pipelined depthwise kernel (csrc/cl_dwconv.hip: cl_dwconv_rows2p_kernel, round 6; DLKA_DW_2P=1 | 2 sends the dw 5^3 /
  * 7^3 dilation-3 convs and their data gradients through it wherever its geometry fits; default: never — it measured slower than the row kernel) */
 long dlka_dwconv_2p_launch_count(void);

@@ -25,6 +25,24 @@ def _refresh_switches():
     _lib.get_lib().dlka_env_refresh()
 
 
+def kernels_launched(fn):
+    """fn() under the launch trace (include/dlka.h dlka_trace_*; GPU only) -> the demangled names of the kernels the library launched, without the dlka:: prefix"""
+    from ctypes import create_string_buffer
+    from deformablelka_amd import _lib as L
+    lib = L.get_lib()
+    L.check(lib.dlka_trace_start(4096, torch.cuda.current_stream().cuda_stream), "trace_start")
+    try:
+        fn()
+    finally:
+        rc = lib.dlka_trace_stop()
+    L.check(rc, "trace_stop")
+    buf, names = create_string_buffer(512), set()
+    for i in range(lib.dlka_trace_count()):
+        L.check(lib.dlka_trace_get(i, buf, 512, None), "trace_get")
+        names.add(buf.value.decode().replace("void dlka::", "").replace("dlka::", "").split("(")[0])
+    return names
+
+
 def assert_close(name, got, ref, atol=None, rtol=None):
     got, ref = got.double().cpu(), ref.double().cpu()
     assert got.shape == ref.shape, (name, got.shape, ref.shape)
@@ -36,7 +54,8 @@ def assert_close(name, got, ref, atol=None, rtol=None):
         assert err <= rtol, f"{name}: max rel err {err:.3e} > {rtol}"
 
 
-def make_deform3d(B, C, Cout, dims, k, s, p, d, g, dg, off_mode="normal", seed=0, scale=1.0):
+def make_deform3d(B, C, Cout, dims, k, s, p, d, g, dg, off_mode="normal", seed=0, scale=1.0, x_log2=0, go_log2=0):
+    """x_log2 / go_log2: x and grad_out times 2^x_log2 / 2^go_log2 (exact: the same random numbers at another scale)."""
     gen = torch.Generator().manual_seed(seed)
     k3 = (k,) * 3 if isinstance(k, int) else tuple(k)
     s3 = (s,) * 3 if isinstance(s, int) else tuple(s)
@@ -61,6 +80,7 @@ def make_deform3d(B, C, Cout, dims, k, s, p, d, g, dg, off_mode="normal", seed=0
     else:
         off = torch.randn(shp, generator=gen) * scale
     go = torch.randn(B, Cout, Do, Ho, Wo, generator=torch.Generator().manual_seed(seed + 1))
+    x, go = x * 2.0 ** x_log2, go * 2.0 ** go_log2
     return x, off, w, b, go, (k3, s3, p3, d3)
 
 
@@ -222,16 +242,23 @@ def check_conv3d_cl(dev, B, C, Cout, dims, k, p, d, g, planar=False, seed=0):
     assert_close("conv3d_cl grad_bias", gb, br.grad, rtol=BWD_RTOL)
 
 
-def check_deform3d_cl(dev, B, C, Cout, dims, off_mode="normal", seed=0, dtype=torch.float32):
+def check_deform3d_cl(dev, B, C, Cout, dims, off_mode="normal", seed=0, dtype=torch.float32, x_log2=0, go_log2=0, go_hook=None):
     """dtype = torch.bfloat16: bf16 storage of x / out / grad_out (everything else fp32) against the oracle on the bf16-rounded activations, at the bf16
-    contract (BF16_RTOL of max |reference|, as tests/partial_grad_cases.py holds the same entry points to)."""
-    x, off, w, b, go, (k3, s3, p3, d3) = make_deform3d(B, C, Cout, dims, 3, 1, 1, 1, 1, 1, off_mode, seed)
+    contract (BF16_RTOL of max |reference|, as tests/partial_grad_cases.py holds the same entry points to).
+    x_log2 / go_log2: the activations / grad_out at another power-of-two scale (tests/scale_cases.py).  FWD_ATOL is an absolute bound on an output of magnitude ~1;
+    with x (and so the output) 2^x_log2 times larger, x_log2 > 0, one fp32 ulp of the output already exceeds it, so the bound scales with the output: FWD_ATOL * 2^x_log2.
+    At x_log2 <= 0 it stays FWD_ATOL.  The gradients' bound is relative and unchanged.  go_hook(go) -> go: edits grad_out before both sides see it."""
+    x, off, w, b, go, (k3, s3, p3, d3) = make_deform3d(B, C, Cout, dims, 3, 1, 1, 1, 1, 1, off_mode, seed, x_log2=x_log2, go_log2=go_log2)
+    if go_hook is not None:
+        go = go_hook(go)
     bf = dtype == torch.bfloat16
     if bf:
         x, go = x.bfloat16().float(), go.bfloat16().float()
     fwd_tol, bwd_tol = (dict(rtol=BF16_RTOL), dict(rtol=BF16_RTOL)) if bf else (dict(atol=FWD_ATOL), dict(rtol=BWD_RTOL))
     ref = oracle.deform_conv3d_forward(x, w, b, off, 1, 1, 1, 1, 1)
     out = ops.deform_conv3d_forward_cl(to_cl(x).to(dev).to(dtype), off.to(dev), w.to(dev), b.to(dev), 1, 1)
+    if x_log2 > 0 and not bf:
+        fwd_tol = dict(atol=FWD_ATOL * 2.0 ** x_log2)
     assert_close("deform3d_cl fwd", from_cl(out), ref, **fwd_tol)
     rgi, rgo, rgw, rgb = oracle.deform_conv3d_backward(x, w, b, off, go, 1, 1, 1, 1, 1, q1_literal=False)
     gi, goff, gw, gb = ops.deform_conv3d_backward_cl(to_cl(x).to(dev).to(dtype), off.to(dev), w.to(dev), to_cl(go).to(dev).to(dtype), 1, 1)
@@ -319,7 +346,8 @@ def check_deform3d_cl_gx_fx2_vs_fx1(dev, B, C, dims, off_mode="normal", scale=1.
     assert rel_err(g2, g64) < 4e-4
 
 
-def check_lka3d_tokens(dev, B, C, dims, seed=0, offset_std=0.02, atol=FWD_ATOL, rtol=BWD_RTOL, report_offsets=False, acdc=False, volume=False):
+def check_lka3d_tokens(dev, B, C, dims, seed=0, offset_std=0.02, atol=FWD_ATOL, rtol=BWD_RTOL, report_offsets=False, acdc=False, volume=False, prepare=None,
+                       grads_out=None):
     """Token-layout fused block vs the oracle block (oracle/blocks.py) at the CONTRACT's tolerances: forward 1e-4 abs (north_star), every
     gradient 1e-3 rel.
 
@@ -345,6 +373,8 @@ def check_lka3d_tokens(dev, B, C, dims, seed=0, offset_std=0.02, atol=FWD_ATOL, 
         m = dk.LKA_Attention3d_deform(C)
     variant = m.variant
     blocks.randomize_offsets_(m, std=offset_std)
+    if prepare is not None:   # (tests/scale_cases.py: rescales parameters; the oracle sees the module's state_dict AFTER it)
+        prepare(m)
     x = torch.randn(B, C, H, W, D) if volume else torch.randn(B, N, C)
     gy = torch.randn_like(x)
     m0 = {k: v.detach().clone() for k, v in m.state_dict().items()}
@@ -380,6 +410,8 @@ def check_lka3d_tokens(dev, B, C, dims, seed=0, offset_std=0.02, atol=FWD_ATOL, 
         _, captured["saved"] = ops.lka3d_attention_tokens_forward(x.detach().to(dev), [p_.detach() for p_ in m.block_params()], dims, variant)
     off_hip = ops.lka3d_tokens_saved_offsets(captured["saved"], B, C, dims).cpu().clone()
     grads = {k: p.grad for k, p in m.named_parameters()}
+    if grads_out is not None:
+        grads_out.update({k: g.detach().float().cpu().clone() for k, g in grads.items()})
     return compare_lka3d_with_oracle(f"tokens C={C} dims={dims}", oracle_fn, x, gy, m0, dims, y, xd.grad, grads, off_hip, atol=atol, rtol=rtol,
                                      report=report_offsets)
 
@@ -596,7 +628,7 @@ def check_tblock3d_forward_reproducible(dev, B, C, dims, training=True, runs=4, 
         assert torch.equal(cur[2], first[2]), f"run {r}: predicted offsets / activation patterns differ in {int((cur[2] != first[2]).sum())} elements"
 
 
-def check_lka3d_tokens_sample_handover(dev, B, C, dims, dtype=torch.float32, seed=0, offset_std=0.3):
+def check_lka3d_tokens_sample_handover(dev, B, C, dims, dtype=torch.float32, seed=0, offset_std=0.3, prepare=None):
     """The deformable conv's weight gradient from the samples the grad_offset kernel stores (default) against the weight-gradient kernel that
     gathers for itself (dlka_lka3d_force_wgrad_gather(1) / DLKA_WGRAD_GATHER=1): same fma chain for every sample, same MFMA order over the rows -> the two agree to summation
     order, and no other gradient notices the switch."""
@@ -606,6 +638,8 @@ def check_lka3d_tokens_sample_handover(dev, B, C, dims, dtype=torch.float32, see
     H, W, D = dims
     m = dk.LKA_Attention3d_deform(C)
     blocks.randomize_offsets_(m, std=offset_std)
+    if prepare is not None:
+        prepare(m)
     m = m.to(dev)
     x = torch.randn(B, H * W * D, C).to(dev).to(dtype)
     gy = torch.randn(B, H * W * D, C).to(dev).to(dtype)
@@ -633,6 +667,7 @@ def check_lka3d_tokens_sample_handover(dev, B, C, dims, dtype=torch.float32, see
         # agrees with the gathering kernel's to the rounding of the samples — a random-sign sum over M rows keeps its relative error at ~2^-12, 5e-4 of max at the outside
         tol = 2e-2 if dtype != torch.float32 else (5e-4 if name == k else 1e-5)
         assert rel_err(g_s[name], g_g[name]) < tol, (name, rel_err(g_s[name], g_g[name]))
+    return g_s
 
 
 def check_lka3d_tokens_pointwise_pair(dev, B, dims, dtype=torch.float32, seed=0):
@@ -806,7 +841,7 @@ def check_lka2d_attention_bf16(dev, B, C, H, W, seed=0, offset_std=0.03, rtol=No
 BF16_RTOL = 2e-2   # bf16 path vs the fp32 oracle <= 2e-2 rel (of max |reference|)
 
 
-def check_lka3d_tokens_bf16(dev, B, C, dims, seed=0, offset_std=0.38, rtol=BF16_RTOL, via_autocast=False, report=False):
+def check_lka3d_tokens_bf16(dev, B, C, dims, seed=0, offset_std=0.38, rtol=BF16_RTOL, via_autocast=False, report=False, prepare=None):
     """DLKA_BF16 token path: bf16 activations (x, y, every saved tensor, the intermediate gradients), fp32 parameters / offsets /
     accumulation — against the fp32 oracle block fed the SAME bf16-rounded input.  via_autocast: fp32 tensors inside torch.autocast(bf16)
     (the block's autocast policy) instead of explicit bf16 tensors."""
@@ -817,6 +852,8 @@ def check_lka3d_tokens_bf16(dev, B, C, dims, seed=0, offset_std=0.38, rtol=BF16_
     N = H * W * D
     m = dk.LKA_Attention3d_deform(C)
     blocks.randomize_offsets_(m, std=offset_std)
+    if prepare is not None:
+        prepare(m)
     x = torch.randn(B, N, C).bfloat16()
     gy = torch.randn(B, N, C).bfloat16()
     def run_oracle(store):
@@ -1130,7 +1167,7 @@ def kink_report(pre_out):
 
 
 def check_tblock3d(dev, B, C, dims, training, pos, seed=0, offset_std=0.02, atol=FWD_ATOL, rtol=BWD_RTOL, chain=False, report=False, acdc=False,
-                   token_mean_over_std=0.0):
+                   token_mean_over_std=0.0, prepare=None):
     """The fused wrapper block vs the oracle composition (oracle/blocks.py transformer_block_3d): forward 1e-4 abs (north_star), EVERY gradient 1e-3 rel
     (SURVEY §8c), every element of it — on identical sampling cells (the oracle fed the kernels' predicted offsets, as check_lka3d_tokens does) and on the
     kernels' activation pattern at UnetResBlock's two LeakyReLUs (kink protocol above: disagreements counted and capped).  chain=True: two applications of the
@@ -1149,6 +1186,8 @@ def check_tblock3d(dev, B, C, dims, training, pos, seed=0, offset_std=0.02, atol
     else:
         m = dk.TransformerBlock_3D_single_deform_LKA(N, C, C, 4, dropout_rate=0.1, pos_embed=pos)
     blocks.randomize_offsets_(m, std=offset_std)
+    if prepare is not None:
+        prepare(m)
     with torch.no_grad():
         m.gamma.normal_(0.5, 0.2)
         if pos:

@@ -1234,22 +1234,7 @@ def test_weight_preparation_tiled_equals_elementwise(bf):
 # ---- the large-LDS kernel families (dynamic LDS above 64 KB: prepared per family, csrc/dlka_common.h prepare_large_lds) -----------------------------------
 # The emulator never runs the preparation, so every member that a default code path can select has a case on the GPU; the library's launch trace names the
 # kernel that ran.
-def _kernels_launched(fn):
-    """fn() under the launch trace (include/dlka.h dlka_trace_*) -> the demangled names of the kernels the library launched, without the dlka:: prefix"""
-    from ctypes import create_string_buffer
-    from deformablelka_amd import _lib as L
-    lib = L.get_lib()
-    L.check(lib.dlka_trace_start(4096, torch.cuda.current_stream().cuda_stream), "trace_start")
-    try:
-        fn()
-    finally:
-        rc = lib.dlka_trace_stop()
-    L.check(rc, "trace_stop")
-    buf, names = create_string_buffer(512), set()
-    for i in range(lib.dlka_trace_count()):
-        L.check(lib.dlka_trace_get(i, buf, 512, None), "trace_get")
-        names.add(buf.value.decode().replace("void dlka::", "").replace("dlka::", "").split("(")[0])
-    return names
+_kernels_launched = parity.kernels_launched   # (shared with tests/scale_cases.py)
 
 
 @pytest.mark.parametrize("dims,window", [((8, 8, 16), "18, 10, 14"), ((4, 4, 32), "34, 10, 10")])
