@@ -94,9 +94,7 @@ int dlka::tokens_forward_impl(const void *x_, const dlka_lka3d_params *p, void *
                               size_t workspace_bytes, int B, int C, int D, int H, int W, int dtype, void *stream, bool prepared,
                               int variant, const float *x_f32)
 {
-    if (!x_ || !p || !y_ || !saved || !workspace) return DLKA_ERR_NULL;
-    const void *const *pp = (const void *const *)p;
-    for (size_t k = 0; k < sizeof(*p) / sizeof(void *); ++k) if (!pp[k]) return DLKA_ERR_NULL;
+    if (!x_ || !all_set(p) || !y_ || !saved || !workspace) return DLKA_ERR_NULL;
     if (!dlka_lka3d_tokens_supported_v(B, C, D, H, W, dtype, variant)) return DLKA_ERR_UNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;
     // DLKA_BF16: x, y and every saved activation are bf16 storage (`float *` below is then just an address: the kernels reinterpret it);
@@ -408,10 +406,7 @@ int dlka::tokens_backward_impl(const void *x_, const dlka_lka3d_params *p, const
 {
     if (!x_ || !p || !gy_ || !saved || !gx_ || !gr || !workspace) return DLKA_ERR_NULL;
     if (phase < 0 || phase > 2) return DLKA_ERR_SHAPE;
-    const void *const *pp = (const void *const *)p;
-    for (size_t k = 0; k < sizeof(*p) / sizeof(void *); ++k) if (!pp[k]) return DLKA_ERR_NULL;
-    void *const *gp = (void *const *)gr;
-    for (size_t k = 0; k < sizeof(*gr) / sizeof(void *); ++k) if (!gp[k]) return DLKA_ERR_NULL;
+    if (!all_set(p) || !all_set(gr)) return DLKA_ERR_NULL;
     if (!dlka_lka3d_tokens_supported_v(B, C, D, H, W, dtype, variant)) return DLKA_ERR_UNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;
     // DLKA_BF16: x, gy, gx, the saved activations and the intermediate gradients gg1, ga1, gf, gt, gt1, gh are bf16 storage; grad_offset, the

@@ -198,8 +198,7 @@ int dlka_tblock3d_forward_v(const void *x, int x_planar, const dlka_tblock3d_par
         if (dense_forward_splits(G.pw, 3) > 1) add_zero((float *)y, G.E);
         // ... and the attention's own fifteen forms go out with them (round 5: one launch per block less in the path the trainers call; the attention's zero fills ride
         // in its first kernel, as they do behind the engine's hoisted preparation)
-        const void *const *pp = (const void *const *)lka;
-        for (size_t k = 0; k < sizeof(*lka) / sizeof(void *); ++k) if (!pp[k]) return DLKA_ERR_NULL;
+        if (!all_set(lka)) return DLKA_ERR_NULL;
         Carver lsv(S.lka, S.lka_bytes);
         const TokSaved LS = carve_tok_saved(lsv, G.lka);
         if (!lsv.ok()) return DLKA_ERR_WORKSPACE;

@@ -71,6 +71,16 @@ size_t carved_bytes(Carve carve)
         if (rc_ != DLKA_OK) return rc_; \
     } while (0)
 
+// whether `s` and every member of it are set; S: a struct of nothing but pointers (dlka_lka3d_params, dlka_lka2d_grads, ...)
+template <class S>
+bool all_set(const S *s)
+{
+    static_assert(sizeof(S) % sizeof(void *) == 0, "a struct of pointers");
+    const void *const *p = (const void *const *)s;
+    for (size_t i = 0; p && i < sizeof(S) / sizeof(void *); ++i) if (!p[i]) return false;
+    return p != nullptr;
+}
+
 // a stride-1, same-size convolution in channels-last layout
 struct SameConv {
     int B, D, H, W, N, M, Cin, Cout, group;

@@ -2,6 +2,7 @@
 // reference's AT_ASSERTM checks (3D/dcn/src/cuda/deform_conv_cuda.cu:41-76,193-200), workspace carving and the
 // launch sequences.  No allocation, no synchronisation: every function is legal inside hipGraph capture.
 #include <algorithm>
+#include <initializer_list>
 
 #include "cl_host.h"
 
@@ -74,37 +75,47 @@ int deform_forward_t(const void *x, const void *off, const void *w, const void *
     return launch_deform_fwd<T, NOFF>((const T *)x, (const T *)off, (const T *)w, (const T *)bias, (T *)out, wt, g, st);
 }
 
+// The backward pass of a deformable conv, written once for the operator entries and both blocks.  Every output may be null: gx || goff gates the weight
+// relayout and the input / offset kernel, gw the weight part, gb the bias part (the 2-D block's depthwise deformable convs have no bias).
+// wt: deform_fwd_wt_floats(g) floats for the re-laid-out weight.  grad_input and grad_weight are accumulated in fp32: in the output itself for T = float,
+// else in the caller's gx32buf / gw32buf (B C Ni and Cout Cg K floats; gx32buf may be null where gx is) and cast into the output afterwards.
+// (w, gw, gb: tensors of T, untyped as the parameter records of the blocks and the entry points hold them.)
 template <typename T, int NOFF>
-int deform_backward_t(const void *x, const void *off, const void *w, const void *gout, void *gx, void *goff, void *gw,
-                      void *gb, void *ws, size_t wsb, const Geom &g, int dtype, hipStream_t st)
+int deform_bwd_seq(const T *x, const T *off, const void *w, const T *gout, T *gx, T *goff, void *gw, void *gb, float *wt, float *gx32buf, float *gw32buf,
+                   const Geom &g, hipStream_t st)
 {
-    Carver cv(ws, wsb);
-    const int cob = deform_pick_cob(g.Og);
-    const int OgP = round_up(g.Og, cob);
-    float *wt = (float *)cv.take((size_t)deform_fwd_wt_floats(g) * 4);
-    float *gx32 = nullptr, *gw32 = nullptr;
+    constexpr bool f32 = std::is_same<T, float>::value;
+    const int OgP = round_up(g.Og, deform_pick_cob(g.Og));
     const size_t nx = (size_t)g.B * g.C * g.Ni, nw = (size_t)g.Cout * g.Cg * g.K;
-    if (dtype == DLKA_F32) {
-        gx32 = (float *)gx;
-        gw32 = (float *)gw;
-    } else {
-        if (gx) gx32 = (float *)cv.take(nx * 4);
-        if (gw) gw32 = (float *)cv.take(nw * 4);
-    }
-    if (!cv.ok() || !wt) return DLKA_ERR_WORKSPACE;
+    float *gx32 = f32 ? (float *)gx : gx32buf, *gw32 = f32 ? (float *)gw : gw32buf;
     if (gx || goff) {
         DLKA_TRY(launch_relayout_weight<T>((const T *)w, wt, g.group, g.Og, g.Cg, g.K, OgP, st));
         if (gx32) { if (launch_zero(gx32, nx * 4, st) != DLKA_OK) return DLKA_ERR_LAUNCH; }
-        DLKA_TRY((launch_deform_bwd_input_offset<T, NOFF>((const T *)x, (const T *)off, wt, OgP, (const T *)gout, gx32, (T *)goff, g, st)));
-        if (gx && dtype != DLKA_F32) DLKA_TRY(launch_cast_from_f32<T>(gx32, (T *)gx, (long)nx, st));
+        DLKA_TRY((launch_deform_bwd_input_offset<T, NOFF>(x, off, wt, OgP, gout, gx32, goff, g, st)));
+        if (gx && !f32) DLKA_TRY(launch_cast_from_f32<T>(gx32, gx, (long)nx, st));
     }
     if (gw) {
         if (launch_zero(gw32, nw * 4, st) != DLKA_OK) return DLKA_ERR_LAUNCH;
-        DLKA_TRY((launch_deform_bwd_weight<T, NOFF>((const T *)x, (const T *)off, (const T *)gout, gw32, g, st)));
-        if (dtype != DLKA_F32) DLKA_TRY(launch_cast_from_f32<T>(gw32, (T *)gw, (long)nw, st));
+        DLKA_TRY((launch_deform_bwd_weight<T, NOFF>(x, off, gout, gw32, g, st)));
+        if (!f32) DLKA_TRY(launch_cast_from_f32<T>(gw32, (T *)gw, (long)nw, st));
     }
-    if (gb) DLKA_TRY(launch_bias_grad<T>((const T *)gout, (T *)gb, g.B, g.Cout, g.No, st));
+    if (gb) DLKA_TRY(launch_bias_grad<T>(gout, (T *)gb, g.B, g.Cout, g.No, st));
     return DLKA_OK;
+}
+
+template <typename T, int NOFF>
+int deform_backward_t(const void *x, const void *off, const void *w, const void *gout, void *gx, void *goff, void *gw,
+                      void *gb, void *ws, size_t wsb, const Geom &g, hipStream_t st)
+{
+    Carver cv(ws, wsb);
+    float *wt = (float *)cv.take((size_t)deform_fwd_wt_floats(g) * 4);
+    float *gx32 = nullptr, *gw32 = nullptr;
+    if (!std::is_same<T, float>::value) {   // (the areas deform_bwd_ws adds for dtype != DLKA_F32)
+        if (gx) gx32 = (float *)cv.take((size_t)g.B * g.C * g.Ni * 4);
+        if (gw) gw32 = (float *)cv.take((size_t)g.Cout * g.Cg * g.K * 4);
+    }
+    if (!cv.ok() || !wt) return DLKA_ERR_WORKSPACE;
+    return deform_bwd_seq<T, NOFF>((const T *)x, (const T *)off, w, (const T *)gout, (T *)gx, (T *)goff, gw, gb, wt, gx32, gw32, g, st);
 }
 
 size_t conv_fwd_ws(const Geom &g) { return align256((size_t)conv_fwd_wt_floats(g) * 4); }
@@ -125,26 +136,35 @@ int conv_forward_t(const void *x, const void *w, const void *bias, void *out, vo
     return launch_conv_fwd<T>((const T *)x, (const T *)w, (const T *)bias, (T *)out, wt, g, st);
 }
 
+// The backward pass of a plain conv, written once for the operator entry and both blocks; gx, gw and gb may each be null.  wb: conv_bwd_wb_floats(g) floats.
+// grad_weight is accumulated in fp32: in gw itself for T = float, else in gw32buf (Cout Cg K floats) and cast afterwards.  part: the weight gradient's
+// partial-tile buffer (conv_bwd_weight_part_floats) or null — WHICH weight-gradient kernel runs depends on it (launch_conv_bwd_weight).  w, gw, gb: as above.
 template <typename T>
-int conv_backward_t(const void *x, const void *w, const void *gout, void *gx, void *gw, void *gb, void *ws, size_t wsb,
-                    const Geom &g, int dtype, hipStream_t st)
+int conv_bwd_seq(const T *x, const void *w, const T *gout, T *gx, void *gw, void *gb, float *wb, float *gw32buf, float *part, const Geom &g, hipStream_t st)
+{
+    constexpr bool f32 = std::is_same<T, float>::value;
+    const size_t nw = (size_t)g.Cout * g.Cg * g.K;
+    if (gx) DLKA_TRY(launch_conv_bwd_data<T>(gout, (const T *)w, gx, wb, g, st));
+    if (gw) {
+        float *gw32 = f32 ? (float *)gw : gw32buf;
+        if (launch_zero(gw32, nw * 4, st) != DLKA_OK) return DLKA_ERR_LAUNCH;
+        DLKA_TRY(launch_conv_bwd_weight<T>(x, gout, gw32, g, st, part));
+        if (!f32) DLKA_TRY(launch_cast_from_f32<T>(gw32, (T *)gw, (long)nw, st));
+    }
+    if (gb) DLKA_TRY(launch_bias_grad<T>(gout, (T *)gb, g.B, g.Cout, g.No, st));
+    return DLKA_OK;
+}
+
+template <typename T>
+int conv_backward_t(const void *x, const void *w, const void *gout, void *gx, void *gw, void *gb, void *ws, size_t wsb, const Geom &g, hipStream_t st)
 {
     Carver cv(ws, wsb);
     float *wb = (float *)cv.take((size_t)conv_bwd_wb_floats(g) * 4);
-    const size_t nw = (size_t)g.Cout * g.Cg * g.K;
-    float *gw32 = nullptr;
-    if (gw) gw32 = (dtype == DLKA_F32) ? (float *)gw : (float *)cv.take(nw * 4);
+    float *gw32 = gw && !std::is_same<T, float>::value ? (float *)cv.take((size_t)g.Cout * g.Cg * g.K * 4) : nullptr;
     const size_t npart = conv_bwd_weight_part_floats(g, sizeof(T));
     float *part = npart ? (float *)cv.take(npart * 4) : nullptr;
     if (!cv.ok() || !wb) return DLKA_ERR_WORKSPACE;
-    if (gx) DLKA_TRY(launch_conv_bwd_data<T>((const T *)gout, (const T *)w, (T *)gx, wb, g, st));
-    if (gw) {
-        if (launch_zero(gw32, nw * 4, st) != DLKA_OK) return DLKA_ERR_LAUNCH;
-        DLKA_TRY(launch_conv_bwd_weight<T>((const T *)x, (const T *)gout, gw32, g, st, part));
-        if (dtype != DLKA_F32) DLKA_TRY(launch_cast_from_f32<T>(gw32, (T *)gw, (long)nw, st));
-    }
-    if (gb) DLKA_TRY(launch_bias_grad<T>((const T *)gout, (T *)gb, g.B, g.Cout, g.No, st));
-    return DLKA_OK;
+    return conv_bwd_seq<T>((const T *)x, w, (const T *)gout, (T *)gx, gw, gb, wb, gw32, part, g, st);
 }
 
 // ---- geometry builders for the fixed convs of the two blocks --------------------------------------------
@@ -163,6 +183,25 @@ Geom conv_geom(int B, int C, int Cout, int D, int H, int W, int kd, int kh, int 
     return g;
 }
 
+// ---- sizes over the convs of a block -----------------------------------------------------------------------------------
+using GeomList = std::initializer_list<const Geom *>;
+// floats of the ONE scratch area every conv of a block re-lays its weight into: the largest forward / backward relayout of `convs`, and the largest
+// deformable relayout of `deforms`
+size_t max_relayout_floats(GeomList convs, GeomList deforms)
+{
+    int m = 0;
+    for (const Geom *g : convs) m = std::max({m, conv_fwd_wt_floats(*g), conv_bwd_wb_floats(*g)});
+    for (const Geom *g : deforms) m = std::max(m, deform_fwd_wt_floats(*g));
+    return (size_t)m;
+}
+// elements of the largest weight tensor (the fp32 grad_weight accumulator of the bf16 path)
+size_t largest_weight_elems(GeomList convs)
+{
+    size_t m = 0;
+    for (const Geom *g : convs) m = std::max(m, (size_t)g->Cout * g->Cg * g->K);
+    return m;
+}
+
 struct Lka3dGeoms {
     Geom pw, dw5, dw7, offc, dcn;
     long E, Off;
@@ -176,27 +215,10 @@ struct Lka3dGeoms {
         E = (long)B * C * D * H * W;
         Off = (long)B * 81 * D * H * W;
     }
-    size_t scratch_floats() const
-    {
-        size_t m = 0;
-        const Geom *all[5] = {&pw, &dw5, &dw7, &offc, &dcn};
-        for (const Geom *g : all) {
-            m = m > (size_t)conv_fwd_wt_floats(*g) ? m : (size_t)conv_fwd_wt_floats(*g);
-            m = m > (size_t)conv_bwd_wb_floats(*g) ? m : (size_t)conv_bwd_wb_floats(*g);
-        }
-        m = m > (size_t)deform_fwd_wt_floats(dcn) ? m : (size_t)deform_fwd_wt_floats(dcn);
-        return m;
-    }
-    size_t max_weight_elems() const
-    {
-        size_t m = 0;
-        const Geom *all[5] = {&pw, &dw5, &dw7, &offc, &dcn};
-        for (const Geom *g : all) {
-            size_t n = (size_t)g->Cout * g->Cg * g->K;
-            m = m > n ? m : n;
-        }
-        return m;
-    }
+    // the deformable relayout over dcn alone, the block's one deformable conv.  (Lka2dGeoms takes it over all five; callers size their buffers by these
+    // numbers, so neither term may change.)
+    size_t scratch_floats() const { return max_relayout_floats({&pw, &dw5, &dw7, &offc, &dcn}, {&dcn}); }
+    size_t max_weight_elems() const { return largest_weight_elems({&pw, &dw5, &dw7, &offc, &dcn}); }
 };
 
 // ---- buffer layouts of the planar blocks (3-D and 2-D; GEOMS = Lka3dGeoms / Lka2dGeoms): one record and ONE carve function per buffer and direction ----
@@ -267,22 +289,6 @@ int lka3d_forward_t(const void *x, const dlka_lka3d_params *p, void *y, void *sa
 }
 
 template <typename T>
-int conv_bwd_all(const T *xin, const T *w, const T *gout, T *gx, void *gw, void *gb, float *scratch, float *gw32buf,
-                 const Geom &g, int dtype, hipStream_t st)
-{
-    const size_t nw = (size_t)g.Cout * g.Cg * g.K;
-    if (gx) DLKA_TRY(launch_conv_bwd_data<T>(gout, w, gx, scratch, g, st));
-    if (gw) {
-        float *gw32 = (dtype == DLKA_F32) ? (float *)gw : gw32buf;
-        if (launch_zero(gw32, nw * 4, st) != DLKA_OK) return DLKA_ERR_LAUNCH;
-        DLKA_TRY(launch_conv_bwd_weight<T>(xin, gout, gw32, g, st));
-        if (dtype != DLKA_F32) DLKA_TRY(launch_cast_from_f32<T>(gw32, (T *)gw, (long)nw, st));
-    }
-    if (gb) DLKA_TRY(launch_bias_grad<T>(gout, (T *)gb, g.B, g.Cout, g.No, st));
-    return DLKA_OK;
-}
-
-template <typename T>
 int lka3d_backward_t(const void *x_, const dlka_lka3d_params *p, const void *gy_, const void *saved, size_t savedb, void *gx_,
                      const dlka_lka3d_grads *gr, void *ws, size_t wsb, int B, int C, int D, int H, int W, int dtype, hipStream_t st)
 {
@@ -297,41 +303,28 @@ int lka3d_backward_t(const void *x_, const dlka_lka3d_params *p, const void *gy_
     const T *x = (const T *)x_, *gy = (const T *)gy_;
     T *gx = (T *)gx_;
 
+    // conv_bwd_seq's `nullptr` below: the blocks carve no partial-tile buffer, so the weight gradients take the kernels that need none
     // proj_2 (+ residual: d(x + ...)/dx adds gy at the very end)                           transformerblock.py:670-671
     DLKA_TRY(launch_mul_fwd<T>(a, g1, bA, G.E, st));                                        // m = a * g1 (recomputed)
-    DLKA_TRY(conv_bwd_all<T>(bA, (const T *)p->proj_2_w, gy, bB, gr->proj_2_w, gr->proj_2_b, scr, gw32, G.pw, dtype, st));  // bB = gm
+    DLKA_TRY(conv_bwd_seq<T>(bA, p->proj_2_w, gy, bB, gr->proj_2_w, gr->proj_2_b, scr, gw32, nullptr, G.pw, st));  // bB = gm
     // gate u * attn                                                                        :652
     DLKA_TRY(launch_mul_bwd<T>(a, g1, bB, bC, bD, G.E, st));                                // bC = ga1 = gm*g1 ; bD = gg1 = gm*a
     // conv1                                                                                :650
-    DLKA_TRY(conv_bwd_all<T>(f, (const T *)p->conv1_w, bD, bB, gr->conv1_w, gr->conv1_b, scr, gw32, G.pw, dtype, st));      // bB = gf
+    DLKA_TRY(conv_bwd_seq<T>(f, p->conv1_w, bD, bB, gr->conv1_w, gr->conv1_b, scr, gw32, nullptr, G.pw, st));      // bB = gf
     // deformable conv                                                                      deform_conv.py:95-105
-    {
-        const Geom &g = G.dcn;
-        const int OgP = round_up(g.Og, deform_pick_cob(g.Og));
-        const size_t nx = (size_t)G.E, nw = (size_t)g.Cout * g.Cg * g.K;
-        float *gxa = (dtype == DLKA_F32) ? (float *)bA : gx32;
-        float *gwa = (dtype == DLKA_F32) ? (float *)gr->deform_w : gw32;
-        DLKA_TRY(launch_relayout_weight<T>((const T *)p->deform_w, scr, g.group, g.Og, g.Cg, g.K, OgP, st));
-        if (launch_zero(gxa, nx * 4, st) != DLKA_OK) return DLKA_ERR_LAUNCH;
-        DLKA_TRY((launch_deform_bwd_input_offset<T, 3>(t, off, scr, OgP, bB, gxa, bO, g, st)));   // bA = gt_a, bO = goff
-        if (dtype != DLKA_F32) DLKA_TRY(launch_cast_from_f32<T>(gxa, bA, (long)nx, st));
-        if (launch_zero(gwa, nw * 4, st) != DLKA_OK) return DLKA_ERR_LAUNCH;
-        DLKA_TRY((launch_deform_bwd_weight<T, 3>(t, off, bB, gwa, g, st)));
-        if (dtype != DLKA_F32) DLKA_TRY(launch_cast_from_f32<T>(gwa, (T *)gr->deform_w, (long)nw, st));
-        DLKA_TRY(launch_bias_grad<T>(bB, (T *)gr->deform_b, g.B, g.Cout, g.No, st));
-    }
+    DLKA_TRY((deform_bwd_seq<T, 3>(t, off, p->deform_w, bB, bA, bO, gr->deform_w, gr->deform_b, scr, gx32, gw32, G.dcn, st)));  // bA = gt_a, bO = goff
     // offset-predict conv                                                                  deform_conv.py:94
-    DLKA_TRY(conv_bwd_all<T>(t, (const T *)p->offset_w, bO, bD, gr->offset_w, gr->offset_b, scr, gw32, G.offc, dtype, st)); // bD = gt_b
+    DLKA_TRY(conv_bwd_seq<T>(t, p->offset_w, bO, bD, gr->offset_w, gr->offset_b, scr, gw32, nullptr, G.offc, st)); // bD = gt_b
     DLKA_TRY(launch_add_fwd<T>(bA, bD, bA, G.E, st));                                       // bA = gt
     // depthwise 7^3 dil 3                                                                  :647
-    DLKA_TRY(conv_bwd_all<T>(t1, (const T *)p->conv_spatial_w, bA, bB, gr->conv_spatial_w, gr->conv_spatial_b, scr, gw32, G.dw7, dtype, st));  // bB = gt1
+    DLKA_TRY(conv_bwd_seq<T>(t1, p->conv_spatial_w, bA, bB, gr->conv_spatial_w, gr->conv_spatial_b, scr, gw32, nullptr, G.dw7, st));  // bB = gt1
     // depthwise 5^3                                                                        :646
-    DLKA_TRY(conv_bwd_all<T>(a, (const T *)p->conv0_w, bB, bD, gr->conv0_w, gr->conv0_b, scr, gw32, G.dw5, dtype, st));     // bD = ga2
+    DLKA_TRY(conv_bwd_seq<T>(a, p->conv0_w, bB, bD, gr->conv0_w, gr->conv0_b, scr, gw32, nullptr, G.dw5, st));     // bD = ga2
     DLKA_TRY(launch_add_fwd<T>(bC, bD, bC, G.E, st));                                       // bC = ga
     // GELU                                                                                 :668
     DLKA_TRY(launch_gelu_bwd<T>(h, bC, bA, G.E, st));                                       // bA = gh
     // proj_1                                                                               :667
-    DLKA_TRY(conv_bwd_all<T>(x, (const T *)p->proj_1_w, bA, bB, gr->proj_1_w, gr->proj_1_b, scr, gw32, G.pw, dtype, st));   // bB = gx1
+    DLKA_TRY(conv_bwd_seq<T>(x, p->proj_1_w, bA, bB, gr->proj_1_w, gr->proj_1_b, scr, gw32, nullptr, G.pw, st));   // bB = gx1
     DLKA_TRY(launch_add_fwd<T>(bB, gy, gx, G.E, st));                                       // + shortcut
     return DLKA_OK;
 }
@@ -351,27 +344,9 @@ struct Lka2dGeoms {
         Off5 = (long)B * 50 * H * W;
         Off7 = (long)B * 98 * H * W;
     }
-    size_t scratch_floats() const
-    {
-        size_t m = 0;
-        const Geom *all[5] = {&pw, &off5, &dcn5, &off7, &dcn7};
-        for (const Geom *g : all) {
-            m = m > (size_t)conv_fwd_wt_floats(*g) ? m : (size_t)conv_fwd_wt_floats(*g);
-            m = m > (size_t)conv_bwd_wb_floats(*g) ? m : (size_t)conv_bwd_wb_floats(*g);
-            m = m > (size_t)deform_fwd_wt_floats(*g) ? m : (size_t)deform_fwd_wt_floats(*g);
-        }
-        return m;
-    }
-    size_t max_weight_elems() const
-    {
-        size_t m = 0;
-        const Geom *all[5] = {&pw, &off5, &dcn5, &off7, &dcn7};
-        for (const Geom *g : all) {
-            size_t n = (size_t)g->Cout * g->Cg * g->K;
-            m = m > n ? m : n;
-        }
-        return m;
-    }
+    // the deformable relayout over ALL five, the three plain convs included: more than dcn5 and dcn7 need, and unlike Lka3dGeoms — see there
+    size_t scratch_floats() const { return max_relayout_floats({&pw, &off5, &dcn5, &off7, &dcn7}, {&pw, &off5, &dcn5, &off7, &dcn7}); }
+    size_t max_weight_elems() const { return largest_weight_elems({&pw, &off5, &dcn5, &off7, &dcn7}); }
 };
 
 template <typename T> struct PlanarSaved2d { T *h, *a, *o5, *t1, *o7, *t2, *g1; };
@@ -408,26 +383,6 @@ int lka2d_forward_t(const void *x, const dlka_lka2d_params *p, void *y, void *sa
     return DLKA_OK;
 }
 
-// deformable depthwise conv backward inside the 2-D block: input `xin`, offsets `off`, grad_out `go`
-// -> gxin (T buffer), goff (T buffer), grad weight
-template <typename T>
-int deform2d_bwd_all(const T *xin, const T *off, const T *w, const T *go, T *gxin, T *goff, void *gw, float *scr, float *gx32,
-                     float *gw32buf, const Geom &g, int dtype, hipStream_t st)
-{
-    const int OgP = round_up(g.Og, deform_pick_cob(g.Og));
-    const size_t nx = (size_t)g.B * g.C * g.Ni, nw = (size_t)g.Cout * g.Cg * g.K;
-    float *gxa = (dtype == DLKA_F32) ? (float *)gxin : gx32;
-    float *gwa = (dtype == DLKA_F32) ? (float *)gw : gw32buf;
-    DLKA_TRY(launch_relayout_weight<T>(w, scr, g.group, g.Og, g.Cg, g.K, OgP, st));
-    if (launch_zero(gxa, nx * 4, st) != DLKA_OK) return DLKA_ERR_LAUNCH;
-    DLKA_TRY((launch_deform_bwd_input_offset<T, 2>(xin, off, scr, OgP, go, gxa, goff, g, st)));
-    if (dtype != DLKA_F32) DLKA_TRY(launch_cast_from_f32<T>(gxa, gxin, (long)nx, st));
-    if (launch_zero(gwa, nw * 4, st) != DLKA_OK) return DLKA_ERR_LAUNCH;
-    DLKA_TRY((launch_deform_bwd_weight<T, 2>(xin, off, go, gwa, g, st)));
-    if (dtype != DLKA_F32) DLKA_TRY(launch_cast_from_f32<T>(gwa, (T *)gw, (long)nw, st));
-    return DLKA_OK;
-}
-
 template <typename T>
 int lka2d_backward_t(const void *x_, const dlka_lka2d_params *p, const void *gy_, const void *saved, size_t savedb, void *gx_,
                      const dlka_lka2d_grads *gr, void *ws, size_t wsb, int B, int C, int H, int W, int dtype, hipStream_t st)
@@ -442,23 +397,94 @@ int lka2d_backward_t(const void *x_, const dlka_lka2d_params *p, const void *gy_
     float *scr = Wb.scr, *gw32 = Wb.gw32, *gx32 = Wb.gx32;
     const T *x = (const T *)x_, *gy = (const T *)gy_;
     T *gx = (T *)gx_;
+    // (conv_bwd_seq's `nullptr`: no partial-tile buffer, as in lka3d_backward_t)
     DLKA_TRY(launch_mul_fwd<T>(a, g1, bA, G.E, st));                                                                        // m
-    DLKA_TRY(conv_bwd_all<T>(bA, (const T *)p->proj_2_w, gy, bB, gr->proj_2_w, gr->proj_2_b, scr, gw32, G.pw, dtype, st));  // bB = gm
+    DLKA_TRY(conv_bwd_seq<T>(bA, p->proj_2_w, gy, bB, gr->proj_2_w, gr->proj_2_b, scr, gw32, nullptr, G.pw, st));  // bB = gm
     DLKA_TRY(launch_mul_bwd<T>(a, g1, bB, bC, bD, G.E, st));                                                                // bC = ga1, bD = gg1
-    DLKA_TRY(conv_bwd_all<T>(t2, (const T *)p->conv1_w, bD, bB, gr->conv1_w, gr->conv1_b, scr, gw32, G.pw, dtype, st));     // bB = gt2
+    DLKA_TRY(conv_bwd_seq<T>(t2, p->conv1_w, bD, bB, gr->conv1_w, gr->conv1_b, scr, gw32, nullptr, G.pw, st));     // bB = gt2
     // conv_spatial: t2 = dcn7(t1, o7 = off7(t1))
-    DLKA_TRY(deform2d_bwd_all<T>(t1, o7, (const T *)p->conv_spatial_w, bB, bA, bO, gr->conv_spatial_w, scr, gx32, gw32, G.dcn7, dtype, st));  // bA = gt1_a, bO = go7
-    DLKA_TRY(conv_bwd_all<T>(t1, (const T *)p->conv_spatial_offset_w, bO, bD, gr->conv_spatial_offset_w, gr->conv_spatial_offset_b, scr, gw32, G.off7, dtype, st));  // bD = gt1_b
+    DLKA_TRY((deform_bwd_seq<T, 2>(t1, o7, p->conv_spatial_w, bB, bA, bO, gr->conv_spatial_w, nullptr, scr, gx32, gw32, G.dcn7, st)));  // bA = gt1_a, bO = go7
+    DLKA_TRY(conv_bwd_seq<T>(t1, p->conv_spatial_offset_w, bO, bD, gr->conv_spatial_offset_w, gr->conv_spatial_offset_b, scr, gw32, nullptr, G.off7, st));  // bD = gt1_b
     DLKA_TRY(launch_add_fwd<T>(bA, bD, bA, G.E, st));                                                                       // bA = gt1
     // conv0: t1 = dcn5(a, o5 = off5(a))
-    DLKA_TRY(deform2d_bwd_all<T>(a, o5, (const T *)p->conv0_w, bA, bB, bO, gr->conv0_w, scr, gx32, gw32, G.dcn5, dtype, st));  // bB = ga2_a, bO = go5
-    DLKA_TRY(conv_bwd_all<T>(a, (const T *)p->conv0_offset_w, bO, bD, gr->conv0_offset_w, gr->conv0_offset_b, scr, gw32, G.off5, dtype, st));  // bD = ga2_b
+    DLKA_TRY((deform_bwd_seq<T, 2>(a, o5, p->conv0_w, bA, bB, bO, gr->conv0_w, nullptr, scr, gx32, gw32, G.dcn5, st)));  // bB = ga2_a, bO = go5
+    DLKA_TRY(conv_bwd_seq<T>(a, p->conv0_offset_w, bO, bD, gr->conv0_offset_w, gr->conv0_offset_b, scr, gw32, nullptr, G.off5, st));  // bD = ga2_b
     DLKA_TRY(launch_add_fwd<T>(bB, bD, bB, G.E, st));
     DLKA_TRY(launch_add_fwd<T>(bC, bB, bC, G.E, st));                                                                       // bC = ga
     DLKA_TRY(launch_gelu_bwd<T>(h, bC, bA, G.E, st));                                                                       // bA = gh
-    DLKA_TRY(conv_bwd_all<T>(x, (const T *)p->proj_1_w, bA, bB, gr->proj_1_w, gr->proj_1_b, scr, gw32, G.pw, dtype, st));   // bB = gx1
+    DLKA_TRY(conv_bwd_seq<T>(x, p->proj_1_w, bA, bB, gr->proj_1_w, gr->proj_1_b, scr, gw32, nullptr, G.pw, st));   // bB = gx1
     DLKA_TRY(launch_add_fwd<T>(bB, gy, gx, G.E, st));
     return DLKA_OK;
+}
+
+#define DLKA_DISPATCH(dtype, CALL_F32, CALL_BF16) \
+    ((dtype) == DLKA_F32 ? (CALL_F32) : (dtype) == DLKA_BF16 ? (CALL_BF16) : DLKA_ERR_DTYPE)
+
+// ---- deformable conv, 3-D (NOFF = 3) and 2-D (NOFF = 2: torchvision semantics on a D = 1 geometry) ------------------------------------------
+int check_2d(const dlka_conv_geom *c)
+{
+    if (!c) return DLKA_ERR_NULL;
+    if (c->D != 1 || c->kd != 1 || c->sd != 1 || c->dd != 1 || c->pd != 0) return DLKA_ERR_SHAPE;
+    return DLKA_OK;
+}
+
+// the geometry step of every deformable entry: the 2-D ones first require a flat geometry
+template <int NOFF>
+int deform_geom(const dlka_conv_geom *c, Geom &g)
+{
+    if (NOFF == 2) DLKA_TRY(check_2d(c));
+    return make_geom(c, true, g);
+}
+
+template <int NOFF>
+size_t deform_workspace(const dlka_conv_geom *c, int dtype, bool backward)
+{
+    Geom g;
+    if (deform_geom<NOFF>(c, g)) return 0;
+    return backward ? deform_bwd_ws(g, dtype) : deform_fwd_ws(g);
+}
+
+// (bias: required by the 3-D entry, optional in the 2-D one — checked there)
+template <int NOFF>
+int deform_forward(const void *x, const void *offset, const void *weight, const void *bias, void *out, void *ws, size_t wsb, const dlka_conv_geom *c,
+                   int dtype, void *stream)
+{
+    if (!x || !offset || !weight || !out) return DLKA_ERR_NULL;
+    Geom g;
+    DLKA_TRY(deform_geom<NOFF>(c, g));
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == DLKA_F64) return launch_deform_fwd_f64<NOFF>((const double *)x, (const double *)offset, (const double *)weight, (const double *)bias, (double *)out, g, st);
+    return DLKA_DISPATCH(dtype, (deform_forward_t<float, NOFF>(x, offset, weight, bias, out, ws, wsb, g, st)),
+                         (deform_forward_t<bf16_t, NOFF>(x, offset, weight, bias, out, ws, wsb, g, st)));
+}
+
+template <int NOFF>
+int deform_backward(const void *x, const void *offset, const void *weight, const void *gout, void *gx, void *goff, void *gw, void *gb, void *ws, size_t wsb,
+                    const dlka_conv_geom *c, int dtype, void *stream)
+{
+    if (!x || !offset || !weight || !gout) return DLKA_ERR_NULL;
+    Geom g;
+    DLKA_TRY(deform_geom<NOFF>(c, g));
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == DLKA_F64)
+        return launch_deform_bwd_f64<NOFF>((const double *)x, (const double *)offset, (const double *)weight, (const double *)gout, (double *)gx, (double *)goff,
+                                           (double *)gw, (double *)gb, g, st);
+    return DLKA_DISPATCH(dtype, (deform_backward_t<float, NOFF>(x, offset, weight, gout, gx, goff, gw, gb, ws, wsb, g, st)),
+                         (deform_backward_t<bf16_t, NOFF>(x, offset, weight, gout, gx, goff, gw, gb, ws, wsb, g, st)));
+}
+
+template <int NOFF>
+int deform_sample_index(const void *offset, int32_t *idx, uint8_t *mask, const dlka_conv_geom *c, int dtype, int path, void *stream)
+{
+    if (!offset || !idx || !mask) return DLKA_ERR_NULL;
+    Geom g;
+    DLKA_TRY(deform_geom<NOFF>(c, g));
+    hipStream_t st = (hipStream_t)stream;
+    if (NOFF == 2)
+        return DLKA_DISPATCH(dtype, launch_sample_index2<float>((const float *)offset, idx, mask, g, path, st),
+                             launch_sample_index2<bf16_t>((const bf16_t *)offset, idx, mask, g, path, st));
+    return DLKA_DISPATCH(dtype, launch_sample_index<float>((const float *)offset, idx, mask, g, path, st),
+                         launch_sample_index<bf16_t>((const bf16_t *)offset, idx, mask, g, path, st));
 }
 
 }  // namespace
@@ -495,130 +521,52 @@ int dlka_conv_out_size(int in, int pad, int dil, int k, int stride)
     return num / stride + 1;
 }
 
-#define DLKA_DISPATCH(dtype, CALL_F32, CALL_BF16) \
-    ((dtype) == DLKA_F32 ? (CALL_F32) : (dtype) == DLKA_BF16 ? (CALL_BF16) : DLKA_ERR_DTYPE)
-
-// ---- 3-D deformable -------------------------------------------------------------------------------------------
-size_t dlka_deform_conv3d_forward_workspace(const dlka_conv_geom *c, int dtype)
-{
-    (void)dtype;
-    Geom g;
-    if (make_geom(c, true, g)) return 0;
-    return deform_fwd_ws(g);
-}
+// ---- deformable conv: 3-D and 2-D entries over the same templates -----------------------------------------------------------------------------
+size_t dlka_deform_conv3d_forward_workspace(const dlka_conv_geom *c, int dtype) { return deform_workspace<3>(c, dtype, false); }
+size_t dlka_deform_conv3d_backward_workspace(const dlka_conv_geom *c, int dtype) { return deform_workspace<3>(c, dtype, true); }
+size_t dlka_deform_conv2d_forward_workspace(const dlka_conv_geom *c, int dtype) { return deform_workspace<2>(c, dtype, false); }
+size_t dlka_deform_conv2d_backward_workspace(const dlka_conv_geom *c, int dtype) { return deform_workspace<2>(c, dtype, true); }
 
 int dlka_deform_conv3d_forward(const void *x, const void *offset, const void *weight, const void *bias, void *out,
                                void *workspace, size_t workspace_bytes, const dlka_conv_geom *c, int dtype, void *stream)
 {
-    if (!x || !offset || !weight || !bias || !out) return DLKA_ERR_NULL;
-    Geom g;
-    DLKA_TRY(make_geom(c, true, g));
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == DLKA_F64) return launch_deform_fwd_f64<3>((const double *)x, (const double *)offset, (const double *)weight, (const double *)bias, (double *)out, g, st);
-    return DLKA_DISPATCH(dtype, (deform_forward_t<float, 3>(x, offset, weight, bias, out, workspace, workspace_bytes, g, st)),
-                         (deform_forward_t<bf16_t, 3>(x, offset, weight, bias, out, workspace, workspace_bytes, g, st)));
+    if (!bias) return DLKA_ERR_NULL;
+    return deform_forward<3>(x, offset, weight, bias, out, workspace, workspace_bytes, c, dtype, stream);
 }
 
-size_t dlka_deform_conv3d_backward_workspace(const dlka_conv_geom *c, int dtype)
+int dlka_deform_conv2d_forward(const void *x, const void *offset, const void *weight, const void *bias, void *out,
+                               void *workspace, size_t workspace_bytes, const dlka_conv_geom *c, int dtype, void *stream)
 {
-    Geom g;
-    if (make_geom(c, true, g)) return 0;
-    return deform_bwd_ws(g, dtype);
+    return deform_forward<2>(x, offset, weight, bias, out, workspace, workspace_bytes, c, dtype, stream);
 }
 
 int dlka_deform_conv3d_backward(const void *x, const void *offset, const void *weight, const void *grad_out, void *grad_x,
                                 void *grad_offset, void *grad_weight, void *grad_bias, void *workspace, size_t workspace_bytes,
                                 const dlka_conv_geom *c, int dtype, void *stream)
 {
-    if (!x || !offset || !weight || !grad_out) return DLKA_ERR_NULL;
-    Geom g;
-    DLKA_TRY(make_geom(c, true, g));
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == DLKA_F64)
-        return launch_deform_bwd_f64<3>((const double *)x, (const double *)offset, (const double *)weight, (const double *)grad_out, (double *)grad_x, (double *)grad_offset,
-                                        (double *)grad_weight, (double *)grad_bias, g, st);
-    return DLKA_DISPATCH(dtype,
-                         (deform_backward_t<float, 3>(x, offset, weight, grad_out, grad_x, grad_offset, grad_weight, grad_bias, workspace, workspace_bytes, g, dtype, st)),
-                         (deform_backward_t<bf16_t, 3>(x, offset, weight, grad_out, grad_x, grad_offset, grad_weight, grad_bias, workspace, workspace_bytes, g, dtype, st)));
-}
-
-int dlka_deform_conv3d_sample_index_path(const void *offset, int32_t *idx, uint8_t *mask, const dlka_conv_geom *c, int dtype, int path, void *stream)
-{
-    if (!offset || !idx || !mask) return DLKA_ERR_NULL;
-    Geom g;
-    DLKA_TRY(make_geom(c, true, g));
-    hipStream_t st = (hipStream_t)stream;
-    return DLKA_DISPATCH(dtype, launch_sample_index<float>((const float *)offset, idx, mask, g, path, st),
-                         launch_sample_index<bf16_t>((const bf16_t *)offset, idx, mask, g, path, st));
-}
-
-int dlka_deform_conv3d_sample_index(const void *offset, int32_t *idx, uint8_t *mask, const dlka_conv_geom *c, int dtype, void *stream)
-{
-    return dlka_deform_conv3d_sample_index_path(offset, idx, mask, c, dtype, 0, stream);
-}
-
-// ---- 2-D deformable -------------------------------------------------------------------------------------------
-static int check_2d(const dlka_conv_geom *c)
-{
-    if (!c) return DLKA_ERR_NULL;
-    if (c->D != 1 || c->kd != 1 || c->sd != 1 || c->dd != 1 || c->pd != 0) return DLKA_ERR_SHAPE;
-    return DLKA_OK;
-}
-
-size_t dlka_deform_conv2d_forward_workspace(const dlka_conv_geom *c, int dtype)
-{
-    (void)dtype;
-    Geom g;
-    if (check_2d(c) || make_geom(c, true, g)) return 0;
-    return deform_fwd_ws(g);
-}
-
-int dlka_deform_conv2d_forward(const void *x, const void *offset, const void *weight, const void *bias, void *out,
-                               void *workspace, size_t workspace_bytes, const dlka_conv_geom *c, int dtype, void *stream)
-{
-    if (!x || !offset || !weight || !out) return DLKA_ERR_NULL;
-    DLKA_TRY(check_2d(c));
-    Geom g;
-    DLKA_TRY(make_geom(c, true, g));
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == DLKA_F64) return launch_deform_fwd_f64<2>((const double *)x, (const double *)offset, (const double *)weight, (const double *)bias, (double *)out, g, st);
-    return DLKA_DISPATCH(dtype, (deform_forward_t<float, 2>(x, offset, weight, bias, out, workspace, workspace_bytes, g, st)),
-                         (deform_forward_t<bf16_t, 2>(x, offset, weight, bias, out, workspace, workspace_bytes, g, st)));
-}
-
-size_t dlka_deform_conv2d_backward_workspace(const dlka_conv_geom *c, int dtype)
-{
-    Geom g;
-    if (check_2d(c) || make_geom(c, true, g)) return 0;
-    return deform_bwd_ws(g, dtype);
+    return deform_backward<3>(x, offset, weight, grad_out, grad_x, grad_offset, grad_weight, grad_bias, workspace, workspace_bytes, c, dtype, stream);
 }
 
 int dlka_deform_conv2d_backward(const void *x, const void *offset, const void *weight, const void *grad_out, void *grad_x,
                                 void *grad_offset, void *grad_weight, void *grad_bias, void *workspace, size_t workspace_bytes,
                                 const dlka_conv_geom *c, int dtype, void *stream)
 {
-    if (!x || !offset || !weight || !grad_out) return DLKA_ERR_NULL;
-    DLKA_TRY(check_2d(c));
-    Geom g;
-    DLKA_TRY(make_geom(c, true, g));
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == DLKA_F64)
-        return launch_deform_bwd_f64<2>((const double *)x, (const double *)offset, (const double *)weight, (const double *)grad_out, (double *)grad_x, (double *)grad_offset,
-                                        (double *)grad_weight, (double *)grad_bias, g, st);
-    return DLKA_DISPATCH(dtype,
-                         (deform_backward_t<float, 2>(x, offset, weight, grad_out, grad_x, grad_offset, grad_weight, grad_bias, workspace, workspace_bytes, g, dtype, st)),
-                         (deform_backward_t<bf16_t, 2>(x, offset, weight, grad_out, grad_x, grad_offset, grad_weight, grad_bias, workspace, workspace_bytes, g, dtype, st)));
+    return deform_backward<2>(x, offset, weight, grad_out, grad_x, grad_offset, grad_weight, grad_bias, workspace, workspace_bytes, c, dtype, stream);
+}
+
+int dlka_deform_conv3d_sample_index_path(const void *offset, int32_t *idx, uint8_t *mask, const dlka_conv_geom *c, int dtype, int path, void *stream)
+{
+    return deform_sample_index<3>(offset, idx, mask, c, dtype, path, stream);
+}
+
+int dlka_deform_conv3d_sample_index(const void *offset, int32_t *idx, uint8_t *mask, const dlka_conv_geom *c, int dtype, void *stream)
+{
+    return deform_sample_index<3>(offset, idx, mask, c, dtype, 0, stream);
 }
 
 int dlka_deform_conv2d_sample_index_path(const void *offset, int32_t *idx, uint8_t *mask, const dlka_conv_geom *c, int dtype, int path, void *stream)
 {
-    if (!offset || !idx || !mask) return DLKA_ERR_NULL;
-    DLKA_TRY(check_2d(c));
-    Geom g;
-    DLKA_TRY(make_geom(c, true, g));
-    hipStream_t st = (hipStream_t)stream;
-    return DLKA_DISPATCH(dtype, launch_sample_index2<float>((const float *)offset, idx, mask, g, path, st),
-                         launch_sample_index2<bf16_t>((const bf16_t *)offset, idx, mask, g, path, st));
+    return deform_sample_index<2>(offset, idx, mask, c, dtype, path, stream);
 }
 
 // ---- plain conv -----------------------------------------------------------------------------------------------
@@ -658,8 +606,8 @@ int dlka_conv3d_backward(const void *x, const void *weight, const void *grad_out
     hipStream_t st = (hipStream_t)stream;
     if (dtype == DLKA_F64)
         return launch_conv_bwd_f64((const double *)x, (const double *)weight, (const double *)grad_out, (double *)grad_x, (double *)grad_weight, (double *)grad_bias, g, st);
-    return DLKA_DISPATCH(dtype, conv_backward_t<float>(x, weight, grad_out, grad_x, grad_weight, grad_bias, workspace, workspace_bytes, g, dtype, st),
-                         conv_backward_t<bf16_t>(x, weight, grad_out, grad_x, grad_weight, grad_bias, workspace, workspace_bytes, g, dtype, st));
+    return DLKA_DISPATCH(dtype, conv_backward_t<float>(x, weight, grad_out, grad_x, grad_weight, grad_bias, workspace, workspace_bytes, g, st),
+                         conv_backward_t<bf16_t>(x, weight, grad_out, grad_x, grad_weight, grad_bias, workspace, workspace_bytes, g, st));
 }
 
 // ---- elementwise ----------------------------------------------------------------------------------------------
@@ -724,9 +672,7 @@ size_t dlka_lka3d_workspace_bytes(int B, int C, int D, int H, int W, int dtype)
 int dlka_lka3d_attention_forward(const void *x, const dlka_lka3d_params *p, void *y, void *saved, size_t saved_bytes,
                                  void *workspace, size_t workspace_bytes, int B, int C, int D, int H, int W, int dtype, void *stream)
 {
-    if (!x || !p || !y || !saved || !workspace) return DLKA_ERR_NULL;
-    const void *const *pp = (const void *const *)p;
-    for (size_t i = 0; i < sizeof(*p) / sizeof(void *); ++i) if (!pp[i]) return DLKA_ERR_NULL;
+    if (!x || !all_set(p) || !y || !saved || !workspace) return DLKA_ERR_NULL;
     DLKA_TRY(check_block(B, C, D, H, W));
     hipStream_t st = (hipStream_t)stream;
     return DLKA_DISPATCH(dtype, lka3d_forward_t<float>(x, p, y, saved, saved_bytes, workspace, workspace_bytes, B, C, D, H, W, st),
@@ -737,11 +683,7 @@ int dlka_lka3d_attention_backward(const void *x, const dlka_lka3d_params *p, con
                                   void *grad_x, const dlka_lka3d_grads *grads, void *workspace, size_t workspace_bytes,
                                   int B, int C, int D, int H, int W, int dtype, void *stream)
 {
-    if (!x || !p || !grad_y || !saved || !grad_x || !grads || !workspace) return DLKA_ERR_NULL;
-    const void *const *pp = (const void *const *)p;
-    for (size_t i = 0; i < sizeof(*p) / sizeof(void *); ++i) if (!pp[i]) return DLKA_ERR_NULL;
-    void *const *gp = (void *const *)grads;
-    for (size_t i = 0; i < sizeof(*grads) / sizeof(void *); ++i) if (!gp[i]) return DLKA_ERR_NULL;
+    if (!x || !all_set(p) || !grad_y || !saved || !grad_x || !all_set(grads) || !workspace) return DLKA_ERR_NULL;
     DLKA_TRY(check_block(B, C, D, H, W));
     hipStream_t st = (hipStream_t)stream;
     return DLKA_DISPATCH(dtype,
@@ -787,9 +729,7 @@ size_t dlka_lka2d_workspace_bytes(int B, int C, int H, int W, int dtype)
 int dlka_lka2d_attention_forward(const void *x, const dlka_lka2d_params *p, void *y, void *saved, size_t saved_bytes,
                                  void *workspace, size_t workspace_bytes, int B, int C, int H, int W, int dtype, void *stream)
 {
-    if (!x || !p || !y || !saved || !workspace) return DLKA_ERR_NULL;
-    const void *const *pp = (const void *const *)p;
-    for (size_t i = 0; i < sizeof(*p) / sizeof(void *); ++i) if (!pp[i]) return DLKA_ERR_NULL;
+    if (!x || !all_set(p) || !y || !saved || !workspace) return DLKA_ERR_NULL;
     DLKA_TRY(check_block(B, C, 1, H, W));
     hipStream_t st = (hipStream_t)stream;
     // channels-last fast path (MFMA offset nets, gather-layout depthwise deformable convs) wherever the width allows
@@ -819,11 +759,7 @@ int dlka_lka2d_attention_backward(const void *x, const dlka_lka2d_params *p, con
                                   void *grad_x, const dlka_lka2d_grads *grads, void *workspace, size_t workspace_bytes,
                                   int B, int C, int H, int W, int dtype, void *stream)
 {
-    if (!x || !p || !grad_y || !saved || !grad_x || !grads || !workspace) return DLKA_ERR_NULL;
-    const void *const *pp = (const void *const *)p;
-    for (size_t i = 0; i < sizeof(*p) / sizeof(void *); ++i) if (!pp[i]) return DLKA_ERR_NULL;
-    void *const *gp = (void *const *)grads;
-    for (size_t i = 0; i < sizeof(*grads) / sizeof(void *); ++i) if (!gp[i]) return DLKA_ERR_NULL;
+    if (!x || !all_set(p) || !grad_y || !saved || !grad_x || !all_set(grads) || !workspace) return DLKA_ERR_NULL;
     DLKA_TRY(check_block(B, C, 1, H, W));
     hipStream_t st = (hipStream_t)stream;
     if (lka2d_cl_supported(B, C, H, W, dtype) && !lka2d_general())

@@ -898,6 +898,43 @@ def check_lka3d_tokens_bf16(dev, B, C, dims, seed=0, offset_std=0.38, rtol=BF16_
     return errs
 
 
+def check_lka3d_volume_bf16(dev, B, C, dims, seed=0, offset_std=0.3, rtol=BF16_RTOL, report=False):
+    """The general NCDHW block (dlka_lka3d_attention_forward / _backward) with bf16 TENSORS THROUGHOUT — activations, offsets and parameters — the one
+    mode in which its backward pass accumulates grad_input / grad_weight in the fp32 areas of its workspace and casts them back.  y, grad_x and all 14
+    parameter gradients against the bf16-storage oracle (oracle.blocks.bf16_storage on every activation, the offset-determining chain included:
+    chain_store) on the same bf16-rounded x, grad_y and parameters, fed the kernels' own offset VALUES (read from `saved`): bf16 offsets differ from the
+    oracle's by an ulp here and there, which moves samples into other cells — the same-cells protocol of check_lka3d_tokens takes that out.
+    Bar: BF16_RTOL of max |reference| for every quantity.  The oracle models the forward pass's roundings; what it leaves out is the backward pass's own
+    (at most ten bf16 stores between grad_y and any output, half an ulp = 2^-9 relative each: below 10 * 2^-9 = 2e-2 even if they all pointed one way)."""
+    import deformablelka_amd as dk
+    from deformablelka_amd import ops
+    from oracle import blocks
+    torch.manual_seed(seed)
+    m = dk.LKA_Attention3d_deform(C)
+    blocks.randomize_offsets_(m, std=offset_std)
+    P0 = {k: v.detach().bfloat16() for k, v in m.state_dict().items()}
+    x, gy = torch.randn(B, C, *dims).bfloat16(), torch.randn(B, C, *dims).bfloat16()
+    params = [P0[k].to(dev) for k in STACK_PARAM_NAMES]
+    y, saved = ops.lka3d_attention_forward(x.to(dev), params)
+    gx, grads = ops.lka3d_attention_backward(x.to(dev), params, gy.to(dev), saved)
+    assert y.dtype == gx.dtype == torch.bfloat16 and all(g.dtype == torch.bfloat16 for g in grads)
+    # `saved` (csrc/dlka_capi.hip carve_lka3d_saved): h, a, t1, t, off, ... — each area a multiple of 256 bytes
+    E, n_off = x.numel(), B * 81 * x[0, 0].numel()
+    at = 4 * ((E * 2 + 255) // 256 * 256)
+    off_hip = saved[at:at + n_off * 2].view(torch.bfloat16).view(B, 81, *dims).float().cpu()
+    P = {k: v.float().requires_grad_(True) for k, v in P0.items()}
+    xr = x.float().requires_grad_(True)
+    yr = blocks.lka3d_attention_volume(xr, P, store=blocks.bf16_storage, chain_store=blocks.bf16_storage, offsets_override=off_hip)
+    yr.backward(gy.float())
+    errs = {"y": rel_err(y, yr.detach()), "gx": rel_err(gx, xr.grad)}
+    errs.update({k: rel_err(g, P[k].grad) for k, g in zip(STACK_PARAM_NAMES, grads)})
+    if report or os.environ.get("DLKA_PARITY_VERBOSE"):
+        print(f"[bf16 volume C={C} dims={dims}] vs bf16-storage oracle, same cells: " + " ".join(f"{'.'.join(k.split('.')[-2:])}={v:.1e}" for k, v in errs.items()))
+    for k, v in errs.items():
+        assert v <= rtol, f"bf16 volume {k}: rel err vs bf16-storage oracle {v:.3e} > {rtol}"
+    return errs
+
+
 # ---- the wrapper block (TransformerBlock_3D_single_deform_LKA) and its pieces ------------------------------------------------
 def offset_view(t, elems=1):
     """A contiguous copy of ``t`` that starts ``elems`` elements into a fresh allocation: same values, a data pointer that is NOT 16-byte aligned.  ops.py only calls

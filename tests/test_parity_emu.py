@@ -327,6 +327,11 @@ def test_lka3d_block_volume_entry_point(B, C, dims):
     parity.check_lka3d_tokens("cpu", B, C, dims, volume=True)
 
 
+def test_lka3d_block_volume_entry_point_bf16():
+    """The same entry point on bf16 tensors (the fp32 accumulators of its backward workspace) vs the bf16-storage oracle on the same cells at 2e-2."""
+    parity.check_lka3d_volume_bf16("cpu", 1, 8, (3, 4, 5), report=True)
+
+
 def test_lka2d_attention_general_path_contract_tolerances():
     """A width outside the channels-last menu (C % 32 != 0): the general NCHW kernels, offsets read back through dlka_lka2d_saved_offsets."""
     parity.check_lka2d_attention("cpu", 1, 12, 6, 7, report=True)

@@ -112,6 +112,11 @@ def test_lka3d_block_vs_oracle(C, dims):
     parity.check_lka3d_tokens(DEV, 2, C, dims, volume=True, report_offsets=True)
 
 
+def test_lka3d_block_bf16_vs_bf16_storage_oracle():
+    """The NCDHW entry point on bf16 tensors (the fp32 accumulators of its backward workspace) vs the bf16-storage oracle on the same cells at 2e-2."""
+    parity.check_lka3d_volume_bf16(DEV, 1, 8, (3, 4, 5), report=True)
+
+
 def test_full_size_stage0_properties():
     """BASELINE.json full size (C=32, 32^3, B=2): size-independent properties instead of the (slow) oracle.
     (1) zero offsets == plain conv3d computed by our own conv kernel and by the deformable kernel;
