@@ -5,6 +5,7 @@ from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 from . import ops
+from .ops._call import _pair
 
 
 class _Conv3dFn(Function):
@@ -30,9 +31,9 @@ def conv3d(x, weight, bias=None, stride=1, padding=0, dilation=1, groups=1):
 
 def conv2d(x, weight, bias=None, stride=1, padding=0, dilation=1, groups=1):
     """2-D conv through the same kernels (D = kd = 1)."""
-    s = (1,) + tuple(ops._pair(stride))
-    p = (0,) + tuple(ops._pair(padding))
-    d = (1,) + tuple(ops._pair(dilation))
+    s = (1,) + tuple(_pair(stride))
+    p = (0,) + tuple(_pair(padding))
+    d = (1,) + tuple(_pair(dilation))
     y = _Conv3dFn.apply(x.unsqueeze(2), weight.unsqueeze(2), bias, s, p, d, groups)
     return y.squeeze(2)
 

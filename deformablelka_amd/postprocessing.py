@@ -21,6 +21,7 @@ import torch
 
 from . import _lib as L
 from . import ops
+from .ops._call import _SD_DTYPES
 from ._containers import load
 
 __all__ = ["label", "component_sizes", "remove_all_but_the_largest_connected_component"]
@@ -31,7 +32,7 @@ _MAX_COUNT = 2 ** 31 - 1     # a map has fewer than 2^31 cells
 def _as_classes(t):
     """The map in a dtype the kernels read.  Rule of this module: a floating value that is no integer is no class and becomes 0, background
     (metrics maps it to -1, resampling raises): keep the three apart."""
-    if t.dtype in ops._SD_DTYPES:
+    if t.dtype in _SD_DTYPES:
         return t
     if t.dtype == torch.int8:
         return t.to(torch.int16)
@@ -42,7 +43,7 @@ def _as_classes(t):
 
 def _as_object(t):
     """scipy.ndimage.label's input: nonzero cells."""
-    if t.dtype in ops._SD_DTYPES:
+    if t.dtype in _SD_DTYPES:
         return t
     if t.dtype == torch.int8 or t.is_floating_point():
         return (t != 0).to(torch.uint8)

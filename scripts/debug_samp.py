@@ -4,6 +4,7 @@ import os, sys, torch
 from ctypes import byref
 sys.path.insert(0, ".")
 from deformablelka_amd import _lib as L, ops
+from deformablelka_amd.ops._call import ptr_struct
 import deformablelka_amd as dk
 
 emu_mode = "--emu" in sys.argv
@@ -63,7 +64,7 @@ for (B, C, dims) in cases:
         wb = lib.dlka_lka3d_tokens_workspace_bytes(B, C, H, W, D, dt)
         ws = torch.full((wb + (1 << 20),), 0xAB, dtype=torch.uint8, device=dev)
         gx = torch.empty_like(x); grads = [torch.empty_like(t) for t in params]
-        ps = ops._ptr_struct(L.Lka3dPtrs, L.LKA3D_FIELDS, params); gs = ops._ptr_struct(L.Lka3dPtrs, L.LKA3D_FIELDS, grads)
+        ps = ptr_struct(L.Lka3dPtrs, L.LKA3D_FIELDS, params); gs = ptr_struct(L.Lka3dPtrs, L.LKA3D_FIELDS, grads)
         rc = lib.dlka_lka3d_attention_tokens_backward(L.ptr(x), byref(ps), L.ptr(gy), L.ptr(saved), saved.numel(), L.ptr(gx), byref(gs), L.ptr(ws),
                                                       wb + (1 << 20), B, C, H, W, D, dt, L.stream_ptr(x))
         assert rc == 0, rc

@@ -2,6 +2,7 @@ import os, torch, ctypes
 from ctypes import byref
 os.environ["DLKA_WGRAD_GATHER"] = "1"
 from deformablelka_amd import _lib as L, ops
+from deformablelka_amd.ops._call import ptr_struct
 from tests import emu
 import sys
 if "--emu" in sys.argv:
@@ -21,7 +22,7 @@ for (B, C, dims) in [(1, 32, (4, 4, 4)), (2, 32, (8, 8, 8)), (1, 64, (3, 4, 5)),
     wb = lib.dlka_lka3d_tokens_workspace_bytes(B, C, H, W, D, dt)
     ws = torch.full((wb + (1 << 20),), 0xAB, dtype=torch.uint8, device=dev)
     gx = torch.empty_like(x); grads = [torch.empty_like(t) for t in params]
-    ps = ops._ptr_struct(L.Lka3dPtrs, L.LKA3D_FIELDS, params); gs = ops._ptr_struct(L.Lka3dPtrs, L.LKA3D_FIELDS, grads)
+    ps = ptr_struct(L.Lka3dPtrs, L.LKA3D_FIELDS, params); gs = ptr_struct(L.Lka3dPtrs, L.LKA3D_FIELDS, grads)
     rc = lib.dlka_lka3d_attention_tokens_backward(L.ptr(x), byref(ps), L.ptr(gy), L.ptr(saved), saved.numel(), L.ptr(gx), byref(gs), L.ptr(ws), wb + (1 << 20), B, C, H, W, D, dt, L.stream_ptr(x))
     assert rc == 0, rc
     if dev != "cpu": torch.cuda.synchronize()
