@@ -233,7 +233,6 @@ SIGNATURES = {
     "dlka_conv_brick_launch_count": (ctypes.c_long, []),
     "dlka_dwpair_launch_count": (ctypes.c_long, []),
     "dlka_pw_chain_launch_count": (ctypes.c_long, []),
-    "dlka_dwconv_2p_launch_count": (ctypes.c_long, []),
     "dlka_conv_kw_launch_count": (ctypes.c_long, []),
     "dlka_conv_kw_applies": (c_int, [c_int] * 8),
     "dlka_lka3d_tokens_supported_v": (c_int, [c_int] * 7),

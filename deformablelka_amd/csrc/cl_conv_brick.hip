@@ -117,9 +117,6 @@ __global__ __launch_bounds__(64 * WAVES) void cl_conv_brick_kernel(IgemmArgs p, 
     }
     const unsigned plane_bytes = (unsigned)p.N * 4u;
 
-#ifndef DLKA_BRICK_ABL   // TIMING-ONLY ablations (wrong results): 1 no fill, 2 no tap loop
-#define DLKA_BRICK_ABL 0
-#endif
     // gridDim.y > 1: the plane chunks are split over blockIdx.y (volumes too small to fill the chip with one workgroup per tile); the partial sums meet in
     // fp32 atomics on a ZEROED `out` (the caller's business, as for the tap-split kernels) and `aux` enters once
     const int cpw = (nchunk + (int)gridDim.y - 1) / (int)gridDim.y, ck_lo = (int)blockIdx.y * cpw, ck_hi = min(nchunk, ck_lo + cpw);
@@ -128,7 +125,7 @@ __global__ __launch_bounds__(64 * WAVES) void cl_conv_brick_kernel(IgemmArgs p, 
         for (int s = 0; s < DEPTH - 1; ++s) load_b(s, ck, bring[s]);
         // ---- fill (split into the two bf16 terms on the way) ----
 #pragma unroll
-        for (int j = 0; j < ((DLKA_BRICK_ABL & 1) ? 0 : MAXI); ++j) {
+        for (int j = 0; j < MAXI; ++j) {
             if (fdst[j] == DLKA_OOB) continue;
             float a[8];
             const unsigned s0 = fsrc[j] == DLKA_OOB ? DLKA_OOB : fsrc[j] + (unsigned)(ck * 32) * plane_bytes;
@@ -144,7 +141,7 @@ __global__ __launch_bounds__(64 * WAVES) void cl_conv_brick_kernel(IgemmArgs p, 
         // ---- 27 taps from the brick ----
         // (K = 27 is a multiple of DEPTH; unconditional ring loads — see cl_conv_brick3_kernel)
 #pragma unroll 1
-        for (int tap = 0; tap < ((DLKA_BRICK_ABL & 2) ? 0 : p.K); tap += DEPTH) {
+        for (int tap = 0; tap < p.K; tap += DEPTH) {
 #pragma unroll
             for (int s = 0; s < DEPTH; ++s) {
                 load_b(min(tap + s + DEPTH - 1, p.K - 1), ck, bring[(s + DEPTH - 1) % DEPTH]);

@@ -8,17 +8,13 @@
 // (A row-tiled variant — TH output rows spaced DIL apart per work-item, 5 FMA per load instead of 2.15 — was measured SLOWER
 // (72.9 vs 65.5 us at C=32 / 32^3, profiles/archive/r01o_dw_variants.txt): the kernel is bound by instruction issue with too few waves to
 // hide latency, not by the L1 request rate, and bigger per-thread tiles leave ~1 wave per SIMD.)
-#include <stdlib.h>
-
-#include <atomic>
-
 #include "cl_args.h"
 #include "dlka_kernels.h"
 
 namespace dlka {
 
 // T: activation storage (float, or bf16_t with fp32 arithmetic — DLKA_BF16 token path); weights / bias are fp32
-template <typename T, int KW, int DIL, int TW, int ABL = 0>   // ABL: ablation for profiling only (1 = no input loads, 2 = no FMAs)
+template <typename T, int KW, int DIL, int TW>
 __global__ __launch_bounds__(256) void cl_dwconv_kernel(DwArgs p)
 {
     constexpr int SEG = TW + (KW - 1) * DIL;
@@ -51,16 +47,9 @@ __global__ __launch_bounds__(256) void cl_dwconv_kernel(DwArgs p)
 #pragma unroll
             for (int e = 0; e < SEG; ++e) {
                 const int zw = w0 - p.pw + e;
-                seg[e] = (ABL == 1) ? (float)(e + zh) : ((zw >= 0 && zw < p.W) ? act_load1(rowp, (long)zw * p.C) : 0.f);
+                seg[e] = (zw >= 0 && zw < p.W) ? act_load1(rowp, (long)zw * p.C) : 0.f;
             }
             const float *wrow = p.wp + (long)((i * p.kh + j) * KW) * p.C + c;
-            if (ABL == 2) {
-#pragma unroll
-                for (int e = 0; e < SEG; ++e) acc[e % TW] += seg[e];
-#pragma unroll
-                for (int k = 0; k < KW; ++k) acc[k % TW] += wrow[(long)k * p.C];
-                continue;
-            }
 #pragma unroll
             for (int k = 0; k < KW; ++k) {
                 const float wv = wrow[(long)k * p.C];
@@ -289,272 +278,6 @@ __global__ __launch_bounds__(256, WL ? 3 : 1) void cl_dwconv_rowsN_kernel(DwArgs
   }
 }
 
-// ... and with TWO output planes per work-item as well (d0 and d0 + DIL, on top of the two rows h0 and h0 + DIL): the kernel above sits exactly on the L1 return
-// path (1.7 GB of wave loads per 7^3 launch at 32^3 = 42 us at 64 bytes / clock / CU, and it measures 42; the vector units are NOT the limit: independent fp32 FMAs
-// issue at ~110 - 125 lanes per clock and CU, scripts/ubench/fma_rate.hip), and output planes DIL apart share KD - 1 of their KD input planes exactly as the rows do:
-// KD + 1 planes of (KH + 1) segment rows feed 2 x 2 x KH x KW x TW products — 7.5 instead of 3.8 FMAs per loaded element at 7^3.
-// Tap weights in LDS as in the WL variant above, plus ONE all-zero tap plane: the first / last input plane of a pair serves only one of the two outputs, and the
-// other output multiplies it with zeros instead of branching (the FMAs are not what this kernel waits for).  C = 32 (one 32-channel group per workgroup).
-#ifndef DLKA_TD2_OCC
-#define DLKA_TD2_OCC 2   // (3: 168 registers with 14 - 19 spilled at 7^3; measured 60 against 51 us)
-#endif
-template <typename T, int KW, int DIL, int TW>
-__global__ __launch_bounds__(256, DLKA_TD2_OCC) void cl_dwconv_rows2d_kernel(DwArgs p)
-{
-    constexpr int KH = KW, KD = KW, TH = 2, TD = 2;
-    constexpr int SB = sizeof(T);
-    const T *inp = reinterpret_cast<const T *>(p.in), *gxp = reinterpret_cast<const T *>(p.gelu_x), *gap = reinterpret_cast<const T *>(p.gelu_add);
-    T *outp = reinterpret_cast<T *>(p.out);
-    constexpr int SEG = TW + (KW - 1) * DIL;
-    constexpr int NR = KH + TH - 1, NP = KD + TD - 1;        // input rows per plane, input planes per work-item
-    constexpr int cpb = 32, rpb = 8;
-    constexpr int PLANE = KH * KW * 32;                      // floats of one tap plane in LDS
-    __shared__ __attribute__((aligned(16))) float Wl[(KD + 1) * PLANE];   // [tap plane (KD = zeros)][tap row][tap col][channel of the workgroup]
-    {
-        const int n4 = KD * KH * KW * 8;   // 16-byte pieces: 8 per tap
-        for (int e = threadIdx.x; e < n4 + KH * KW * 8; e += 256) {
-            const int tap = e >> 3, q = e & 7;
-            f32x4 v = {0.f, 0.f, 0.f, 0.f};
-            if (e < n4) v = *reinterpret_cast<const f32x4 *>(p.wp + (long)tap * p.C + blockIdx.z * 32 + 4 * q);
-            reinterpret_cast<f32x4 *>(Wl)[e] = v;
-        }
-        __syncthreads();
-    }
-    const int c = blockIdx.z * cpb + threadIdx.x % cpb, cl = threadIdx.x % cpb;
-    const int bx = DLKA_XCD_BX(p.xcd_nx);
-    if (bx < 0) return;
-    const int run = bx * rpb + threadIdx.x / cpb;
-    const int runs_per_row = cdiv(p.W, TW);
-    const int hgroups = DIL * cdiv(p.H, TH * DIL), dgroups = DIL * cdiv(p.D, TD * DIL);   // h0 = r + TH*DIL*q, d0 = r' + TD*DIL*q'  (r, r' < DIL)
-    const long total = (long)p.B * dgroups * hgroups * runs_per_row;
-    if (run >= total || c >= p.C) return;
-    const int w0 = (run % runs_per_row) * TW;
-    const int gidx = wave_uniform(run / runs_per_row);
-    const int hg = gidx % hgroups, dg = (gidx / hgroups) % dgroups, b = gidx / (hgroups * dgroups);
-    const int h0 = (hg % DIL) + (hg / DIL) * TH * DIL, d0 = (dg % DIL) + (dg / DIL) * TD * DIL;
-    if (h0 >= p.H || d0 >= p.D) return;                      // scalar
-    const bool second = d0 + DIL < p.D;                      // the pair's second output plane exists
-
-    float acc[TD][TH][TW];
-    const float bv = p.bias ? p.bias[c] : 0.f;
-#pragma unroll
-    for (int od = 0; od < TD; ++od)
-#pragma unroll
-        for (int o = 0; o < TH; ++o)
-#pragma unroll
-            for (int t = 0; t < TW; ++t) acc[od][o][t] = bv;
-
-    const int cb = p.C * SB;
-    const unsigned rowbytes = (unsigned)(p.W * cb);
-    const int vbase = (w0 - p.pw) * cb + c * SB;
-#pragma unroll 1
-    for (int ip = 0; ip < NP; ++ip) {
-        const int zd = d0 - p.pd + ip * DIL;
-        if (zd < 0 || zd >= p.D) continue;                   // scalar
-        const float *wl0 = Wl + (ip < KD ? ip : KD) * PLANE + cl;                         // output plane d0: tap plane ip
-        const float *wl1 = Wl + ((ip >= 1 && second) ? ip - 1 : KD) * PLANE + cl;         // output plane d0 + DIL: tap plane ip - 1
-        const T *plane = inp + ((long)(b * p.D + zd) * p.H) * p.W * p.C;
-#pragma unroll
-        for (int r = 0; r < NR; ++r) {                       // input row h0 - ph + r*DIL: tap row r - o of output row o
-            const int zh = h0 - p.ph + r * DIL;
-            if (zh < 0 || zh >= p.H) continue;               // scalar
-            const BufRsrc rr = make_rsrc(plane + (long)zh * p.W * p.C, rowbytes);
-            float seg[SEG];
-#pragma unroll
-            for (int e = 0; e < SEG; ++e) seg[e] = act_buf_load1<T>(rr, (unsigned)(vbase + e * cb));
-#pragma unroll
-            for (int o = 0; o < TH; ++o) {
-                if (r - o < 0 || r - o >= KH) continue;      // compile time
-#pragma unroll
-                for (int k = 0; k < KW; ++k) {
-                    const float wk0 = wl0[((r - o) * KW + k) * 32], wk1 = wl1[((r - o) * KW + k) * 32];
-#pragma unroll
-                    for (int t = 0; t < TW; ++t) {
-                        acc[0][o][t] = fmaf(wk0, seg[t + k * DIL], acc[0][o][t]);
-                        acc[1][o][t] = fmaf(wk1, seg[t + k * DIL], acc[1][o][t]);
-                    }
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (int od = 0; od < TD; ++od) {
-        if (d0 + od * DIL >= p.D) break;                     // scalar
-#pragma unroll
-        for (int o = 0; o < TH; ++o) {
-            if (h0 + o * DIL >= p.H) break;                  // scalar
-            const long obase = (((long)(b * p.D + d0 + od * DIL) * p.H + h0 + o * DIL) * p.W + w0) * p.C + c;
-            if (p.gelu_x) {
-#pragma unroll
-                for (int t = 0; t < TW; ++t)
-                    if (w0 + t < p.W) act_store1(outp, obase + (long)t * p.C, (acc[od][o][t] + act_load1(gap, obase + (long)t * p.C)) * dgelu_f(act_load1(gxp, obase + (long)t * p.C)));
-            } else {
-#pragma unroll
-                for (int t = 0; t < TW; ++t)
-                    if (w0 + t < p.W) act_store1(outp, obase + (long)t * p.C, acc[od][o][t]);
-                if (sizeof(T) == 4 && p.out_lo) {   // uniform: bf16 copy (see cl_args.h: DwArgs::out_lo)
-                    bf16_t *lo = reinterpret_cast<bf16_t *>(p.out_lo);
-#pragma unroll
-                    for (int t = 0; t < TW; ++t)
-                        if (w0 + t < p.W) act_store1(lo, obase + (long)t * p.C, acc[od][o][t]);
-                }
-            }
-        }
-    }
-}
-
-// Third attempt at the family (round 6) — OPT-IN (DLKA_DW_2P=1 | 2), measured SLOWER than the row kernel: 7^3 dilation 3 49.5 against 43.4 us, 5^3 21.9 against
-// 20.2 at (32 channels, 32^3); 30.7 against 19.1 / 19.2 against 16.9 at (64, 16^3)  (profiles/r10_notes.md).  What it does:
-//  * input rows go through a RING of register segments; the loads of row r + RING - 1 are issued BEFORE row r computes.  Every load is unconditional (a row outside the
-//    volume gets a zero-sized descriptor: the hardware range check returns 0, no memory is touched) so that the compiler's vmcnt bookkeeping stays exact across the scalar
-//    branches that skip the FMAs of such rows; planes outside the volume are not visited at all.
-//  * the two output ROWS h0 and h0 + DIL of a work-item are the two halves of v_pk_fma_f32: acc.xy += {w[r][k], w[r - 1][k]} * seg.xx — the broadcast is an op_sel of the
-//    instruction and the weight pair is ONE ds_read2_b32 (LDS layout [tap plane][tap column][zero row, tap rows in DEscending order, zero row][channel]: the two tap rows
-//    are 32 floats apart in register order; the zero rows serve the first / last input row), read one row AHEAD of its use: a tap costs one LDS read, one address add and
-//    TW packed FMAs, no v_mov (the row kernels pack along W: 322 v_mov beside 392 v_pk_fma per tap plane at 7^3 dilation 3).  Per output the FMA chain is the row
-//    kernel's (plus zero products): bit-identical to it.
-//  * lane = channel, TW outputs along W, two rows x two planes (d0, d0 + DIL: input plane ip carries tap plane ip for the first, ip - 1 for the second).
-// Why it loses (ablations of this kernel at 7^3, us: as is 49.5 / no weight staging 44.1 / no input loads 38.6 / no FMAs 27.8; scripts/ubench/fma_rate.hip, VGPR operands):
-// ONE wave issues a vector instruction every ~5 - 6 clocks whatever it is (v_fma_f32 115 FMA lanes per ns and CU at one wave per SIMD, 203 at two, 241 at four; v_pk_fma_f32 with
-// three VGPR sources 194 / 253 / 278), so the FMA pipe only fills at three or four waves per SIMD — and a 2 x 2 x 8 register tile with its ring is 232 registers and
-// 1156 waves for the whole stage-0 volume: one or two waves per SIMD, the SIMDs that got two set the time.  4-wide work-items (twice the waves, 144 - 210 registers, 64 KB
-// of LDS per workgroup: still two per SIMD) measured 56 - 60 us.  The family's lever is occupancy at a small instruction count, not reuse per load: the row kernel
-// (three waves per SIMD, 40 % of its vector instructions are register moves and address adds) stays the default.
-template <typename T, int KW, int DIL, int TW, int RING>
-__global__ __launch_bounds__(256, 2) void cl_dwconv_rows2p_kernel(DwArgs p)
-{
-    constexpr int KH = KW, KD = KW, TH = 2;
-    constexpr int SB = sizeof(T);
-    constexpr int SEG = TW + (KW - 1) * DIL;
-    constexpr int NR = KH + TH - 1, NP = KD + 1;             // input rows per plane, input planes per work-item
-    constexpr int PF = RING - 1;                             // rows in flight ahead of the one that computes
-    static_assert(NR % RING == 0, "the ring slot of a row must not depend on the plane");
-    constexpr int KSTR = (KH + 2) * 32, PLANE = KW * KSTR;   // floats of one tap column (KH tap rows between two zero rows) / one tap plane in LDS
-    const T *inp = reinterpret_cast<const T *>(p.in), *gxp = reinterpret_cast<const T *>(p.gelu_x), *gap = reinterpret_cast<const T *>(p.gelu_add);
-    T *outp = reinterpret_cast<T *>(p.out);
-    __shared__ __attribute__((aligned(16))) float Wl[KD * PLANE];   // [tap plane][tap column k][zero row, tap rows KH - 1 .. 0, zero row][channel of the workgroup]
-    {
-#pragma unroll 4
-        for (int e = threadIdx.x; e < KD * PLANE / 4; e += 256) {
-            const int q = e & 7, slot = (e >> 3) % (KH + 2), k = ((e >> 3) / (KH + 2)) % KW, i = (e >> 3) / ((KH + 2) * KW);
-            f32x4 v = {0.f, 0.f, 0.f, 0.f};
-            if (slot >= 1 && slot <= KH) v = *reinterpret_cast<const f32x4 *>(p.wp + (long)((i * KH + KH - slot) * KW + k) * p.C + blockIdx.z * 32 + 4 * q);   // tap row KH - slot
-            reinterpret_cast<f32x4 *>(Wl)[e] = v;
-        }
-        __syncthreads();
-    }
-    const int cl = threadIdx.x % 32, c = blockIdx.z * 32 + cl;
-    const int bx = DLKA_XCD_BX(p.xcd_nx);
-    if (bx < 0) return;
-    const int run = bx * 8 + threadIdx.x / 32;
-    const int runs_per_row = cdiv(p.W, TW);
-    const int hgroups = DIL * cdiv(p.H, TH * DIL), dgroups = DIL * cdiv(p.D, 2 * DIL);   // h0 = r + 2*DIL*q, d0 = r' + 2*DIL*q'  (r, r' < DIL)
-    const long total = (long)p.B * dgroups * hgroups * runs_per_row;
-    if (run >= total) return;
-    const int w0 = (run % runs_per_row) * TW;
-    const int gidx = wave_uniform(run / runs_per_row);
-    const int hg = gidx % hgroups, dg = (gidx / hgroups) % dgroups, b = gidx / (hgroups * dgroups);
-    const int h0 = (hg % DIL) + (hg / DIL) * TH * DIL, d0 = (dg % DIL) + (dg / DIL) * 2 * DIL;
-    if (h0 >= p.H || d0 >= p.D) return;                      // scalar
-
-    f32x2 acc[2][TW];                                        // [output plane d0 + od*DIL][w]; .x: row h0, .y: row h0 + DIL
-    const float bv = p.bias ? p.bias[c] : 0.f;
-#pragma unroll
-    for (int od = 0; od < 2; ++od)
-#pragma unroll
-        for (int t = 0; t < TW; ++t) acc[od][t] = f32x2{bv, bv};
-
-    const int cb = p.C * SB;
-    const unsigned rowbytes = (unsigned)(p.W * cb);
-    const int vbase = (w0 - p.pw) * cb + c * SB;
-    // input planes zd = d0 - pd + ip*DIL inside the volume: ip in [ip_lo, ip_hi)
-    const int ip_lo = d0 < p.pd ? cdiv(p.pd - d0, DIL) : 0;
-    const int ip_hi = min(NP, cdiv(p.D - d0 + p.pd, DIL));
-    float seg[RING][SEG];
-    // descriptor of input row rr of plane ip (zero-sized outside the volume)
-    auto row_rsrc = [&](int ip, int rr) {
-        const int zd = d0 - p.pd + ip * DIL, zh = h0 - p.ph + rr * DIL;
-        const bool ok = ip < ip_hi && zh >= 0 && zh < p.H;
-        return make_rsrc(inp + ((long)(b * p.D + (ok ? zd : 0)) * p.H + (ok ? zh : 0)) * p.W * p.C, ok ? rowbytes : 0u);
-    };
-#pragma unroll
-    for (int r = 0; r < PF; ++r) {
-        const BufRsrc rr = row_rsrc(ip_lo, r);
-#pragma unroll
-        for (int e = 0; e < SEG; ++e) seg[r % RING][e] = act_buf_load1<T>(rr, (unsigned)(vbase + e * cb));
-    }
-    // tap weights of the row about to compute, read from LDS one row AHEAD (with one or two waves per SIMD nothing else hides the LDS latency: read at the point of
-    // use, every tap cost ~60 stall clocks beside its 32 clocks of FMAs).  wr[od][k] = {w[i][r][k], w[i][r - 1][k]}, i = ip - od clamped into the staged planes (an
-    // output plane that does not take this input plane skips its FMAs by a scalar branch; what was read for it is dropped).
-    f32x2 wr[2][KW];
-    auto load_w = [&](f32x2 (&w)[2][KW], int ip, int r) {
-#pragma unroll
-        for (int od = 0; od < 2; ++od) {
-            const float *wl = Wl + min(max(ip - od, 0), KD - 1) * PLANE + (KH - r) * 32 + cl;
-#pragma unroll
-            for (int k = 0; k < KW; ++k) w[od][k] = f32x2{wl[k * KSTR], wl[k * KSTR + 32]};   // tap rows r (slot KH - r) and r - 1 (the next slot): one ds_read2_b32, in register order
-        }
-    };
-    load_w(wr, ip_lo, 0);
-#pragma unroll 1
-    for (int ip = ip_lo; ip < ip_hi; ++ip) {
-#pragma unroll
-        for (int r = 0; r < NR; ++r) {                       // input row h0 - ph + r*DIL: tap row r of output row h0, r - 1 of h0 + DIL
-            {                                                // row r + PF (of this plane or the next one) into the slot row r - 1 left
-                const BufRsrc rr = row_rsrc(ip + (r + PF) / NR, (r + PF) % NR);
-#pragma unroll
-                for (int e = 0; e < SEG; ++e) seg[(r + PF) % RING][e] = act_buf_load1<T>(rr, (unsigned)(vbase + e * cb));
-            }
-            f32x2 wn[2][KW];
-            load_w(wn, ip + (r + 1) / NR, (r + 1) % NR);
-            const int zh = h0 - p.ph + r * DIL;
-            if (zh >= 0 && zh < p.H) {                       // scalar (else: the row's segment is zeros, nothing to add)
-#pragma unroll
-                for (int od = 0; od < 2; ++od) {
-                    const int i = ip - od;                   // tap plane of output plane d0 + od*DIL
-                    if (i < 0 || i >= KD) continue;          // scalar
-#pragma unroll
-                    for (int k = 0; k < KW; ++k) {
-#pragma unroll
-                        for (int t = 0; t < TW; ++t) {
-                            const float sv = seg[r % RING][t + k * DIL];
-                            acc[od][t] = pk_fma(wr[od][k], f32x2{sv, sv}, acc[od][t]);
-                        }
-                    }
-                }
-            }
-#pragma unroll
-            for (int od = 0; od < 2; ++od)
-#pragma unroll
-                for (int k = 0; k < KW; ++k) wr[od][k] = wn[od][k];
-        }
-    }
-#pragma unroll
-    for (int od = 0; od < 2; ++od) {
-        if (d0 + od * DIL >= p.D) break;                     // scalar
-#pragma unroll
-        for (int o = 0; o < TH; ++o) {
-            if (h0 + o * DIL >= p.H) break;                  // scalar
-            const long obase = (((long)(b * p.D + d0 + od * DIL) * p.H + h0 + o * DIL) * p.W + w0) * p.C + c;
-            if (p.gelu_x) {
-#pragma unroll
-                for (int t = 0; t < TW; ++t)
-                    if (w0 + t < p.W) act_store1(outp, obase + (long)t * p.C, (acc[od][t][o] + act_load1(gap, obase + (long)t * p.C)) * dgelu_f(act_load1(gxp, obase + (long)t * p.C)));
-            } else {
-#pragma unroll
-                for (int t = 0; t < TW; ++t)
-                    if (w0 + t < p.W) act_store1(outp, obase + (long)t * p.C, acc[od][t][o]);
-                if (sizeof(T) == 4 && p.out_lo) {   // uniform: bf16 copy (see cl_args.h: DwArgs::out_lo)
-                    bf16_t *lo = reinterpret_cast<bf16_t *>(p.out_lo);
-#pragma unroll
-                    for (int t = 0; t < TW; ++t)
-                        if (w0 + t < p.W) act_store1(lo, obase + (long)t * p.C, acc[od][t][o]);
-                }
-            }
-        }
-    }
-}
-
 // reference layout W[c][1][kd][kh][kw] -> Wp[tap][c]; flip = 1 reverses the taps (data gradient)
 __global__ void cl_dw_prep_weight_kernel(const float *__restrict__ w, float *__restrict__ wp, int C, int K, int flip)
 {
@@ -572,10 +295,6 @@ int launch_cl_dw_prep_weight(const float *w, float *wp, int C, int K, int flip, 
     return DLKA_OK;
 }
 
-static std::atomic<long> g_dw2p_launches{0};   // dlka_dwconv_2p_launch_count (include/dlka.h): diagnostics
-#ifndef DLKA_DW_2P_MIN_WAVES
-#define DLKA_DW_2P_MIN_WAVES 1000000000   // (no launch size at which it won: off unless DLKA_DW_2P asks for it)
-#endif
 // f(kw, dil_w as constants) for the shapes the kernels of this file are instantiated for: the two D-LKA shapes (5^3, 7^3 dil 3) in both storage
 // types, 3 / 1, 5 / 3 and 7 / 1 in fp32 only.  false: none of them
 template <bool F32, class F> static bool dispatch_kw_dil(int kw, int dil_w, F &&f)
@@ -616,24 +335,6 @@ static int launch_cl_dwconv_t(const DwArgs &a, int kw, int dil_w, hipStream_t st
         const bool cubic = a.kd == kw && a.kh == kw && a.dd == dil_w && a.dh == dil_w;
         constexpr int th = 2;   // output rows per work-item
         if (cubic && a.H >= th * dil_w && ((kw == 7 && dil_w == 3) || (kw == 5 && dil_w == 1))) {
-            // Software-pipelined kernel with two output rows on the halves of v_pk_fma_f32 and two output planes per work-item (cl_dwconv_rows2p_kernel): OPT-IN, measured
-            // slower (see its header).  DLKA_DW_2P (read per launch): unset / 0 = never, 1 = wherever its geometry fits (5^3: two rows ahead), 2 = the same with one row ahead.
-            {
-                const char *e3 = getenv("DLKA_DW_2P");
-                const int mode = e3 ? atoi(e3) : -1;
-                const bool ok2p = a.C % 32 == 0 && a.D >= 2 * dil_w && a.pd == (kw - 1) / 2 * dil_w && a.ph == a.pd && !a.out_blk && cdiv(a.W, TW) % 2 == 0;
-                const long runs3 = (long)a.B * dil_w * cdiv(a.D, 2 * dil_w) * dil_w * cdiv(a.H, th * dil_w) * cdiv(a.W, TW);
-                const long waves3 = runs3 / 2 * (a.C / 32);
-                if (ok2p && (mode > 0 || (mode < 0 && waves3 >= DLKA_DW_2P_MIN_WAVES))) {
-                    dim3 grid3((unsigned)cdivl(runs3, 8), 1, a.C / 32);
-                    swz(grid3);
-                    if (kw == 7) go(cl_dwconv_rows2p_kernel<T, 7, 3, TW, 2>, grid3);   // (a ring of 4 spills: 262 registers' worth)
-                    else dispatch_bool(mode == 2, [&](auto one) { go(cl_dwconv_rows2p_kernel<T, 5, 1, TW, DLKA_V(one) ? 2 : 3>, grid3); });
-                    DLKA_CHECK_LAUNCH();
-                    g_dw2p_launches.fetch_add(1, std::memory_order_relaxed);
-                    return DLKA_OK;
-                }
-            }
             const long runs2 = (long)a.B * a.D * dw_row_groups(a.H, th, dil_w).groups * cdiv(a.W, TW);
             dim3 grid2((unsigned)cdivl(runs2, rpb), 1, cdiv(a.C, cpb));
             swz(grid2);
@@ -653,22 +354,6 @@ static int launch_cl_dwconv_t(const DwArgs &a, int kw, int dil_w, hipStream_t st
                 dispatch_dlka_shape(kw, [&](auto KW, auto DIL) { go(cl_dwconv_rowsN_kernel<T, DLKA_V(KW), DLKA_V(DIL), 4, th>, grid4); });
                 DLKA_CHECK_LAUNCH();
                 return DLKA_OK;
-            }
-            // two output planes per work-item (cl_dwconv_rows2d_kernel): OPT-IN, DLKA_DW_TD2=1 (read per launch).  Measured SLOWER at (32, 32^3): 7^3 60 us (51 at two waves
-            // per SIMD, without its 14 spilled registers) against 45, 5^3 33 against 28; stage-0 stack 5.67 against 5.49 ms (profiles/r06_notes.md) — half the loads per
-            // output did not pay for half the workgroups, twice the LDS weight reads and the longer per-wave stream: these convs are not simply L1-bound.
-            {
-                const char *e2 = getenv("DLKA_DW_TD2");
-                const bool td2 = (e2 && e2[0] == '1') && cpb == 32 && a.C == 32 && a.D >= 4 * dil_w && a.pd == (kw - 1) / 2 * dil_w && !a.out_blk;
-                if (td2) {
-                    const long runs3 = (long)a.B * dil_w * cdiv(a.D, 2 * dil_w) * dil_w * cdiv(a.H, th * dil_w) * cdiv(a.W, TW);
-                    dim3 grid3((unsigned)cdivl(runs3, rpb), 1, 1);
-                    ax.xcd_nx = 0;   // (swz(grid2) above may have set it for the one-plane grid)
-                    swz(grid3);
-                    dispatch_dlka_shape(kw, [&](auto KW, auto DIL) { go(cl_dwconv_rows2d_kernel<T, DLKA_V(KW), DLKA_V(DIL), TW>, grid3); });
-                    DLKA_CHECK_LAUNCH();
-                    return DLKA_OK;
-                }
             }
             // the weights of 7^3 in LDS (measured: 54.3 -> 45.0 us at 32 channels / 32^3, profiles/r04_notes.md)
             if (kw == 7 && cpb == 32 && a.kd == 7) go(cl_dwconv_rowsN_kernel<T, 7, 3, TW, th, true>, grid2);
@@ -695,10 +380,6 @@ int launch_cl_dwconv(const DwArgs &a, int kw, int dil_w, hipStream_t st)
     if (e != DLKA_ERR_UNSUPPORTED) return e;
     return a.act_bf16 ? launch_cl_dwconv_t<bf16_t>(a, kw, dil_w, st) : launch_cl_dwconv_t<float>(a, kw, dil_w, st);
 }
-
-}   // namespace dlka
-extern "C" long dlka_dwconv_2p_launch_count(void) { return dlka::g_dw2p_launches.load(std::memory_order_relaxed); }
-namespace dlka {
 
 // ---------------------------------------------------------------------------------------------
 // depthwise weight gradient:  gW[c][tap] = sum_{b,d,h,w} G[b,d,h,w][c] * in[b, d+i*dd-pd, h+j*dh-ph, w+k*dw-pw][c]

@@ -591,10 +591,6 @@ __device__ __forceinline__ void wgrad_dense_body(const WgradArgs &p, const int b
         }
     };
 
-#ifndef DLKA_ABLG   // -DDLKA_ABLG=bits: TIMING-ONLY ablations of the split dense weight gradient (wrong results): 1 no split arithmetic, 2 one MFMA per
-#define DLKA_ABLG 0  // (co-tile, tap) and k-half instead of three, 4 no operand fetch in the loop
-#endif
-    constexpr int ABLG = (SPLIT && GMODE == 1 && COT == 3 && TPW == 3) ? DLKA_ABLG : 0;
     if (m_lo < m_hi) load_step(m_lo);
     for (int mbase = m_lo; mbase < m_hi; mbase += 32) {
         float ga[COT][16], bv[TPW][16];
@@ -613,7 +609,7 @@ __device__ __forceinline__ void wgrad_dense_body(const WgradArgs &p, const int b
 #pragma unroll
                 for (int s = 0; s < 16; ++s) bv[t][s] = bv_n[t][s];
         }
-        if (mbase + 32 < m_hi && !(ABLG & 4)) load_step(mbase + 32);   // in flight under the MFMAs below
+        if (mbase + 32 < m_hi) load_step(mbase + 32);   // in flight under the MFMAs below
         const bool gpk = GMODE == 1 && SPLIT && p.g_cpad;   // uniform: g arrives as pack_split2() words
         if (want_bias) {
 #pragma unroll
@@ -633,20 +629,17 @@ __device__ __forceinline__ void wgrad_dense_body(const WgradArgs &p, const int b
 #pragma unroll
                 for (int c = 0; c < COT; ++c) {
                     if (gpk) unpack_split2x8(ga[c] + 8 * mf, ahi[c], alo[c]);
-                    else if (ABLG & 1) { ahi[c] = bf16x8_from_words(ga[c] + 8 * mf); alo[c] = bf16x8_from_words(ga[c] + 8 * mf + 4); }
                     else split_bf16x8(ga[c] + 8 * mf, ahi[c], alo[c]);
                 }
 #pragma unroll
                 for (int t = 0; t < TPW; ++t) {
-                    if (ABLG & 1) { bhi[t] = bf16x8_from_words(bv[t] + 8 * mf); blo[t] = bf16x8_from_words(bv[t] + 8 * mf + 4); }
-                    else split_bf16x8(bv[t] + 8 * mf, bhi[t], blo[t]);
+                    split_bf16x8(bv[t] + 8 * mf, bhi[t], blo[t]);
                 }
 #pragma unroll
                 for (int c = 0; c < COT; ++c)
 #pragma unroll
                     for (int t = 0; t < TPW; ++t) {
                         acc[c][t] = mfma_32x32x16_bf16(alo[c], bhi[t], acc[c][t]);
-                        if (ABLG & 2) continue;
                         if (!B16) acc[c][t] = mfma_32x32x16_bf16(ahi[c], blo[t], acc[c][t]);   // a bf16 `in` has no low term
                         acc[c][t] = mfma_32x32x16_bf16(ahi[c], bhi[t], acc[c][t]);
                     }

@@ -212,12 +212,8 @@ __global__ __launch_bounds__(256, 2) void conv3_row_mfma_kernel(const float *__r
         request(0, lo, hi);
 #pragma unroll
         for (int step = 0; step < 36; ++step) {
-#ifndef DLKA_ABLR   // -DDLKA_ABLR=bits: TIMING-ONLY ablations (wrong results): 1 no operand loads in the loop, 2 no MFMAs in the loop
-#define DLKA_ABLR 0
-#endif
-            if (step + 1 < 36 && !(DLKA_ABLR & 1)) request(step + 1, nlo, nhi);
+            if (step + 1 < 36) request(step + 1, nlo, nhi);
             const int t0 = (step / 4) * 3, s4 = step & 3;
-            if (DLKA_ABLR & 2) { acc[0][0] += lo[0] + hi[3]; lo = nlo; hi = nhi; continue; }
             const float xv[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
             const float el = row_shr1(xv[7]), er = row_shl1(xv[0]);
 #pragma unroll
@@ -731,7 +727,7 @@ __global__ __launch_bounds__(256, 2) void conv3_bwd_weight_row_mfma_kernel(const
         hi = buf_load_f32x4(rg, off + 16u);
     };
     // The operand loads run PD (tap_d, tap_h) steps ahead of their MFMAs, across segments and rows (9 % PD == 0: the ring slot of a step is known at compile time).  Timing-only
-    // ablations of the one-step version (-DDLKA_ABLC): 361 us as built, 338 with the loads alone, 56 with the split + MFMAs alone — the kernel waits for its loads, two waves per
+    // ablations of the one-step version (since removed): 361 us as built, 338 with the loads alone, 56 with the split + MFMAs alone — the kernel waits for its loads, two waves per
     // SIMD with four load instructions each in flight are too few for the ~2 us a line takes to arrive under load (profiles/r10_notes.md).
 #ifndef DLKA_WGRAD_PD
 #define DLKA_WGRAD_PD 3
@@ -755,21 +751,15 @@ __global__ __launch_bounds__(256, 2) void conv3_bwd_weight_row_mfma_kernel(const
 #pragma unroll
         for (int step = 0; step < 9; ++step) {
             const XStep cx = ring[step % PD];
-#ifndef DLKA_ABLC   // -DDLKA_ABLC=bits: TIMING-ONLY ablations (wrong results): 1 no operand loads in the loop, 2 no split / MFMAs in the loop
-#define DLKA_ABLC 0
-#endif
-            if (!(DLKA_ABLC & 1)) {
-                if (step + PD < 9) request_x(r, seg, step + PD, ring[step % PD]);
-                else {
-                    if (step + PD == 9) request_g(rn, sn, qnl, qnh);
-                    request_x(rn, sn, step + PD - 9, ring[step % PD]);
-                }
+            if (step + PD < 9) request_x(r, seg, step + PD, ring[step % PD]);
+            else {
+                if (step + PD == 9) request_g(rn, sn, qnl, qnh);
+                request_x(rn, sn, step + PD - 9, ring[step % PD]);
             }
             const float c[8] = {cx.lo[0], cx.lo[1], cx.lo[2], cx.lo[3], cx.hi[0], cx.hi[1], cx.hi[2], cx.hi[3]};
             const int t0 = step * 3;
             // tap_w = 0: x[w - 1], 1: x[w], 2: x[w + 1] for the lane's voxel w = w0 + e
-            if (DLKA_ABLC & 2) { acc[t0][0] += c[0] + cx.lft + cx.rgt + c[7] + q[0]; }
-            else if (B16) {
+            if (B16) {
                 const float xm[10] = {cx.lft, c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[7], cx.rgt};   // x[w0 - 1 .. w0 + 8]
 #pragma unroll
                 for (int tw = 0; tw < 3; ++tw) {

@@ -8,10 +8,11 @@ fwd+bwd is a fixed sequence of C-ABI calls on one stream, so it can be captured 
 """
 from __future__ import annotations
 
+import ctypes
+import math
+import os
 from ctypes import byref
 from typing import List, Sequence, Tuple
-
-import os
 
 import torch
 
@@ -33,22 +34,17 @@ def _offset_std_for(C: int, offset_std_voxels: float = 1.0) -> float:
     (after proj_1, GELU and the two default-initialised depthwise convs) shrinks with C, so the gain is calibrated per stage width:
     measured on MI355X with gain 3/sqrt(fan_in) the predicted offsets had std 0.272 / 0.190 / 0.104 / 0.080 at C = 32 / 64 / 128 / 256
     (scripts/stack_stats.py); the table brings all four to ~1.0 and is frozen."""
-    import math
     calib = {32: 3.68, 64: 5.26, 128: 9.6, 256: 12.5}.get(C, 1.0)
     return offset_std_voxels * calib * 3.0 / math.sqrt(C * 27)
 
 
-def chain_order(stages: Sequence, order: str = "unet"):
-    """The chains (stage instances of up to CHAIN blocks) of a patch in EXECUTION order.
-
-    "unet" (default): the order D_LKA_Former's own forward pass visits them — the encoder's stage instances from the widest volume to the bottleneck, then the
+def chain_order(stages: Sequence):
+    """The chains (stage instances of up to CHAIN blocks) of a patch in EXECUTION order: the order D_LKA_Former's own forward pass visits them — the encoder's stage instances from the widest volume to the bottleneck, then the
     decoder's back up (model_components.py:33-39 the encoder's four stages, :127-131 the decoder's; network_architecture/synapse/d_lka_former_synapse.py chains them):
     of a stage's chains the first is the encoder's, the others the decoder's.  The backward pass runs it in reverse, i.e. it STARTS with the decoder's 32^3 blocks —
     whose weight gradients (the largest of the step) then trail on the side stream under the small stages' data chains, which leave most of the chip idle.
-    "stages": stage by stage as the table lists them (rounds 1 - 4; DLKA_STACK_ORDER=stages), small stages first in the backward pass."""
+    (Rounds 1 - 4 ran stage by stage as the table lists them, small stages first in the backward pass.)"""
     per_stage = [[(C, dims, min(CHAIN, n - c0)) for c0 in range(0, n, CHAIN)] for C, dims, n in stages]
-    if order == "stages":
-        return [c for cs in per_stage for c in cs]
     return [cs[0] for cs in per_stage if cs] + [c for cs in reversed(per_stage) for c in cs[1:]]
 
 
@@ -65,8 +61,7 @@ class DLKABlockStack:
         self.lib = L.get_lib()
         self.dt = L.DLKA_F32 if dtype == torch.float32 else L.DLKA_BF16
         gen = torch.Generator().manual_seed(seed)
-        self.order = os.environ.get("DLKA_STACK_ORDER", "unet")
-        chain_specs = chain_order(stages, self.order)
+        chain_specs = chain_order(stages)
         shapes_all = []
         for C, dims, n in chain_specs:
             for _ in range(n):
@@ -125,7 +120,6 @@ class DLKABlockStack:
     # (3D/dcn/modules/deform_conv.py:44-50).  conv_offset would be zero (deform_conv.py:86-88) which makes every
     # sample integer-aligned; for timing it is drawn so that predicted offsets have ~offset_std_voxels std.
     def _init_block(self, blk, gen, offset_std):
-        import math
         for idx in range(0, 14, 2):
             w, b = blk.params[idx], blk.params[idx + 1]
             fan_in = int(w[0].numel())
@@ -140,7 +134,6 @@ class DLKABlockStack:
         """The prepared (MFMA-operand-order) weight forms of ALL blocks are produced by ONE launch per step (``prepare()``), not by one launch
         inside every block's forward call: the job table is built here once — parameter and ``saved`` addresses never change — and lives on
         the device (include/dlka.h: dlka_lka3d_tokens_prepare_*)."""
-        import ctypes
         n = len(self.blocks)
         nbytes = self.lib.dlka_lka3d_tokens_prepare_plan_bytes(n)
         params = (L.Lka3dPtrs * n)(*[b.pstruct for b in self.blocks])
@@ -162,10 +155,8 @@ class DLKABlockStack:
         self._fin_host = self._fin_dev = None
         self._fin_sealed = False
         self._fin_recorded = set()
-        import os
-        if not enable or os.environ.get("DLKA_STACK_PER_BLOCK_FINALIZE"):   # (A/B switch: the per-block finalize launches)
+        if not enable:   # (defer_finalize=False: the per-block finalize launches)
             return
-        import ctypes
         n = len(self.blocks)
         for blk in self.blocks:
             H, W, D = blk.dims
@@ -180,36 +171,27 @@ class DLKABlockStack:
         finalisation at the end of the pass reads THEIR results: they run on a side stream behind an event, overlapping the next block's data chain
         (dlka_lka3d_attention_tokens_backward_phase_v).  Two workspaces alternate; the data chain of a block waits for the weight gradients that last
         used its workspace.  Under hipGraph capture the events become a fork / join in the graph.  Needs the deferred finalisation."""
-        import os
         if enable is None:   # default: on (measured 11.95 -> 11.47 ms per step under hipGraph replay); DLKA_STACK_WGRAD_OVERLAP=0 = one stream
             enable = os.environ.get("DLKA_STACK_WGRAD_OVERLAP", "1") != "0"
         self._overlap = bool(enable) and self._fin_host is not None
-        # blocks narrower than this run their weight gradients IN LINE on the calling stream (A/B knob: at the widest-volume stage the data chain fills
-        # the chip by itself, so the side stream's kernels mostly stretch it; profiles/r05_notes.md has the measurement behind the default)
-        self._overlap_min_c = int(os.environ.get("DLKA_STACK_WGRAD_OVERLAP_MIN_C", "0"))
         self._prep_pending, self._prep_split = None, 0
+        self._side = None
         if not self._overlap:
             return
-        # Workspaces of the backward pass, used round-robin: block n's data chain writes pool[n % K], its weight gradients read it on the side stream, and the
-        # data chain of block n + K waits for them.  K = 2 (rounds 2 - 4) ties the side stream to the data chain within one block; with the decoder's 32^3 blocks at
-        # the head of the backward pass (chain_order) a deeper pool lets their weight gradients trail under the small stages.  288 GB of HBM: 0.44 GB each.
-        # Measured (profiles/r08_notes.md, `r8e`): a deep ROUND-ROBIN pool is slower (K = 2 / 4 / 8 / 12: 10.50 / 10.71 / 10.86 / 11.03 ms per step) — the small
-        # stages' working sets then rotate through K x their size and fall out of the L2 / Infinity Cache.  So: two alternating workspaces as before, plus
-        # DLKA_STACK_TRAIL private ones for the FIRST blocks of the backward pass (the decoder's 32^3 chain), whose weight gradients may then trail freely.
-        self._trail = max(0, int(os.environ.get("DLKA_STACK_TRAIL", "0")))
-        self._pool_k = 2 + self._trail
-        self._ws_pool = [self.ws] + [torch.empty(self.ws_bytes, dtype=torch.uint8, device=self.device) for _ in range(self._pool_k - 1)]
-        self.ws2 = self._ws_pool[1]
+        # Two workspaces of the backward pass alternate: block n's data chain writes pool[n & 1], its weight gradients read it on the side stream, and the data
+        # chain of block n + 2 waits for them.  288 GB of HBM: 0.44 GB each.  Deeper pools were measured slower, round-robin (K = 2 / 4 / 8 / 12: 10.50 / 10.71 /
+        # 10.86 / 11.03 ms per step — the small stages' working sets then rotate through K x their size and fall out of the L2 / Infinity Cache) and as private
+        # workspaces for the first blocks of the pass (profiles/r08_notes.md).
+        self.ws2 = torch.empty(self.ws_bytes, dtype=torch.uint8, device=self.device)
+        self._ws_pool = [self.ws, self.ws2]
         if self.device.type == "cuda":
             self._side = torch.cuda.Stream(device=self.device)
-            self._ev_data = [torch.cuda.Event() for _ in range(self._pool_k)]
-            self._ev_wg = [torch.cuda.Event() for _ in range(self._pool_k)]
+            self._ev_data = [torch.cuda.Event(), torch.cuda.Event()]
+            self._ev_wg = [torch.cuda.Event(), torch.cuda.Event()]
             self._ev_prep, self._ev_prep2 = torch.cuda.Event(), torch.cuda.Event()
             self._ev_fin = torch.cuda.Event()
             c0 = self.blocks[0].C
             self._prep_split = next((i for i, b in enumerate(self.blocks) if b.C != c0), len(self.blocks))   # the leading blocks of the first width
-        else:
-            self._side = None
 
     def prepare(self):
         """Re-lay the weights of all blocks (after every parameter update): ONE launch, complete in stream order on the calling stream — safe to follow
@@ -222,7 +204,7 @@ class DLKABlockStack:
         it (and ``backward`` would, were it ever entered with the join still pending), so the fork never outlives the call that made it."""
         n, st = len(self.blocks), self._stream()
         self._join_prepare()
-        k = self._prep_split if split and getattr(self, "_overlap", False) and getattr(self, "_side", None) is not None else 0
+        k = self._prep_split if split and self._overlap and self._side is not None else 0
         if 0 < k < n:
             cur = torch.cuda.current_stream(self.device)
             L.check(self.lib.dlka_lka3d_tokens_prepare_run_range(L.ptr(self._plan_dev), L.ptr(self._plan_host), n, 0, k, st), "lka3d_tokens_prepare_run_range")
@@ -264,16 +246,9 @@ class DLKABlockStack:
 
     def backward(self, lo: int = 0, hi: int = None, on_block=None):
         """Backward pass of blocks[lo:hi] in reverse order (default: all)."""
-        import ctypes
         st = self._stream()
         self._join_prepare()
         idx = list(range(len(self.blocks)))[lo:hi]
-        defer = self._fin_host is not None
-        plan_ptr = ctypes.c_void_p(self._fin_host.data_ptr()) if defer else None
-        overlap = defer and getattr(self, "_overlap", False)
-        side = self._side if overlap else None
-        K = self._pool_k if overlap else 2
-        used = [False] * K   # workspace k has weight gradients in flight on the side stream
         # Sealed plan + side stream: the folds of a block's partial sums follow its weight gradients ON THE SIDE STREAM, a few blocks per launch, instead
         # of one launch for the whole pass after the join (330 us exposed at the end of every step, profiles/r04s): that stream has the slack (the weight
         # gradients are ~40 % of a block's backward work) and only the last group's fold is left behind the last block.  DLKA_STACK_FINALIZE_GROUP=0:
@@ -281,90 +256,109 @@ class DLKABlockStack:
         # (faster folds and weight gradients: the side stream has more slack) one block per launch is ahead, 10.07 against 10.11 - 10.14 fp32 and 9.32 against 9.36 bf16
         # (profiles/r09h_ab_fin_*.json, each configuration twice in one process).
         fin_group = int(os.environ.get("DLKA_STACK_FINALIZE_GROUP", "1"))
-        side_fin = bool(overlap and side is not None and self._fin_sealed and fin_group > 0)
-        pending = []   # blocks (descending) whose weight gradients are issued and whose folds are not
-
-        def fold_pending():
-            rc = self.lib.dlka_wgrad_finalize_run(L.ptr(self._fin_dev), plan_ptr, pending[-1], pending[0] + 1, side.cuda_stream)
-            L.check(rc, "wgrad_finalize_run (side stream)")
-            pending.clear()
-
+        side = self._side if self._overlap else None   # (bench.py's launch trace clears _overlap for one-stream passes of a stack that has a side stream)
+        fold_every = fin_group if side is not None and self._fin_sealed and fin_group > 0 else 0   # blocks per fold on the side stream; 0: one fold after the join
+        used = [False, False]   # workspace k has weight gradients in flight on the side stream
+        pending = []            # blocks (descending) whose weight gradients are issued and whose folds are not
         for n, i in enumerate(reversed(idx)):
-            blk = self.blocks[i]
             if on_block is not None:
                 on_block(i)
-            H, W, D = blk.dims
-            if overlap:
-                k = (2 + n) if n < K - 2 else ((n - (K - 2)) & 1)   # the first K - 2 blocks of the pass: a workspace of their own; then two alternate
-                ws = self._ws_pool[k]
-                record = not self._fin_sealed and i not in self._fin_recorded
-                args = (L.ptr(blk.x), byref(blk.pstruct), L.ptr(blk.gy), L.ptr(blk.saved), blk.saved_bytes, L.ptr(blk.gx), byref(blk.gstruct), L.ptr(ws),
-                        self.ws_bytes, L.ptr(blk.partials), blk.partials_bytes)
-                dims7 = (self.B, blk.C, H, W, D, self.dt, 0)
-                if side is not None and used[k]:
-                    torch.cuda.current_stream(self.device).wait_event(self._ev_wg[k])   # the weight gradients that last read this workspace are done
-                L.check(self.lib.dlka_lka3d_attention_tokens_backward_phase_v(*args, None, i, 1, *dims7, st), "backward phase 1")
-                if side is not None and blk.C < self._overlap_min_c:
-                    # this block's weight gradients in line; the side stream (which folds the partial sums) continues behind them
-                    L.check(self.lib.dlka_lka3d_attention_tokens_backward_phase_v(*args, plan_ptr if record else None, i, 2, *dims7, st), "backward phase 2")
-                    used[k] = False   # (whatever read this workspace on the side stream was waited for in front of phase 1)
-                    if side_fin:
-                        self._ev_data[k].record(torch.cuda.current_stream(self.device))
-                        side.wait_event(self._ev_data[k])
-                        pending.append(i)
-                        if len(pending) >= fin_group:
-                            fold_pending()
-                elif side is not None:
-                    self._ev_data[k].record(torch.cuda.current_stream(self.device))
-                    side.wait_event(self._ev_data[k])
-                    L.check(self.lib.dlka_lka3d_attention_tokens_backward_phase_v(*args, plan_ptr if record else None, i, 2, *dims7, side.cuda_stream),
-                            "backward phase 2")
-                    self._ev_wg[k].record(side)
-                    used[k] = True
-                    if side_fin:
-                        pending.append(i)
-                        if len(pending) >= fin_group:
-                            fold_pending()
-                else:
-                    L.check(self.lib.dlka_lka3d_attention_tokens_backward_phase_v(*args, plan_ptr if record else None, i, 2, *dims7, st), "backward phase 2")
-                if record:
-                    self._fin_recorded.add(i)
-                if not self._fin_sealed:
-                    if side is not None:   # (the per-slot finalize of the recording pass reads the partial sums: behind the weight gradients)
-                        torch.cuda.current_stream(self.device).wait_event(self._ev_wg[k])
-                        used[k] = False
-                    L.check(self.lib.dlka_wgrad_finalize_run_slot(plan_ptr, i, st), "wgrad_finalize_run_slot")
-            elif defer:
-                record = not self._fin_sealed and i not in self._fin_recorded
-                rc = self.lib.dlka_lka3d_attention_tokens_backward_deferred_v(
-                    L.ptr(blk.x), byref(blk.pstruct), L.ptr(blk.gy), L.ptr(blk.saved), blk.saved_bytes, L.ptr(blk.gx), byref(blk.gstruct), L.ptr(self.ws),
-                    self.ws_bytes, L.ptr(blk.partials), blk.partials_bytes, plan_ptr if record else None, i, self.B, blk.C, H, W, D, self.dt, 0, st)
-                L.check(rc, "lka3d_attention_tokens_backward_deferred_v")
-                if record:
-                    self._fin_recorded.add(i)
-                if not self._fin_sealed:   # the table is still being recorded: this block's folds as the ordinary per-block launch
-                    L.check(self.lib.dlka_wgrad_finalize_run_slot(plan_ptr, i, st), "wgrad_finalize_run_slot")
+            if self._overlap:
+                self._issue_two_phase(i, n & 1, st, side, used, pending, fold_every)
+            elif self._fin_host is not None:
+                self._issue_deferred(i, st)
             else:
-                rc = self.lib.dlka_lka3d_attention_tokens_backward(L.ptr(blk.x), byref(blk.pstruct), L.ptr(blk.gy), L.ptr(blk.saved),
-                                                            blk.saved_bytes, L.ptr(blk.gx), byref(blk.gstruct), L.ptr(self.ws),
-                                                            self.ws_bytes, self.B, blk.C, H, W, D, self.dt, st)
-                L.check(rc, "lka3d_attention_tokens_backward")
+                self._issue_plain(i, st)
+        self._finish_pass(idx, st, side, used, pending, fold_every)
+
+    def _plan_ptr(self):
+        return ctypes.c_void_p(self._fin_host.data_ptr())
+
+    def _recording(self, i: int) -> bool:
+        """Block i's folds still have to enter the finalize plan (its first backward pass)."""
+        return not self._fin_sealed and i not in self._fin_recorded
+
+    def _fold_pending(self, pending, side):
+        rc = self.lib.dlka_wgrad_finalize_run(L.ptr(self._fin_dev), self._plan_ptr(), pending[-1], pending[0] + 1, side.cuda_stream)
+        L.check(rc, "wgrad_finalize_run (side stream)")
+        pending.clear()
+
+    def _issue_two_phase(self, i, k, st, side, used, pending, fold_every):
+        """Block i on workspace k: the data chain (phase 1) on the calling stream, the weight gradients (phase 2) on the side stream behind an event — on the
+        calling stream where there is no side stream (the CPU test backend)."""
+        blk, plan = self.blocks[i], self._plan_ptr()
+        H, W, D = blk.dims
+        record = self._recording(i)
+        args = (L.ptr(blk.x), byref(blk.pstruct), L.ptr(blk.gy), L.ptr(blk.saved), blk.saved_bytes, L.ptr(blk.gx), byref(blk.gstruct), L.ptr(self._ws_pool[k]),
+                self.ws_bytes, L.ptr(blk.partials), blk.partials_bytes)
+        dims7 = (self.B, blk.C, H, W, D, self.dt, 0)
+        phase = self.lib.dlka_lka3d_attention_tokens_backward_phase_v
+        if side is None:
+            L.check(phase(*args, None, i, 1, *dims7, st), "backward phase 1")
+            L.check(phase(*args, plan if record else None, i, 2, *dims7, st), "backward phase 2")
+        else:
+            cur = torch.cuda.current_stream(self.device)
+            if used[k]:
+                cur.wait_event(self._ev_wg[k])   # the weight gradients that last read this workspace are done
+            L.check(phase(*args, None, i, 1, *dims7, st), "backward phase 1")
+            self._ev_data[k].record(cur)
+            side.wait_event(self._ev_data[k])
+            L.check(phase(*args, plan if record else None, i, 2, *dims7, side.cuda_stream), "backward phase 2")
+            self._ev_wg[k].record(side)
+            used[k] = True
+            if fold_every:
+                pending.append(i)
+                if len(pending) >= fold_every:
+                    self._fold_pending(pending, side)
+        if record:
+            self._fin_recorded.add(i)
+        if not self._fin_sealed:
+            if side is not None:   # (the per-slot finalize of the recording pass reads the partial sums: behind the weight gradients)
+                cur.wait_event(self._ev_wg[k])
+                used[k] = False
+            L.check(self.lib.dlka_wgrad_finalize_run_slot(plan, i, st), "wgrad_finalize_run_slot")
+
+    def _issue_deferred(self, i, st):
+        """Block i on the calling stream, its folds left to the end of the pass (block-private partial sums)."""
+        blk, plan = self.blocks[i], self._plan_ptr()
+        H, W, D = blk.dims
+        record = self._recording(i)
+        rc = self.lib.dlka_lka3d_attention_tokens_backward_deferred_v(
+            L.ptr(blk.x), byref(blk.pstruct), L.ptr(blk.gy), L.ptr(blk.saved), blk.saved_bytes, L.ptr(blk.gx), byref(blk.gstruct), L.ptr(self.ws),
+            self.ws_bytes, L.ptr(blk.partials), blk.partials_bytes, plan if record else None, i, self.B, blk.C, H, W, D, self.dt, 0, st)
+        L.check(rc, "lka3d_attention_tokens_backward_deferred_v")
+        if record:
+            self._fin_recorded.add(i)
+        if not self._fin_sealed:   # the table is still being recorded: this block's folds as the ordinary per-block launch
+            L.check(self.lib.dlka_wgrad_finalize_run_slot(plan, i, st), "wgrad_finalize_run_slot")
+
+    def _issue_plain(self, i, st):
+        """Block i with its own finalize launch (defer_finalize=False)."""
+        blk = self.blocks[i]
+        H, W, D = blk.dims
+        rc = self.lib.dlka_lka3d_attention_tokens_backward(L.ptr(blk.x), byref(blk.pstruct), L.ptr(blk.gy), L.ptr(blk.saved),
+                                                    blk.saved_bytes, L.ptr(blk.gx), byref(blk.gstruct), L.ptr(self.ws),
+                                                    self.ws_bytes, self.B, blk.C, H, W, D, self.dt, st)
+        L.check(rc, "lka3d_attention_tokens_backward")
+
+    def _finish_pass(self, idx, st, side, used, pending, fold_every):
+        """The tail of a pass (or slice): join the side stream, fold the partial sums that are not folded yet, seal the plan once it is complete."""
         if side is not None:   # join: the finalisation (and whatever follows the pass) is behind every weight gradient
-            for k in range(K):
+            for k in range(2):
                 if used[k]:
                     torch.cuda.current_stream(self.device).wait_event(self._ev_wg[k])
-        if side_fin:
+        if fold_every:
             if pending:
-                fold_pending()
+                self._fold_pending(pending, side)
             self._ev_fin.record(side)
             torch.cuda.current_stream(self.device).wait_event(self._ev_fin)   # the gradients are complete for whatever follows the pass
-        elif defer and idx:
+        elif self._fin_host is not None and idx:
             if self._fin_sealed:
-                rc = self.lib.dlka_wgrad_finalize_run(L.ptr(self._fin_dev), plan_ptr, idx[0], idx[-1] + 1, st)
+                rc = self.lib.dlka_wgrad_finalize_run(L.ptr(self._fin_dev), self._plan_ptr(), idx[0], idx[-1] + 1, st)
                 L.check(rc, "wgrad_finalize_run")
             elif len(self._fin_recorded) == len(self.blocks) and not self._capturing():
                 # every block has been through a backward pass once: from the next pass on, ONE launch per pass (or slice)
-                L.check(self.lib.dlka_wgrad_finalize_plan_seal(plan_ptr), "wgrad_finalize_plan_seal")
+                L.check(self.lib.dlka_wgrad_finalize_plan_seal(self._plan_ptr()), "wgrad_finalize_plan_seal")
                 self._fin_dev = self._fin_host.to(self.device) if self.device.type == "cuda" else self._fin_host
                 self._fin_sealed = True
 

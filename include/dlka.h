@@ -523,9 +523,6 @@ long dlka_conv_kw_launch_count(void);
  * output; split_bf16: 0 exact fp32, 2 / 3 two- / three-term operands; K taps; epi: 0 none, 3 "+ aux"; NP: output columns padded to 32; volume: D > 1.  The planar store
  * has no aux add, so epi = 3 with omode = 1 is refused (tests/test_small_fixes.py). */
 int dlka_conv_kw_applies(int amode, int omode, int split_bf16, int K, int epi, int NP, int act_bf16, int volume);
-/* launches so far of the opt-in software-pipelined depthwise kernel (csrc/cl_dwconv.hip: cl_dwconv_rows2p_kernel, round 6; DLKA_DW_2P=1 | 2 sends the dw 5^3 /
- * 7^3 dilation-3 convs and their data gradients through it wherever its geometry fits; default: never — it measured slower than the row kernel) */
-long dlka_dwconv_2p_launch_count(void);
 size_t dlka_lka3d_tokens_workspace_bytes_v(int B, int C, int D, int H, int W, int dtype, int variant);
 int dlka_lka3d_attention_tokens_forward_v(const void *x, const dlka_lka3d_params *p, void *y, void *saved, size_t saved_bytes,
                                           void *workspace, size_t workspace_bytes, int B, int C, int D, int H, int W, int dtype, int variant, void *stream);

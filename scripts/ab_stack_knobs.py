@@ -4,7 +4,7 @@ every configuration builds its own DLKABlockStack, captures fwd+bwd in a hipGrap
 interleaved rounds so that clock / thermal drift hits all of them alike.
 
 usage: python scripts/ab_stack_knobs.py OUT.json [--dtype f32|bf16] [--rounds 3] [--steps 30] -- NAME:K=V,K=V NAME2: ...
-  e.g. ... -- base: inline0:DLKA_STACK_WGRAD_OVERLAP_MIN_C=64 packed:DLKA_GOFF_PACKED=1
+  e.g. ... -- base: onefold:DLKA_STACK_FINALIZE_GROUP=0 packed:DLKA_GOFF_PACKED=1
 (knobs read once per process by the LIBRARY — `static const` getenv — cannot be A/B-ed this way; the ones used here are read per stack / per call)
 pseudo-knobs handled here: _stages=0+1 (only those stages' blocks), _lib=PATH (another build of libdlka_hip.so, bound in this process)"""
 import json

@@ -802,68 +802,19 @@ def test_lka3d_tokens_block_through_brick_kernels(split, monkeypatch):
     assert lib.dlka_conv_brick_launch_count() - n1 >= 2
 
 
-@pytest.mark.parametrize("case", [(1, 32, (13, 7, 9), 7, 9, 3), (2, 32, (5, 6, 9), 5, 2, 1), (1, 32, (12, 6, 8), 7, 9, 3)])
-def test_dwconv_two_output_planes(case, monkeypatch):
-    """cl_dwconv_rows2d_kernel (depthwise 5^3 / 7^3 dilation 3 with two output planes AND two output rows per work-item, tap weights + one zero tap plane in LDS; 32 channels)
-    against the fp64 conv (forward, data gradient through the same kernel with flipped taps, weight gradient untouched) — and bit for bit against the one-plane kernel it
-    stands beside (default: one plane; the same FMA chain per output, zero products added at the pair's outer planes).  Cases: odd depth / height / width (an unpaired
-    last plane, ragged rows and runs); 5^3 across a batch; even sizes."""
-    from deformablelka_amd import ops
+@pytest.mark.parametrize("case", [(1, 32, (13, 7, 9), 7, 9, 3), (2, 32, (5, 6, 9), 5, 2, 1), (1, 32, (12, 6, 8), 7, 9, 3), (1, 32, (13, 7, 16), 7, 9, 3),
+                                  (2, 64, (5, 6, 16), 5, 2, 1), (1, 32, (12, 8, 9), 7, 9, 3), (1, 32, (7, 5, 12), 5, 2, 1)])
+def test_dwconv_row_kernels_at_ragged_shapes(case):
+    """The depthwise 5^3 / 7^3 dilation-3 row kernels (cl_dwconv.hip: one and two output rows per work-item) against the fp64 conv — forward, data gradient through the
+    same kernel with flipped taps, weight gradient — at the ragged shapes: odd depth / height / width (an unpaired last plane / row, rows outside the volume), a ragged last
+    run (W = 9, 12), 5^3 across a batch, two channel groups across a batch (C = 64), even sizes."""
     B, C, dims, k, p, d = case
-    monkeypatch.setenv("DLKA_DW_TD2", "1")   # opt-in: measured slower than the one-plane kernel on the MI355X (cl_dwconv.hip)
     parity.check_conv3d_cl("cpu", B, C, C, dims, k, p, d, C, planar=False, seed=8)
-    gen = torch.Generator().manual_seed(10)
-    x = torch.randn(B, *dims, C, generator=gen)
-    w = torch.randn(C, 1, k, k, k, generator=gen) * 0.1
-    bias = torch.randn(C, generator=gen)
-    y2 = ops.conv3d_forward_cl(x, w, bias, p, d, C)
-    monkeypatch.delenv("DLKA_DW_TD2")
-    y1 = ops.conv3d_forward_cl(x, w, bias, p, d, C)
-    assert torch.equal(y1, y2)
 
 
-@pytest.mark.parametrize("mode", ["1", "2"])
-@pytest.mark.parametrize("case", [(1, 32, (13, 7, 16), 7, 9, 3), (2, 64, (5, 6, 16), 5, 2, 1), (1, 32, (12, 8, 9), 7, 9, 3), (1, 32, (7, 5, 12), 5, 2, 1)])
-def test_dwconv_pipelined_row_pairs(case, mode, monkeypatch):
-    """cl_dwconv_rows2p_kernel (round 6: software-pipelined input rows, the two output rows of a work-item on the two halves of v_pk_fma_f32, two output planes, tap weights with
-    zero rows in LDS) against the fp64 conv (forward, data gradient through the same kernel with flipped taps) — and bit for bit against the row kernel it replaces (the
-    same FMA chain per output, zero products added for the first / last input row).  Cases: odd depth / height (unpaired last plane / row, planes and rows outside the volume),
-    two channel groups across a batch, a ragged last run (W = 9, 12), both ring depths (mode 2: one row ahead)."""
-    from deformablelka_amd import ops
-    B, C, dims, k, p, d = case
-    from deformablelka_amd._lib import get_lib
-    lib = get_lib()
-    monkeypatch.setenv("DLKA_DW_2P", mode)
-    n0 = lib.dlka_dwconv_2p_launch_count()
-    parity.check_conv3d_cl("cpu", B, C, C, dims, k, p, d, C, planar=False, seed=8)
-    assert lib.dlka_dwconv_2p_launch_count() - n0 >= 2, (n0, lib.dlka_dwconv_2p_launch_count())   # forward + data gradient
-    gen = torch.Generator().manual_seed(10)
-    x = torch.randn(B, *dims, C, generator=gen)
-    w = torch.randn(C, 1, k, k, k, generator=gen) * 0.1
-    bias = torch.randn(C, generator=gen)
-    y2 = ops.conv3d_forward_cl(x, w, bias, p, d, C)
-    monkeypatch.setenv("DLKA_DW_2P", "0")
-    y1 = ops.conv3d_forward_cl(x, w, bias, p, d, C)
-    assert torch.equal(y1, y2)
-
-
-def test_dwconv_pipelined_row_pairs_in_the_bf16_block(monkeypatch):
-    """The bf16-storage instantiation of cl_dwconv_rows2p_kernel, reached through the token block (DLKA_BF16, DLKA_DW_2P=1): the block's parity against the oracle holds and its
-    output equals the default row kernels' bit for bit (volume 7 x 6 x 16: both depthwise convs and both data gradients fit the kernel's geometry)."""
-    import deformablelka_amd as dk
-    from deformablelka_amd._lib import get_lib
-    lib = get_lib()
-    monkeypatch.setenv("DLKA_DW_2P", "1")
-    n0 = lib.dlka_dwconv_2p_launch_count()
+def test_lka3d_tokens_bf16_block_at_a_ragged_volume():
+    """The bf16-storage instantiations of the depthwise row kernels, reached through the token block (DLKA_BF16) at volume 7 x 6 x 16: the block's parity against the oracle."""
     parity.check_lka3d_tokens_bf16("cpu", 1, 32, (7, 6, 16))
-    assert lib.dlka_dwconv_2p_launch_count() - n0 >= 4, (n0, lib.dlka_dwconv_2p_launch_count())   # dw 5^3, dw 7^3 dil 3 and their data gradients
-    torch.manual_seed(3)
-    m = dk.LKA_Attention3d_deform(32)
-    x = torch.randn(1, 6 * 16 * 7, 32).bfloat16()
-    y2 = m(x, 1, 32, 7, 6, 16)
-    monkeypatch.setenv("DLKA_DW_2P", "0")
-    y1 = m(x, 1, 32, 7, 6, 16)
-    assert torch.equal(y1, y2)
 
 
 @pytest.mark.parametrize("C,dims,bf", [(32, (3, 4, 5), False), (64, (2, 4, 3), True)])

@@ -186,6 +186,11 @@ CL_CONV = [
     (2, 32, 32, (12, 12, 12), 7, 9, 3, 32, False),
     (2, 128, 128, (8, 8, 8), 7, 9, 3, 128, False),    # stage-2 dw7, real size
     (2, 256, 256, (4, 4, 4), 5, 2, 1, 256, False),    # stage-3 dw5, real size
+    (2, 32, 32, (32, 32, 32), 7, 9, 3, 32, False),    # stage-0 dw7, real size
+    (2, 32, 32, (32, 32, 32), 5, 2, 1, 32, False),    # stage-0 dw5, real size
+    (2, 64, 64, (16, 16, 16), 7, 9, 3, 64, False),    # stage-1 dw7, real size
+    (1, 32, 32, (13, 7, 9), 7, 9, 3, 32, False),      # odd depth / height / width: an unpaired last row, a ragged last run
+    (2, 64, 64, (5, 6, 16), 5, 2, 1, 64, False),      # two channel groups across a batch
 ]
 
 
@@ -1201,33 +1206,6 @@ def test_dwpair_equals_unfused(C, dims, bf):
     wrapper block's outputs and gradients, fp32 and DLKA_BF16 storage, at the real stage shapes and two ragged ones.  (That block is also held to the oracle by the
     tblock parity tests, which run through the fused kernel at these shapes.)"""
     parity.check_dwpair_equals_unfused(DEV, 2, C, dims, lka_bf16=bf)
-
-
-@pytest.mark.parametrize("case", [(2, 32, (32, 32, 32), 7, 9, 3), (2, 32, (32, 32, 32), 5, 2, 1), (2, 64, (16, 16, 16), 7, 9, 3), (1, 32, (13, 7, 9), 7, 9, 3), (2, 64, (5, 6, 16), 5, 2, 1)])
-def test_dwconv_pipelined_row_pairs_equal_row_kernel(case, monkeypatch):
-    """cl_dwconv_rows2p_kernel (round 6, opt-in DLKA_DW_2P: software-pipelined rows, output rows on the halves of v_pk_fma_f32, two output planes) at the stage-0 / stage-1
-    shapes and two ragged ones: bit for bit the row kernel's result (same FMA chain per output), forward and data gradient, and the fp64 conv's to 1e-4."""
-    from deformablelka_amd import ops
-    from deformablelka_amd._lib import get_lib
-    lib = get_lib()
-    B, C, dims, k, p, d = case
-    gen = torch.Generator().manual_seed(11)
-    x = torch.randn(B, *dims, C, generator=gen).to(DEV)
-    g = torch.randn(B, *dims, C, generator=gen).to(DEV)
-    w = (torch.randn(C, 1, k, k, k, generator=gen) * 0.1).to(DEV)
-    bias = torch.randn(C, generator=gen).to(DEV)
-    res = {}
-    for mode in ("0", "1", "2"):
-        monkeypatch.setenv("DLKA_DW_2P", mode)
-        n0 = lib.dlka_dwconv_2p_launch_count()
-        y = ops.conv3d_forward_cl(x, w, bias, p, d, C)
-        gi = ops.conv3d_backward_cl(x, w, g, p, d, C)[0]
-        assert (lib.dlka_dwconv_2p_launch_count() - n0 >= 2) == (mode != "0"), (mode, n0, lib.dlka_dwconv_2p_launch_count())
-        res[mode] = (y, gi)
-    for mode in ("1", "2"):
-        assert torch.equal(res["0"][0], res[mode][0]) and torch.equal(res["0"][1], res[mode][1]), mode
-    ref = torch.nn.functional.conv3d(x.permute(0, 4, 1, 2, 3).double().cpu(), w.double().cpu(), bias.double().cpu(), padding=p, dilation=d, groups=C).permute(0, 2, 3, 4, 1)
-    assert float((res["1"][0].double().cpu() - ref).abs().max()) <= 1e-4 * float(ref.abs().max())
 
 
 @pytest.mark.parametrize("bf", [False, True])
