@@ -38,6 +38,9 @@ DLKA_PREP_C_MAX, DLKA_PREP_REC = 32, 8                                  # includ
 DLKA_PREP_CT, DLKA_PREP_CT2, DLKA_PREP_NONCT = 0, 1, 2
 DLKA_ZOOM2D_I16, DLKA_ZOOM2D_K_MAX, DLKA_ZOOM2D_OUTSIDE = 3, 255, -2 ** 31   # include/dlka.h: dlka_zoom2d_*
 DLKA_OPTIM_TENSORS_PER_LAUNCH, DLKA_OPTIM_CHUNK = 120, 4096               # include/dlka.h: dlka_optim_*
+DLKA_LOAD_B_MAX, DLKA_LOAD_K_MAX = 32, 32                                  # include/dlka.h: dlka_load_*
+DLKA_LOAD_CONSTANT, DLKA_LOAD_EDGE = 0, 1
+DLKA_LOAD_F32, DLKA_LOAD_I32 = 0, 1
 (DLKA_AUG_OP_NONE, DLKA_AUG_OP_NOISE, DLKA_AUG_OP_SCALE_ADD, DLKA_AUG_OP_CONTRAST, DLKA_AUG_OP_GAMMA, DLKA_AUG_OP_RETAIN,
  DLKA_AUG_OP_REPLACE) = range(7)
 
@@ -121,6 +124,22 @@ class OptimDesc(ctypes.Structure):
     """``dlka_optim_desc`` (include/dlka.h)."""
     _fields_ = [("n_tensors", c_int32), ("dtype", c_int32), ("nesterov", c_int32), ("has_momentum", c_int32), ("clip", c_int32),
                 ("momentum", ctypes.c_float), ("weight_decay", ctypes.c_float), ("max_norm", ctypes.c_float), ("lr_index", c_int32)]
+
+
+class LoadSample(ctypes.Structure):
+    """``dlka_load_sample`` (include/dlka.h)."""
+    _fields_ = [("data", c_void_p), ("ext", c_int64 * 3), ("lb", c_int64 * 3)]
+
+
+class LoadCropDesc(ctypes.Structure):
+    """``dlka_load_crop_desc`` (include/dlka.h)."""
+    _fields_ = [("B", c_int32), ("C", c_int32), ("mode", c_int32), ("constant", ctypes.c_float), ("patch", c_int64 * 3),
+                ("sample", LoadSample * DLKA_LOAD_B_MAX)]
+
+
+class LoadClassesDesc(ctypes.Structure):
+    """``dlka_load_classes_desc`` (include/dlka.h)."""
+    _fields_ = [("K", c_int32), ("dtype", c_int32), ("ext", c_int64 * 3), ("class_id", c_int64 * DLKA_LOAD_K_MAX)]
 
 
 # name -> (restype, argtypes); every symbol include/dlka.h declares
@@ -307,6 +326,13 @@ SIGNATURES = {
     "dlka_optim_scale": (c_int, [_PTRS, _I64S, c_int64, c_int, c_void_p, ctypes.c_float, c_void_p]),
     "dlka_optim_sgd_step": (c_int, [_PTRS, _PTRS, _PTRS, _I64S, _OPD, c_void_p, c_void_p, c_void_p]),
     "dlka_optim_launch_count": (ctypes.c_long, []),
+    "dlka_load_crop_batch": (c_int, [POINTER(LoadCropDesc), c_void_p, c_void_p, c_void_p]),
+    "dlka_load_counts_workspace_bytes": (c_size_t, [POINTER(LoadClassesDesc)]),
+    "dlka_load_class_counts": (c_int, [c_void_p, POINTER(LoadClassesDesc), c_void_p, c_size_t, c_void_p, c_void_p]),
+    "dlka_load_select_workspace_bytes": (c_size_t, [POINTER(LoadClassesDesc), _I64S]),
+    "dlka_load_class_select": (c_int, [c_void_p, POINTER(LoadClassesDesc), c_void_p, c_size_t, _I64S, c_void_p, c_size_t, c_void_p, c_void_p,
+                                       c_int64, c_void_p, c_void_p]),
+    "dlka_load_launch_count": (ctypes.c_long, []),
     "dlka_trace_start": (c_int, [c_int, c_void_p]),
     "dlka_trace_mark": (c_int, [c_void_p]),
     "dlka_trace_stop": (c_int, []),

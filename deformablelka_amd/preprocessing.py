@@ -210,16 +210,20 @@ class GenericPreprocessor(object):
         out, seg_out, properties = self._resample_and_normalize(t.to(torch.float32), seg_t, target_spacing, properties, force_separate_z, False)
         return back(out), None if seg is None else seg_back(seg_out), properties
 
-    def preprocess_arrays(self, data, target_spacing, properties, seg=None, force_separate_z=None):
+    def preprocess_arrays(self, data, target_spacing, properties, seg=None, force_separate_z=None, *, all_classes=None):
         """``preprocess_test_case`` (:308-316) from the point where the files have been read: crop to the nonzero region, ``transpose_forward``,
         resample to ``target_spacing`` (already transposed) and normalise.  ``properties`` needs ``original_spacing``.  Data comes back as
-        float32; the volume does not leave the device between the stages."""
+        float32; the volume does not leave the device between the stages.  With ``all_classes`` the returned properties carry
+        ``class_locations`` of the returned seg's last channel, as ``_run_internal`` records them (:333-348, ``dataloading.class_locations``)."""
         if len(data.shape) != 4:
             raise NotImplementedError(f"preprocessing: preprocess_arrays takes (C, X, Y, Z) data, got {tuple(data.shape)}")
         _, _, properties, (t, seg_t) = ImageCropper._crop(data, properties, seg, True)
         perm = (0, *[i + 1 for i in self.transpose_forward])
         t, seg_t = t.permute(perm).contiguous(), seg_t.permute(perm).contiguous()
         out, seg_out, properties = self._resample_and_normalize(t, seg_t, target_spacing, properties, force_separate_z, True)
+        if all_classes is not None:
+            from .dataloading import class_locations
+            properties["class_locations"] = class_locations(seg_out[-1], all_classes)
         _, back = load(data, "preprocessing", "data")
         if seg is None:
             return back(out, torch.float32), back(seg_out, torch.int64), properties
@@ -249,8 +253,8 @@ class GenericPreprocessor(object):
 
     def __getattr__(self, name):
         if name in ("run", "_run_internal", "load_cropped"):
-            raise NotImplementedError(f"preprocessing: GenericPreprocessor.{name} (.npz / .pkl files, class_locations and the worker pool) "
-                                      "is not part of this module")
+            raise NotImplementedError(f"preprocessing: GenericPreprocessor.{name} (.npz / .pkl files and the worker pool) is not part of this module; "
+                                      "preprocess_arrays(..., all_classes=...) records class_locations")
         raise AttributeError(name)
 
 

@@ -1038,6 +1038,60 @@ int dlka_optim_sgd_step(void *const *params, const void *const *grads, void *con
 long dlka_optim_launch_count(void);
 
 /* =======================================================================================
+ * The 3-D trainer's batch loader: oversampled patch batches and class locations — csrc/cl_dataload.hip
+ * =======================================================================================
+ * DataLoader3D.generate_train_batch (3D/d_lka_former/training/dataloading/dataset_loading.py:223-379) cuts one box per sample out of a
+ * case [C + 1][x][y][z] float32 (the label map is the last channel) and pads what falls outside; GenericPreprocessor._run_internal
+ * (preprocessing/preprocessing.py:333-348) records, per class, the cells the loader's foreground oversampling centres a box on.
+ *
+ * dlka_load_crop_batch     data [B][C][patch] and seg [B][1][patch] of B <= DLKA_LOAD_B_MAX samples in ONE launch.  Sample b reads the case
+ *                          at sample[b].data with extents sample[b].ext; output cell p takes case cell p + sample[b].lb.  Outside the case
+ *                          the data takes `constant` (DLKA_LOAD_CONSTANT) or the nearest cell of the case (DLKA_LOAD_EDGE: np.pad's 'edge');
+ *                          the label map always takes -1.  The description is a HOST structure; the library hands it to the kernel by
+ *                          value, so a call copies nothing to the device.  Cells are moved as bits.  A larger batch is the caller's to cut.
+ * dlka_load_class_counts   one read of a label map [x][y][z] (DLKA_LOAD_F32 with integer values, or DLKA_LOAD_I32) for all K <=
+ *                          DLKA_LOAD_K_MAX distinct class_id: totals[K] int32 (device) = cells per class, and in `workspace`
+ *                          (dlka_load_counts_workspace_bytes, kept for the selection) the exclusive offset of every tile per class.  Cells
+ *                          with any other label are ignored.  Two launches.
+ * dlka_load_class_select   out[count][3] int32 (device) = the (x, y, z) of cell number sel_rank[j], in raster order (numpy.argwhere's), among
+ *                          the cells of class_id[sel_slot[j]].  `offsets` is the workspace dlka_load_class_counts filled for the same map
+ *                          and description, `totals` its totals read back (host, int64); `workspace`: dlka_load_select_workspace_bytes.
+ *                          The order comes from the scan of the tile counts; there is no atomic: bitwise reproducible.  A slot or rank
+ *                          that does not exist gives (-1, -1, -1).  Two launches.
+ * Return codes: DLKA_ERR_NULL, DLKA_ERR_SHAPE (B, C, K, count or an extent < 1, a class_id listed twice, totals no map of these extents
+ * has), DLKA_ERR_DTYPE, DLKA_ERR_UNSUPPORTED (B > DLKA_LOAD_B_MAX, K > DLKA_LOAD_K_MAX, another mode, a case or label map of 2^31 cells per
+ * channel or more, a patch extent or |lb| above 2^30, |class_id| above 2^24), DLKA_ERR_WORKSPACE.  Nothing is launched before the checks pass. */
+#define DLKA_LOAD_B_MAX 32
+#define DLKA_LOAD_K_MAX 32
+enum { DLKA_LOAD_CONSTANT = 0, DLKA_LOAD_EDGE = 1 };
+enum { DLKA_LOAD_F32 = 0, DLKA_LOAD_I32 = 1 };
+typedef struct dlka_load_sample {
+    const float *data;
+    int64_t ext[3], lb[3];
+} dlka_load_sample;
+typedef struct dlka_load_crop_desc {
+    int32_t B, C, mode;
+    float constant;
+    int64_t patch[3];
+    dlka_load_sample sample[DLKA_LOAD_B_MAX];
+} dlka_load_crop_desc;
+typedef struct dlka_load_classes_desc {
+    int32_t K, dtype;
+    int64_t ext[3];
+    int64_t class_id[DLKA_LOAD_K_MAX];
+} dlka_load_classes_desc;
+int dlka_load_crop_batch(const dlka_load_crop_desc *d, float *data, float *seg, void *stream);
+size_t dlka_load_counts_workspace_bytes(const dlka_load_classes_desc *d);
+int dlka_load_class_counts(const void *seg, const dlka_load_classes_desc *d, void *workspace, size_t workspace_bytes, int32_t *totals,
+                           void *stream);
+size_t dlka_load_select_workspace_bytes(const dlka_load_classes_desc *d, const int64_t *totals);
+int dlka_load_class_select(const void *seg, const dlka_load_classes_desc *d, const void *offsets, size_t offsets_bytes, const int64_t *totals,
+                           void *workspace, size_t workspace_bytes, const int32_t *sel_slot, const int32_t *sel_rank, int64_t count,
+                           int32_t *out, void *stream);
+/* Diagnostics: kernel launches so far (this process) of the entries above. */
+long dlka_load_launch_count(void);
+
+/* =======================================================================================
  * Launch trace — measurement aid (no reference counterpart; the reference has no profiling hooks)
  * =======================================================================================
  * Between dlka_trace_start and dlka_trace_stop every kernel launch of the library is followed by a HIP timing event on the
