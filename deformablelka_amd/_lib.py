@@ -41,6 +41,8 @@ DLKA_OPTIM_TENSORS_PER_LAUNCH, DLKA_OPTIM_CHUNK = 120, 4096               # incl
 DLKA_LOAD_B_MAX, DLKA_LOAD_K_MAX = 32, 32                                  # include/dlka.h: dlka_load_*
 DLKA_LOAD_CONSTANT, DLKA_LOAD_EDGE = 0, 1
 DLKA_LOAD_F32, DLKA_LOAD_I32 = 0, 1
+DLKA_DSTATS_RANKS_MAX, DLKA_DSTATS_LABEL_MIN, DLKA_DSTATS_LABEL_MAX, DLKA_DSTATS_LABEL_WORDS = 8, -1, 255, 10   # include/dlka.h: dlka_dstats_*
+DLKA_DSTATS_F32, DLKA_DSTATS_I32 = 0, 1
 (DLKA_AUG_OP_NONE, DLKA_AUG_OP_NOISE, DLKA_AUG_OP_SCALE_ADD, DLKA_AUG_OP_CONTRAST, DLKA_AUG_OP_GAMMA, DLKA_AUG_OP_RETAIN,
  DLKA_AUG_OP_REPLACE) = range(7)
 
@@ -142,6 +144,11 @@ class LoadClassesDesc(ctypes.Structure):
     _fields_ = [("K", c_int32), ("dtype", c_int32), ("ext", c_int64 * 3), ("class_id", c_int64 * DLKA_LOAD_K_MAX)]
 
 
+class DatasetStatsDesc(ctypes.Structure):
+    """``dlka_dstats_desc`` (include/dlka.h)."""
+    _fields_ = [("rank", c_int32), ("C", c_int32), ("label_dtype", c_int32), ("reserved", c_int32), ("ext", c_int64 * 3), ("step", c_int64)]
+
+
 # name -> (restype, argtypes); every symbol include/dlka.h declares
 _G = POINTER(ConvGeom)
 _SD = POINTER(SegLossDesc)
@@ -152,6 +159,7 @@ _AGD = POINTER(AugmentDesc)
 _PPD = POINTER(PrepDesc)
 _ZMD = POINTER(Zoom2dDesc)
 _OPD = POINTER(OptimDesc)
+_DSD = POINTER(DatasetStatsDesc)
 _PTRS, _I64S = POINTER(c_void_p), POINTER(c_int64)
 SIGNATURES = {
     "dlka_abi_version": (c_int, []),
@@ -333,6 +341,15 @@ SIGNATURES = {
     "dlka_load_class_select": (c_int, [c_void_p, POINTER(LoadClassesDesc), c_void_p, c_size_t, _I64S, c_void_p, c_size_t, c_void_p, c_void_p,
                                        c_int64, c_void_p, c_void_p]),
     "dlka_load_launch_count": (ctypes.c_long, []),
+    "dlka_dstats_fg_workspace_bytes": (c_size_t, [_DSD]),
+    "dlka_dstats_fg_count": (c_int, [c_void_p, _DSD, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "dlka_dstats_fg_sample": (c_int, [c_void_p, c_void_p, _DSD, c_void_p, c_size_t, c_int64, c_void_p, c_int64, c_int64, c_void_p]),
+    "dlka_dstats_moments_workspace_bytes": (c_size_t, [c_int64]),
+    "dlka_dstats_moments": (c_int, [c_void_p, c_int64, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "dlka_dstats_select_workspace_bytes": (c_size_t, []),
+    "dlka_dstats_select": (c_int, [c_void_p, c_int64, _I64S, c_int32, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
+    "dlka_dstats_unique_labels": (c_int, [c_void_p, _DSD, c_void_p, c_void_p]),
+    "dlka_dstats_launch_count": (ctypes.c_long, []),
     "dlka_trace_start": (c_int, [c_int, c_void_p]),
     "dlka_trace_mark": (c_int, [c_void_p]),
     "dlka_trace_stop": (c_int, []),

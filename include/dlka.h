@@ -1092,6 +1092,60 @@ int dlka_load_class_select(const void *seg, const dlka_load_classes_desc *d, con
 long dlka_load_launch_count(void);
 
 /* =======================================================================================
+ * The dataset fingerprint: DatasetAnalyzer's intensity statistics and unique labels — csrc/cl_dataset_stats.hip
+ * =======================================================================================
+ * DatasetAnalyzer (3D/d_lka_former/experiment_planning/DatasetAnalyzer.py) samples every tenth foreground voxel of every case
+ * (_get_voxels_in_foreground, :161-166), takes median, mean, sd, min, max and the 99.5 / 0.5 percentiles of the samples of a case and of
+ * the whole dataset (_compute_stats, :168-179; collect_intensity_properties, :181-223), and lists the labels of a case (_get_unique_labels,
+ * :76-79).  All device arrays below are contiguous; a label map is float32 with integer values (DLKA_DSTATS_F32, the last channel of a
+ * cropped case) or int32 (DLKA_DSTATS_I32) and is read in that type.
+ *
+ * dlka_dstats_fg_count       :164: *count (device, int64) = cells of the label map [ext] with label > 0, and in `workspace`
+ *                            (dlka_dstats_fg_workspace_bytes, kept for the sample) the exclusive offset of every tile.  Two launches.
+ * dlka_dstats_fg_sample      :163-165: out[c * out_stride + out_offset + j] = data[c][mask][::step][j] for the C <= DLKA_PREP_C_MAX volumes
+ *                            data [C][ext] and j < out_count, in raster order, fixed by the scan: no atomic.  `offsets` is the workspace
+ *                            dlka_dstats_fg_count filled for the same map and description; out_count = ceil(count / step) as the host read
+ *                            it (a smaller value writes fewer, a larger one no more than exist).  Writing at out_offset is what lets the
+ *                            samples of a dataset's cases land in one buffer, case after case.  One launch.
+ * dlka_dstats_moments        :173-174: result[4] (device, float64) = n, np.mean, np.std (ddof 0), the number of NaNs of x[n], accumulated in
+ *                            float64 in a fixed order, two passes (mean, then centred squares).  Four launches.
+ * dlka_dstats_select         :172,175-178: values[j] (device) = the ranks[j]-th smallest (0-based) of x[n], NaNs sorting last as numpy sorts
+ *                            them (a rank among them gives a NaN) and -0.0 counting as +0.0, which is what a zero comes back as;
+ *                            *nan_count (device, int64, may be NULL) = the NaNs of x.  `ranks` is a HOST array of n_ranks <=
+ *                            DLKA_DSTATS_RANKS_MAX ranks.  A radix select, 4 passes of 8 bits over x, which is only read; `workspace`:
+ *                            dlka_dstats_select_workspace_bytes.  Nine launches, whatever n and the ranks are.
+ * dlka_dstats_unique_labels  :78: bitmap[DLKA_DSTATS_LABEL_WORDS] (device): bit (v - DLKA_DSTATS_LABEL_MIN) % 32 of word
+ *                            (v - DLKA_DSTATS_LABEL_MIN) / 32 is set for every label v of the map; the LAST word is nonzero when a label lies
+ *                            outside DLKA_DSTATS_LABEL_MIN .. DLKA_DSTATS_LABEL_MAX or is no integer.  One launch.
+ * Integer atomics only: every result is bitwise reproducible.
+ * Return codes: DLKA_ERR_NULL, DLKA_ERR_SHAPE (rank outside 2..3, rank 2 with ext[0] != 1, C, step, n, n_ranks, out_count or an extent < 1,
+ * a rank outside 0 .. n - 1, out_count beyond ceil(cells / step), out_offset < 0 or out_offset + out_count > out_stride), DLKA_ERR_DTYPE,
+ * DLKA_ERR_UNSUPPORTED (C > DLKA_PREP_C_MAX, n_ranks > DLKA_DSTATS_RANKS_MAX, a map of 2^31 cells or more, step above 2^31 - 1, n of 2^32
+ * or more), DLKA_ERR_WORKSPACE.  Nothing is launched before the checks pass. */
+#define DLKA_DSTATS_RANKS_MAX 8
+#define DLKA_DSTATS_LABEL_MIN (-1)
+#define DLKA_DSTATS_LABEL_MAX 255
+#define DLKA_DSTATS_LABEL_WORDS 10
+enum { DLKA_DSTATS_F32 = 0, DLKA_DSTATS_I32 = 1 };
+typedef struct dlka_dstats_desc {
+    int32_t rank, C, label_dtype, reserved;   /* rank 2: ext[0] = 1; C: volumes of the sample (1 where none is read) */
+    int64_t ext[3];
+    int64_t step;                             /* every step-th foreground cell (1 where none is sampled) */
+} dlka_dstats_desc;
+size_t dlka_dstats_fg_workspace_bytes(const dlka_dstats_desc *d);
+int dlka_dstats_fg_count(const void *seg, const dlka_dstats_desc *d, void *workspace, size_t workspace_bytes, int64_t *count, void *stream);
+int dlka_dstats_fg_sample(const float *data, const void *seg, const dlka_dstats_desc *d, const void *offsets, size_t offsets_bytes,
+                          int64_t out_count, float *out, int64_t out_stride, int64_t out_offset, void *stream);
+size_t dlka_dstats_moments_workspace_bytes(int64_t n);
+int dlka_dstats_moments(const float *x, int64_t n, void *workspace, size_t workspace_bytes, double *result, void *stream);
+size_t dlka_dstats_select_workspace_bytes(void);
+int dlka_dstats_select(const float *x, int64_t n, const int64_t *ranks, int32_t n_ranks, void *workspace, size_t workspace_bytes,
+                       float *values, int64_t *nan_count, void *stream);
+int dlka_dstats_unique_labels(const void *seg, const dlka_dstats_desc *d, uint32_t *bitmap, void *stream);
+/* Diagnostics: kernel launches so far (this process) of the entries above. */
+long dlka_dstats_launch_count(void);
+
+/* =======================================================================================
  * Launch trace — measurement aid (no reference counterpart; the reference has no profiling hooks)
  * =======================================================================================
  * Between dlka_trace_start and dlka_trace_stop every kernel launch of the library is followed by a HIP timing event on the
