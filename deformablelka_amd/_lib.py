@@ -79,6 +79,14 @@ class Lka2dPtrs(ctypes.Structure):
     _fields_ = [(n, c_void_p) for n in LKA2D_FIELDS]
 
 
+LKA2D_PLAIN_FIELDS = ("proj_1_w", "proj_1_b", "conv0_w", "conv0_b", "conv_spatial_w", "conv_spatial_b", "conv1_w", "conv1_b", "proj_2_w", "proj_2_b")
+
+
+class Lka2dPlainPtrs(ctypes.Structure):
+    """``dlka_lka2d_plain_params`` / ``dlka_lka2d_plain_grads``."""
+    _fields_ = [(n, c_void_p) for n in LKA2D_PLAIN_FIELDS]
+
+
 class SegLossDesc(ctypes.Structure):
     """``dlka_seg_loss_desc`` (include/dlka.h)."""
     _fields_ = [("B", c_int32), ("K", c_int32), ("N", c_int64), ("dtype", c_int32), ("label_dtype", c_int32), ("mode", c_int32),
@@ -198,6 +206,15 @@ SIGNATURES = {
                                               POINTER(Lka2dPtrs), c_void_p, c_size_t] + [c_int] * 5 + [c_void_p]),
     "dlka_lka2d_force_general": (c_int, [c_int]),
     "dlka_lka2d_saved_offsets": (c_int, [c_int] * 5 + [POINTER(c_size_t), POINTER(c_int)]),
+    "dlka_lka2d_plain_saved_bytes": (c_size_t, [c_int] * 5),
+    "dlka_lka2d_plain_workspace_bytes": (c_size_t, [c_int] * 5),
+    "dlka_lka2d_plain_attention_forward": (c_int, [c_void_p, POINTER(Lka2dPlainPtrs), c_void_p, c_void_p, c_size_t, c_void_p, c_size_t]
+                                           + [c_int] * 5 + [c_void_p]),
+    "dlka_lka2d_plain_attention_backward": (c_int, [c_void_p, POINTER(Lka2dPlainPtrs), c_void_p, c_void_p, c_size_t, c_void_p,
+                                                    POINTER(Lka2dPlainPtrs), c_void_p, c_size_t] + [c_int] * 5 + [c_void_p]),
+    "dlka_dwconv2d_cl_workspace": (c_size_t, [_G, c_int, c_int]),
+    "dlka_dwconv2d_forward_cl": (c_int, [c_void_p] * 5 + [c_size_t, _G, c_int, c_void_p]),
+    "dlka_dwconv2d_backward_cl": (c_int, [c_void_p] * 7 + [c_size_t, _G, c_int, c_void_p]),
     "dlka_conv3d_cl_workspace": (c_size_t, [_G, c_int, c_int]),
     "dlka_conv3d_forward_cl": (c_int, [c_void_p] * 4 + [c_int, c_void_p, c_size_t, _G, c_int, c_void_p]),
     "dlka_conv3d_backward_cl": (c_int, [c_void_p] * 3 + [c_int] + [c_void_p] * 4 + [c_size_t, _G, c_int, c_void_p]),

@@ -144,6 +144,26 @@ struct DwArgs2d {
     int act_bf16;        // backward: in / g are bf16 storage (gx, goff, the weight-gradient partials stay fp32); the forward kernel is fp32-in only
 };
 
+// channels-last 2-D depthwise conv with bias (cl_dw2d.hip): the plain LKA block's conv0 / conv_spatial; kernel size and dilation are template parameters
+struct Dw2dArgs {
+    const float *in;    // [B][H][W][C], float or (act_bf16) bf16 storage
+    const float *wp;    // [k k][C] prepared tap weights (prep mode 3: forward; mode 4: flipped = data gradient)
+    const float *bias;  // [C] fp32 or null
+    float *out;         // [B][H][W][C], storage as `in`
+    int B, H, W, C;
+    int act_bf16;
+};
+
+struct Dw2dWgradArgs {
+    const float *g;     // [B][H][W][C] grad_out
+    const float *in;    // [B][H][W][C]
+    float *part;        // [chunks][k k][C] partial weight-gradient tiles, followed by [chunks][C] partial bias sums (cl_dw2d_part_floats)
+    float *bpart;       // set by the launcher: the bias sums inside `part`, or null
+    int B, H, W, C;
+    int runs_per_chunk, chunks;   // set by the launcher
+    int act_bf16;       // 1: g / in are bf16 storage (the partial tiles stay fp32)
+};
+
 struct DwWgradArgs {
     const float *g;     // [B][D][H][W][C]
     const float *in;    // [B][D][H][W][C]

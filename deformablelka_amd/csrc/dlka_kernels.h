@@ -124,6 +124,13 @@ int lka2d_cl_forward(const void *x, const dlka_lka2d_params *p, void *y, void *s
 int lka2d_cl_backward(const void *x, const dlka_lka2d_params *p, const void *gy, const void *saved, size_t saved_bytes, void *gx, const dlka_lka2d_grads *gr,
                       void *workspace, size_t workspace_bytes, int B, int C, int H, int W, int dtype, hipStream_t st);
 
+// ---- cl_dw2d.hip: channels-last 2-D depthwise conv with bias, (k, dil) = (5, 1) | (7, 3) (the plain 2-D LKA block's large-kernel convs) --------
+bool cl_dw2d_supported(int B, int H, int W, int C, int k, int dil);
+int launch_cl_dw2d(const Dw2dArgs &a, int k, int dil, hipStream_t st);   // forward, or — on flipped taps without bias — the data gradient
+int cl_dw2d_wgrad_chunks(int B, int H, int W);
+size_t cl_dw2d_part_floats(int B, int H, int W, int C, int k);
+int launch_cl_dw2d_wgrad(Dw2dWgradArgs a, int k, int dil, float *gw, float *gb, hipStream_t st, FinalizeJob *fold);   // partial tiles; `fold` goes to launch_cl_wgrad_finalize
+
 // ---- cl_norm.hip: the non-convolutional pieces of TransformerBlock_3D_single_deform_LKA ---------------------------------
 int launch_cl_layernorm_fwd(const float *x, int x_planar, const float *pos, const float *w, const float *b, float *xt, float *xn, float *stats, int B, int N,
                             int C, float eps, hipStream_t st, int lo = 0, float *xn32 = nullptr);   // lo: the tensor that crosses into the D-LKA block (xn / g / e / ge) is bf16 storage; xn32: + its unrounded fp32 twin

@@ -253,6 +253,45 @@ int dlka_lka2d_attention_backward(const void *x, const dlka_lka2d_params *p, con
                                   void *workspace, size_t workspace_bytes,
                                   int B, int C, int H, int W, int dtype, void *stream);
 
+/* Parameters of the plain (non-deformable) 2-D LKA_Attention (2D/deformable_LKA/LKA.py:4-37; the same block as SpatialAttention /
+ * AttentionModule of 2D/networks/MaxViT_LKA_Decoder.py:53-85).  Unlike the deformable block, both depthwise convs carry a bias. */
+typedef struct dlka_lka2d_plain_params {
+    const void *proj_1_w, *proj_1_b;             /* [C][C][1][1], [C]                                             */
+    const void *conv0_w, *conv0_b;               /* [C][1][5][5], [C]     spatial_gating_unit.conv0                */
+    const void *conv_spatial_w, *conv_spatial_b; /* [C][1][7][7], [C]     spatial_gating_unit.conv_spatial (dil 3) */
+    const void *conv1_w, *conv1_b;               /* [C][C][1][1], [C]                                             */
+    const void *proj_2_w, *proj_2_b;             /* [C][C][1][1], [C]                                             */
+} dlka_lka2d_plain_params;
+
+typedef struct dlka_lka2d_plain_grads {
+    void *proj_1_w, *proj_1_b, *conv0_w, *conv0_b, *conv_spatial_w, *conv_spatial_b, *conv1_w, *conv1_b, *proj_2_w, *proj_2_b;
+} dlka_lka2d_plain_grads;
+
+/* Replaces  LKA_Attention.forward (LKA.py:30-37) incl. LKA.forward (:12-18):  y = proj_2(u * conv1(conv_spatial(conv0(u)))) + x,  u = GELU(proj_1 x).
+ * x, y: [B][C][H][W]; the block runs channels-last inside.  dtype DLKA_F32, or DLKA_BF16: x / y / grad_y / grad_x and the saved activations are bf16
+ * storage, the PARAMETERS and their gradients stay fp32 masters, accumulation is fp32.  Covered: C / 32 in {1, 2, 3, 4, 6, 8, 12}; for anything else the
+ * size queries return 0 and the calls DLKA_ERR_UNSUPPORTED (the modules then run operator by operator).  No float atomics: two identical calls give the
+ * same bits.  saved / workspace: as for dlka_lka2d_attention_*. */
+size_t dlka_lka2d_plain_saved_bytes(int B, int C, int H, int W, int dtype);
+size_t dlka_lka2d_plain_workspace_bytes(int B, int C, int H, int W, int dtype);
+int dlka_lka2d_plain_attention_forward(const void *x, const dlka_lka2d_plain_params *p, void *y,
+                                       void *saved, size_t saved_bytes, void *workspace, size_t workspace_bytes,
+                                       int B, int C, int H, int W, int dtype, void *stream);
+int dlka_lka2d_plain_attention_backward(const void *x, const dlka_lka2d_plain_params *p, const void *grad_y,
+                                        const void *saved, size_t saved_bytes,
+                                        void *grad_x, const dlka_lka2d_plain_grads *grads,
+                                        void *workspace, size_t workspace_bytes,
+                                        int B, int C, int H, int W, int dtype, void *stream);
+/* The block's two depthwise convs as single operators, channels-last (cl_dw2d.hip): x / out / grad_out / grad_x [B][H][W][C] (float, or bf16 storage
+ * with DLKA_BF16), weight / grad_weight [C][1][k][k] and bias / grad_bias [C] always fp32.  geom: D = kd = 1, stride 1, group = Cout = C, C % 32 == 0,
+ * (k, dilation, padding) = (5, 1, 2) or (7, 3, 9); anything else DLKA_ERR_UNSUPPORTED.  bias may be null.  backward: grad_x / grad_weight optional
+ * (null = not wanted), grad_bias needs grad_weight.  The weight and bias gradients are summed in a fixed order (no atomics). */
+size_t dlka_dwconv2d_cl_workspace(const dlka_conv_geom *geom, int dtype, int backward);
+int dlka_dwconv2d_forward_cl(const void *x, const void *weight, const void *bias, void *out, void *workspace, size_t workspace_bytes,
+                             const dlka_conv_geom *geom, int dtype, void *stream);
+int dlka_dwconv2d_backward_cl(const void *x, const void *weight, const void *grad_out, void *grad_x, void *grad_weight, void *grad_bias,
+                              void *workspace, size_t workspace_bytes, const dlka_conv_geom *geom, int dtype, void *stream);
+
 
 /* =======================================================================================
  * Channels-last (NDHWC / token layout) fast path — fp32, stride 1, same-size output
