@@ -123,16 +123,18 @@ def case_id(c):
 
 # ---- reference ----------------------------------------------------------------------------------------------------------------------------------------
 @functools.lru_cache(maxsize=None)
-def _host(B, C, dims, conv, with_bias):
-    """Seeded inputs (channels-last x and grad_out) and F.conv3d in float64: out and the three gradients."""
+def _host(B, C, dims, conv, with_bias, Cout=None, groups=None):
+    """Seeded inputs (channels-last x and grad_out) and F.conv3d in float64: out and the three gradients.  Depthwise (Cout = groups = C) unless told otherwise
+    (tests/dense_conv_cases.py: groups = 1); w ~ N(0, 1 / (taps * C / groups))."""
     k, p, d = conv
+    Cout, groups = Cout or C, groups or C
     gen = torch.Generator().manual_seed(8)
     x = torch.randn(B, C, *dims, generator=gen)
-    w = torch.randn(C, 1, *k, generator=gen) * (1.0 / (k[0] * k[1] * k[2]) ** 0.5)
-    b = torch.randn(C, generator=gen)
-    go = torch.randn(B, C, *dims, generator=gen)
+    w = torch.randn(Cout, C // groups, *k, generator=gen) * (1.0 / (C // groups * k[0] * k[1] * k[2]) ** 0.5)
+    b = torch.randn(Cout, generator=gen)
+    go = torch.randn(B, Cout, *dims, generator=gen)
     xr, wr, br = (t.double().requires_grad_(True) for t in (x, w, b))
-    out = F.conv3d(xr, wr, br if with_bias else None, 1, p, d, C)
+    out = F.conv3d(xr, wr, br if with_bias else None, 1, p, d, groups)
     out.backward(go.double())
     ref = {"out": parity.to_cl(out.detach()), "grad_input": parity.to_cl(xr.grad), "grad_weight": wr.grad, "grad_bias": go.double().sum((0, 2, 3, 4))}
     return parity.to_cl(x), w, (b if with_bias else None), parity.to_cl(go), ref
@@ -179,31 +181,44 @@ def _guarded_outputs(alloc):
 
 
 # ---- the check ----------------------------------------------------------------------------------------------------------------------------------------
-def run(dev, case, with_bias=True, trace=False):
-    """The two wrappers on guard-banded inputs with guarded outputs -> ({name: output on the CPU}, kernel names launched (None without the trace)).  The guard
-    cells are checked here; the values are not."""
-    x, w, b, go, _ = _host(case.B, case.C, case.dims, case.conv, with_bias)
-    k, p, d = case.conv
+def run_conv(dev, what, x, w, b, go, conv, groups, trace=False, out_planar=False, grad_out_planar=False, forward=True, need=(True, True, True)):
+    """The two wrappers on guard-banded inputs (x channels-last; go in the layout grad_out_planar names) with guarded outputs -> ({name: output on the CPU},
+    (kernel names the forward launched, kernel names the backward launched) — None without the trace).  forward / need: which of the four outputs to ask for.
+    The guard cells are checked here; the values are not."""
+    k, p, d = conv
     gx, ggo = GuardedInput(x, dev), GuardedInput(go, dev)
     assert gx.view.is_contiguous() and ggo.view.is_contiguous()
     wd, bd = w.to(dev), (None if b is None else b.to(dev))
     alloc = _GuardedAllocator()
     got = {}
 
-    def call():
+    def call_forward():
         with _guarded_outputs(alloc):
-            got["out"] = ops.conv3d_forward_cl(gx.view, wd, bd, p, d, case.C)
-            got["grad_input"], got["grad_weight"], got["grad_bias"] = ops.conv3d_backward_cl(gx.view, wd, ggo.view, p, d, case.C)
+            got["out"] = ops.conv3d_forward_cl(gx.view, wd, bd, p, d, groups, out_planar=out_planar)
 
-    names = parity.kernels_launched(call) if trace else call()
-    what = case_id(case)
-    assert len(alloc.made) == 4, f"{what}: {len(alloc.made)} outputs were allocated through the wrappers, expected 4"
+    def call_backward():
+        with _guarded_outputs(alloc):
+            grads = ops.conv3d_backward_cl(gx.view, wd, ggo.view, p, d, groups, grad_out_planar=grad_out_planar, need=need)
+            got.update({n: t for n, t, k_ in zip(("grad_input", "grad_weight", "grad_bias"), grads, need) if k_})
+
+    names = []
+    for fn in ([call_forward] if forward else []) + ([call_backward] if any(need) else []):
+        names.append(parity.kernels_launched(fn) if trace else fn())
+    asked = [n for n, k_ in zip(("out", "grad_input", "grad_weight", "grad_bias"), (forward,) + tuple(need)) if k_]
+    assert len(alloc.made) == len(asked), f"{what}: {len(alloc.made)} outputs were allocated through the wrappers, expected {len(asked)}"
     assert all(any(t.data_ptr() == g.view.data_ptr() for g in alloc.made) for t in got.values())
-    for g, name in zip(alloc.made, ("out", "grad_input", "grad_weight", "grad_bias")):
+    for g, name in zip(alloc.made, asked):
         g.assert_guards_untouched(f"{what} {name}")
     gx.assert_unchanged(f"{what} x")
     ggo.assert_unchanged(f"{what} grad_out")
-    return {n: t.detach().cpu().clone() for n, t in got.items()}, names
+    return {n: t.detach().cpu().clone() for n, t in got.items()}, (tuple(names) if trace else None)
+
+
+def run(dev, case, with_bias=True, trace=False):
+    """run_conv on a depthwise case -> ({name: output on the CPU}, kernel names launched (None without the trace))."""
+    x, w, b, go, _ = _host(case.B, case.C, case.dims, case.conv, with_bias)
+    got, names = run_conv(dev, case_id(case), x, w, b, go, case.conv, case.C, trace)
+    return got, (names[0] | names[1] if trace else None)
 
 
 def assert_members(case, names):
@@ -216,18 +231,28 @@ def assert_members(case, names):
     assert wg == [case.wgrad], f"{case_id(case)}: weight gradient ran {wg}, expected {case.wgrad}"
 
 
-def compare(case, got, with_bias=True, only=None):
-    """Every output against the float64 reference at the contract's bounds; all of them are measured and printed before the first failure is raised."""
-    ref = _host(case.B, case.C, case.dims, case.conv, with_bias)[4]
+def compare_with(what, got, ref, only=None, more=()):
+    """Every output against the float64 reference at the contract's bounds; all of them are measured and printed before the first failure is raised.
+    more: further checks, each a callable that asserts and returns (name, figure); they are measured and printed with the rest.  -> {name: figure}"""
     failures, figures = [], {}
     for name in only or ("out", "grad_input", "grad_weight", "grad_bias"):
         try:
-            figures[name] = assert_matches(f"{case_id(case)} {name}", got[name], ref[name], "f32", forward=(name == "out"))
+            figures[name] = assert_matches(f"{what} {name}", got[name], ref[name], "f32", forward=(name == "out"))
         except AssertionError as e:
             failures.append(str(e))
-    print(f"[{case_id(case)}] worst error: " + "  ".join(f"{n} {v:.2e}" for n, v in figures.items()) +
+    for check in more:
+        try:
+            name, figures[name] = check()
+        except AssertionError as e:
+            failures.append(str(e))
+    print(f"[{what}] worst error: " + "  ".join(f"{n} {v:.2e}" for n, v in figures.items()) +
           f"   (bounds: out {parity.FWD_ATOL:.0e} abs, gradients {parity.BWD_RTOL:.0e} of max |ref|)")
     assert not failures, "\n".join(failures)
+    return figures
+
+
+def compare(case, got, with_bias=True, only=None):
+    compare_with(case_id(case), got, _host(case.B, case.C, case.dims, case.conv, with_bias)[4], only)
 
 
 def single_op(dev, case, with_bias=True, trace=False, only=None):
