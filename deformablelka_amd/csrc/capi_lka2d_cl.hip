@@ -2,12 +2,13 @@
 // The 2-D D-LKA block (deformable_LKA_Attention, 2D/deformable_LKA/deformable_LKA.py:124-140) on the channels-last kernels.
 // x / y arrive in the reference's NCHW layout; the block transposes once on the way in and once on the way out (two passes of E
 // floats against ~100 E of work) and runs entirely in [B][H][W][C]:
-//   1x1 projections (+GELU / gate / residual epilogues)      cl_pointwise_kernel
+//   1x1 projections (+GELU / gate / residual epilogues)      cl_pointwise_kernel: the frame shared with the plain block, capi_lka2d_frame.h — the frame is changed THERE; here only the spatial stage and the buffers
 //   offset nets C -> 50 (5x5) and C -> 98 (7x7 dil 3)        cl_igemm_kernel (3-D kernel with D = kd = 1), planar offsets as torchvision wants them;
 //                                                            split-bf16 MFMA as in the 3-D block (forward fp32-equivalent three-term)
 //   the two depthwise deformable convs                       cl_ddw2d.hip
 // Supported: fp32, C / 32 in {1, 2, 3, 4, 6, 8, 12} (the net's 96 / 192 / 384 / 768 -> the first three; 768 never runs).
 // =========================================================================================================================
+#include "capi_lka2d_frame.h"
 #include "cl_fork.h"
 
 using namespace dlka;
@@ -16,66 +17,45 @@ namespace dlka {
 
 namespace {
 
-SameConv block_conv2d(int B, int C, int Cout, int H, int W, int k, int pad, int dil, int act_bf16 = 0)
-{
-    SameConv s;
-    s.act_bf16 = act_bf16;
-    s.B = B; s.D = 1; s.H = H; s.W = W; s.N = H * W; s.M = B * s.N; s.Cin = C; s.Cout = Cout; s.group = 1;
-    s.kd = 1; s.kh = s.kw = k; s.pd = 0; s.ph = s.pw = pad; s.dd = 1; s.dh = s.dw = dil; s.K = k * k;
-    return s;
-}
-
 // DLKA_BF16 (BASELINE.json config 2: "224x224 bf16 training, batch 24") is MIXED precision, like the 3-D block (TokGeoms): bf16 storage for x, y,
 // every saved activation and the intermediate gradients — except the chain that decides WHERE the two deformable convs sample:
 //     a = GELU(proj_1 x)  ->  o5 = offnet5(a)  ->  t1 = DDW5(a, o5)  ->  o7 = offnet7(t1)
 // runs on fp32 tensors (a32, t1_32: forward-only workspace) with the fp32 path's own kernels, so that both offset fields equal the fp32 block's to
 // fp32 rounding.  The bf16 copies of a / t1 (saved for the backward pass) ride in the producing kernels.
-struct Lka2dCl {
-    SameConv pw, off5, off7;      // activation-typed (bf16 on DLKA_BF16): the pointwise convs, the offset nets' backward passes
+struct Lka2dCl : Lka2dFrame {
+    SameConv off5, off7;          // activation-typed (bf16 on DLKA_BF16): the offset nets' backward passes
     SameConv off5_f, off7_f;      // the offset nets' FORWARD passes: fp32 input on both paths
-    size_t E, O5, O7, SB;
-    int B, C, H, W, bf;
-    Lka2dCl(int B_, int C_, int H_, int W_, int dtype = DLKA_F32) : B(B_), C(C_), H(H_), W(W_)
+    size_t O5, O7;
+    Lka2dCl(int B_, int C_, int H_, int W_, int dtype) : Lka2dFrame(B_, C_, H_, W_, dtype)
     {
-        bf = dtype == DLKA_BF16 ? 1 : 0;
-        SB = bf ? 2 : 4;
-        pw = block_conv2d(B, C, C, H, W, 1, 0, 1, bf);
         off5 = block_conv2d(B, C, 50, H, W, 5, 2, 1, bf);
         off7 = block_conv2d(B, C, 98, H, W, 7, 9, 3, bf);
         off5_f = block_conv2d(B, C, 50, H, W, 5, 2, 1, 0);
         off7_f = block_conv2d(B, C, 98, H, W, 7, 9, 3, 0);
-        E = (size_t)B * C * H * W; O5 = (size_t)B * 50 * H * W; O7 = (size_t)B * 98 * H * W;
+        O5 = (size_t)B * 50 * H * W; O7 = (size_t)B * 98 * H * W;
     }
-    size_t pw_floats() const { return (size_t)C * C; }
     size_t off5_floats() const { return dense_wp_floats(off5); }
     size_t off7_floats() const { return dense_wp_floats(off7); }
     size_t prep_floats() const { return 6 * (pw_floats() + 64) + 2 * (off5_floats() + 64) + 2 * (off7_floats() + 64) + (size_t)(25 + 49) * C + 256; }
-    size_t part_pw() const { return (cl_wgrad_part_floats_mode(pw.M, 1, C, C, 0) + 63) & ~(size_t)63; }
     size_t part_o5() const { return (cl_wgrad_part_floats_mode(pw.M, 25, 50, C, 0) + 63) & ~(size_t)63; }
     size_t part_o7() const { return (cl_wgrad_part_floats_mode(pw.M, 49, 98, C, 0) + 63) & ~(size_t)63; }
     size_t part_dw() const { return (cl_ddw2d_part_floats(pw.M, 49, C) + 63) & ~(size_t)63; }
     size_t part_floats() const { return 3 * part_pw() + part_o5() + part_o7() + part_dw(); }
 };
 
-struct Prep2d { float *pw_f[3], *pw_b[3], *o5_f, *o5_b, *o7_f, *o7_b, *dw5, *dw7; };
+struct Prep2d : FramePrep { float *o5_f, *o5_b, *o7_f, *o7_b, *dw5, *dw7; };
 
 int carve_prep2d(const Lka2dCl &G, float *base, Prep2d &t, const dlka_lka2d_params *p, hipStream_t st, bool fill)
 {
-    float *q = base;
-    auto take = [&](size_t n) { float *r = q; q += (n + 63) & ~(size_t)63; return r; };
-    for (int k = 0; k < 3; ++k) { t.pw_f[k] = take(G.pw_floats()); t.pw_b[k] = take(G.pw_floats()); }
+    PrepTake take{base};
+    PrepBatch pb;
+    memset(&pb, 0, sizeof(pb));
+    const int C = G.C;
+    carve_frame_prep(G, take, t, p, pb);
     t.o5_f = take(G.off5_floats()); t.o5_b = take(G.off5_floats());
     t.o7_f = take(G.off7_floats()); t.o7_b = take(G.off7_floats());
     t.dw5 = take((size_t)25 * G.C); t.dw7 = take((size_t)49 * G.C);
     if (!fill) return DLKA_OK;
-    PrepBatch pb;
-    memset(&pb, 0, sizeof(pb));
-    const int C = G.C;
-    const void *pw_w[3] = {p->proj_1_w, p->conv1_w, p->proj_2_w};
-    for (int k = 0; k < 3; ++k) {
-        add_job(pb, pw_w[k], t.pw_f[k], C, C, 1, C, C, 0);
-        add_job(pb, pw_w[k], t.pw_b[k], C, C, 1, C, C, 1);
-    }
     add_job(pb, p->conv0_offset_w, t.o5_f, 50, C, 25, C, 64, split_mode_flag(use_split(G.off5_f, true)));
     add_job(pb, p->conv0_offset_w, t.o5_b, 50, C, 25, 64, C, use_split(G.off5, false) ? 9 : 1);
     add_job(pb, p->conv_spatial_offset_w, t.o7_f, 98, C, 49, C, 128, split_mode_flag(use_split(G.off7_f, true)));
@@ -86,13 +66,13 @@ int carve_prep2d(const Lka2dCl &G, float *base, Prep2d &t, const dlka_lka2d_para
 }
 
 // ---- the block's buffer layouts: one record and ONE carve function per buffer and direction (Carver, cl_host.h) ---------------------------------
-// `saved`: activation-typed tensors, the two offset fields (fp32 on both paths), the prepared weights
-struct Lka2dSaved { float *xt, *h, *a, *t1, *t2, *g1, *m, *spare, *o5, *o7, *prep; };
+// `saved`: the frame's activation-typed tensors and one more nothing uses, the two offset fields (fp32 on both paths), the prepared weights
+struct Lka2dSaved : FrameSaved { float *spare, *o5, *o7, *prep; };
 Lka2dSaved carve_lka2d_saved(Carver &sv, const Lka2dCl &G)
 {
     Lka2dSaved S;
-    float **act[8] = {&S.xt, &S.h, &S.a, &S.t1, &S.t2, &S.g1, &S.m, &S.spare};
-    for (float **t : act) *t = (float *)sv.take(G.E * G.SB);
+    S.carve(sv, G);
+    S.spare = (float *)sv.take(G.E * G.SB);
     S.o5 = (float *)sv.take(G.O5 * 4); S.o7 = (float *)sv.take(G.O7 * 4);
     S.prep = (float *)sv.take(G.prep_floats() * 4);
     return S;
@@ -139,7 +119,7 @@ void fill_ddw(DwArgs2d &d, const Lka2dCl &G, int k, int pad, int dil)
 
 int lka2d_cl_supported(int B, int C, int H, int W, int dtype)
 {
-    if ((dtype != DLKA_F32 && dtype != DLKA_BF16) || B <= 0 || H <= 0 || W <= 0 || !cl_ddw2d_supported(C)) return 0;
+    if ((dtype != DLKA_F32 && dtype != DLKA_BF16) || B <= 0 || H <= 0 || W <= 0 || !frame_width_ok(C) || !cl_ddw2d_supported(C)) return 0;
     if (!(nt_ok(C) || C == 192 || C == 384)) return 0;   // the offset nets' data gradient has C columns: the igemm launcher's tile menu
     if ((long)B * H * W * C >= (1l << 29)) return 0;
     return dense_fwd_supported(block_conv2d(B, C, 50, H, W, 5, 2, 1)) ? 1 : 0;
@@ -178,13 +158,12 @@ int lka2d_cl_forward(const void *x_, const dlka_lka2d_params *p, void *y_, void 
     const Lka2dSaved S = carve_lka2d_saved(sv, G);
     const Lka2dFwdWs Wf = carve_lka2d_fwd_ws(cv, G);
     if (!sv.ok() || !cv.ok()) return DLKA_ERR_WORKSPACE;
-    float *xt = S.xt, *h = S.h, *a = S.a, *t1 = S.t1, *t2 = S.t2, *g1 = S.g1, *m = S.m, *o5 = S.o5, *o7 = S.o7, *prep = S.prep;
-    float *yt = Wf.yt, *a32 = Wf.a32, *t1_32 = Wf.t1_32;
+    float *a = S.a, *t1 = S.t1, *t2 = S.t2, *o5 = S.o5, *o7 = S.o7, *prep = S.prep;
+    float *a32 = Wf.a32, *t1_32 = Wf.t1_32;
     const float *N0 = nullptr;
     Prep2d PW;
     DLKA_TRY(carve_prep2d(G, prep, PW, p, st, true));
-    DLKA_TRY(launch_cl_transpose((const float *)x_, xt, B, C, G.pw.N, 1, st, bf));                                           // NCHW -> NHWC
-    DLKA_TRY(dense_forward(G.pw, xt, N0, (const float *)p->proj_1_b, h, 0, PW.pw_f[0], 1, nullptr, a, st, false, nullptr, bf ? a32 : nullptr));   // :135-136 (+GELU)
+    DLKA_TRY(frame_forward_head(G, PW, x_, p->proj_1_b, S, bf ? a32 : nullptr, st));                                           // :135-136 proj_1 (+GELU)
     const float *a_in = bf ? a32 : a;
     DLKA_TRY(dense_forward(G.off5_f, a_in, N0, (const float *)p->conv0_offset_b, o5, 1, PW.o5_f, 0, nullptr, nullptr, st));     // :28 offset_net
     DwArgs2d d;
@@ -196,9 +175,7 @@ int lka2d_cl_forward(const void *x_, const dlka_lka2d_params *p, void *y_, void 
     fill_ddw(d, G, 7, 9, 3);
     d.in = t1_in; d.off = o7; d.wp = PW.dw7; d.out = bf ? nullptr : t2; d.out_lo = bf ? t2 : nullptr;
     DLKA_TRY(launch_cl_ddw2d_fwd(d, st));
-    DLKA_TRY(dense_forward(G.pw, t2, N0, (const float *)p->conv1_b, g1, 0, PW.pw_f[1], 2, a, m, st));                          // :102-104 conv1 + gate
-    DLKA_TRY(dense_forward(G.pw, m, N0, (const float *)p->proj_2_b, yt, 0, PW.pw_f[2], 3, xt, nullptr, st));                   // :138-139 proj_2 + shortcut
-    return launch_cl_transpose(yt, (float *)y_, B, C, G.pw.N, 0, st, bf);
+    return frame_forward_tail(G, PW, p->conv1_b, p->proj_2_b, S, Wf.yt, y_, st);                                           // :102-104 conv1 + gate, :138-139 proj_2 + shortcut
 }
 
 int lka2d_cl_backward(const void *x_, const dlka_lka2d_params *p, const void *gy_, const void *saved, size_t saved_bytes, void *gx_, const dlka_lka2d_grads *gr,
@@ -211,13 +188,12 @@ int lka2d_cl_backward(const void *x_, const dlka_lka2d_params *p, const void *gy
     const Lka2dSaved S = carve_lka2d_saved(sv, G);
     const Lka2dBwdWs Wb = carve_lka2d_bwd_ws(cv, G);
     if (!sv.ok() || !cv.ok()) return DLKA_ERR_WORKSPACE;
-    const float *xt = S.xt, *h = S.h, *a = S.a, *t1 = S.t1, *t2 = S.t2, *g1 = S.g1, *m = S.m, *o5 = S.o5, *o7 = S.o7;
-    float *prep = S.prep;
+    const float *a = S.a, *t1 = S.t1, *o5 = S.o5, *o7 = S.o7;
     float *gyt = Wb.gyt, *gg1 = Wb.gg1, *ga1 = Wb.ga1, *gt2 = Wb.gt2, *gta = Wb.gta, *gt1 = Wb.gt1, *gaa = Wb.gaa, *gab = Wb.gab, *gh = Wb.gh;
     float *goff = Wb.goff, *goff5 = Wb.goff5, *part = Wb.part, *pad7 = Wb.pad7, *pad5 = Wb.pad5;
     const float *N0 = nullptr;
     Prep2d PW;
-    DLKA_TRY(carve_prep2d(G, prep, PW, p, st, false));
+    DLKA_TRY(carve_prep2d(G, S.prep, PW, p, st, false));
     // The two offset nets' WEIGHT gradients (the largest kernels of this pass after grad_input: C -> 98 / 50 channels over 49 / 25 taps) only read grad_offset and a saved
     // activation, and nothing before the finalisation reads their partial sums: they run on the library's internal stream (aux_ctx) beside the data chain — fork behind
     // each depthwise deformable conv's backward, one join in front of the finalisation.  DLKA_LKA2D_FORK=0: one stream (A/B; read per call).  Measured in
@@ -236,8 +212,8 @@ int lka2d_cl_backward(const void *x_, const dlka_lka2d_params *p, const void *gy
     auto join_gx = [&]() -> int { return forkgx ? lease.join(2) : DLKA_OK; };
     hipStream_t wst = fork2d ? lease.stream(1) : st;
     auto fork_to_aux = [&]() -> int { return fork2d ? lease.fork(1) : DLKA_OK; };
-    float *part_p2 = part, *part_c1 = part_p2 + G.part_pw(), *part_p1 = part_c1 + G.part_pw(), *part_o5 = part_p1 + G.part_pw();
-    float *part_o7 = part_o5 + G.part_o5(), *part_dw = part_o7 + G.part_o7();
+    float *const part_pw[3] = {part, part + G.part_pw(), part + 2 * G.part_pw()};   // proj_2, conv1, proj_1
+    float *part_o5 = part + 3 * G.part_pw(), *part_o7 = part_o5 + G.part_o5(), *part_dw = part_o7 + G.part_o7();
     FinalizeBatch fb;
     memset(&fb, 0, sizeof(fb));
     // bf16: the fp32 landing zone of a tap-split offset-net data gradient (converted into its bf16 destination afterwards): gg1 is dead by then for
@@ -251,10 +227,7 @@ int lka2d_cl_backward(const void *x_, const dlka_lka2d_params *p, const void *gy
     if (zb.overflow) return DLKA_ERR_WORKSPACE;
     DLKA_TRY(launch_zero_batch(zb, st));
     float *gxt = gt2;   // (gt2 is dead by the time the last projection's data gradient is written)
-    DLKA_TRY(launch_cl_transpose((const float *)gy_, gyt, B, C, G.pw.N, 1, st, bf));
-    // proj_2 data gradient with the gate's backward in the epilogue: gg1 = gm * a, ga1 = gm * g1
-    DLKA_TRY(dense_backward_data(G.pw, gyt, 0, N0, gg1, PW.pw_b[2], 4, a, st, g1, ga1));
-    DLKA_TRY(dense_backward_data(G.pw, gg1, 0, N0, gt2, PW.pw_b[1], 0, nullptr, st));                                           // conv1
+    DLKA_TRY(frame_backward_head(G, PW, S, gy_, gyt, gg1, ga1, gt2, st));
     // conv_spatial = DeformConv(7x7 dil 3): t2 = DDW7(t1, o7 = offnet7(t1))
     DwArgs2d d;
     fill_ddw(d, G, 7, 9, 3);
@@ -277,23 +250,9 @@ int lka2d_cl_backward(const void *x_, const dlka_lka2d_params *p, const void *gy
     DLKA_TRY(join_gx());
     if (bf && split5) DLKA_TRY(launch_zero(gh, G.E * 4, st));
     DLKA_TRY(dense_backward_data(G.off5, goff5, 1, N0, gab, PW.o5_b, 3, gaa, st, nullptr, nullptr, bf && split5, false, bf != 0, bf ? gh : nullptr));   // gab = gaa + offnet5^T goff
-    // a = GELU(h) feeds the gate and conv0: gh = (ga1 + gab) * gelu'(h)
-    if (bf) DLKA_TRY(launch_gelu_bwd_sum<bf16_t>((const bf16_t *)h, (const bf16_t *)ga1, (const bf16_t *)gab, (bf16_t *)gh, (long)G.E, st));
-    else DLKA_TRY(launch_gelu_bwd_sum<float>(h, ga1, gab, gh, (long)G.E, st));
-    {
-        WgradArgs jobs[3];
-        fill_pw_wgrad(jobs[0], G.pw, m, gyt, part_p2);
-        fill_pw_wgrad(jobs[1], G.pw, t2, gg1, part_c1);
-        fill_pw_wgrad(jobs[2], G.pw, xt, gh, part_p1);
-        float *const gws[3] = {(float *)gr->proj_2_w, (float *)gr->conv1_w, (float *)gr->proj_1_w};
-        float *const gbs[3] = {(float *)gr->proj_2_b, (float *)gr->conv1_b, (float *)gr->proj_1_b};
-        DLKA_TRY(launch_cl_wgrad_pw3(jobs, gws, gbs, st, &fb.j[fb.njobs]));
-        fb.njobs += 3;
-    }
+    DLKA_TRY(frame_backward_wgrads(G, S, gr, gyt, gg1, ga1, gab, gh, part_pw, fb, st));
     if (fork2d) DLKA_TRY(lease.join(1));   // the folds read the offset nets' partial sums
-    DLKA_TRY(launch_cl_wgrad_finalize(fb, st));
-    DLKA_TRY(dense_backward_data(G.pw, gh, 0, N0, gxt, PW.pw_b[0], 3, gyt, st));                                                // gx = P1^T gh + gy
-    return launch_cl_transpose(gxt, (float *)gx_, B, C, G.pw.N, 0, st, bf);
+    return frame_backward_finish(G, PW, fb, gyt, gh, gxt, gx_, st);
 }
 
 }  // namespace dlka

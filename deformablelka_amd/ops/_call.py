@@ -38,6 +38,20 @@ def _require_input_dtype(input, **named):
             raise RuntimeError(f"expected `{name}` to have the dtype of `input` ({input.dtype}), got {t.dtype}")
 
 
+def require_fp32_params(what, x, **named):
+    """bfloat16 is an ACTIVATION dtype of the channels-last and token-layout blocks: the library reads every parameter as float32 whatever x is.  A parameter
+    of another dtype is refused before any launch."""
+    for name, t in named.items():
+        if t is not None and t.dtype != torch.float32:
+            raise RuntimeError(f"{what}: `{name}` must be float32 (bfloat16 is the storage of the activations only), got {t.dtype} next to {x.dtype} activations")
+
+
+def lka2d_width_ok(C: int) -> bool:
+    """Widths the channels-last 2-D attention blocks cover, plain and deformable, in float32 and with bfloat16 activations alike: C / 32 in
+    {1, 2, 3, 4, 6, 8, 12} (csrc/capi_lka2d_frame.h: frame_width_ok)."""
+    return C % 32 == 0 and C // 32 in (1, 2, 3, 4, 6, 8, 12)
+
+
 # ---- dtype tables of the pipeline families: torch dtype -> the library's code -------------------------------------------------------------
 _SD_DTYPES = {torch.uint8: L.DLKA_SD_U8, torch.bool: L.DLKA_SD_U8, torch.int16: L.DLKA_SD_I16, torch.int32: L.DLKA_SD_I32, torch.int64: L.DLKA_SD_I64}
 _RS_DTYPES = {torch.float32: L.DLKA_F32, torch.float64: L.DLKA_F64}

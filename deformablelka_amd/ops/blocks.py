@@ -11,26 +11,23 @@ from typing import Sequence
 import torch
 
 from .. import _lib as L
-from ._call import Block, block_backward, block_backward_args, block_forward, call, ptr_struct, saved_view, side_stream_phases
+from ._call import (Block, block_backward, block_backward_args, block_forward, call, lka2d_width_ok, ptr_struct, require_fp32_params, saved_view,
+                    side_stream_phases)
+
+lka2d_bf16_supported = lka2d_width_ok   # widths the DLKA_BF16 2-D block covers: the channels-last fast path's
 
 
-def lka2d_bf16_supported(C: int) -> bool:
-    """Widths the DLKA_BF16 2-D block covers (channels-last fast path: C / 32 in {1, 2, 3, 4, 6, 8, 12})."""
-    return C % 32 == 0 and C // 32 in (1, 2, 3, 4, 6, 8, 12)
-
-
-def _fp32_param(t):
-    """Parameters of the token-layout block are fp32 masters whatever the activation dtype is."""
-    if t.dtype != torch.float32:
-        raise RuntimeError(f"the token-layout D-LKA block keeps its parameters in float32 (bf16 is an ACTIVATION dtype); got {t.dtype}")
-    return t.contiguous()
+def _fp32_params(what, fields, x, params):
+    """Parameters are fp32 masters whatever the activation dtype is."""
+    require_fp32_params(what, x, **dict(zip(fields, params)))
+    return [t.contiguous() for t in params]
 
 
 def _lka2d_params(x, params):
     if x.dtype == torch.bfloat16:   # DLKA_BF16: bf16 ACTIVATIONS, fp32 master parameters (include/dlka.h)
         if not lka2d_bf16_supported(int(x.shape[1])):
             raise RuntimeError(f"deformable_LKA_Attention with bfloat16 activations needs C / 32 in {{1,2,3,4,6,8,12}}, got C={int(x.shape[1])}")
-        return [_fp32_param(t) for t in params]
+        return _fp32_params("deformable_LKA_Attention", L.LKA2D_FIELDS, x, params)
     return [t.contiguous() for t in params]
 
 
@@ -40,7 +37,8 @@ def _planar_extents(x, dims):
 
 _LKA3D = Block("lka3d_attention", "lka3d", "", L.Lka3dPtrs, L.LKA3D_FIELDS, lambda x, params: [t.contiguous() for t in params], _planar_extents, -4, False)
 _LKA2D = Block("lka2d_attention", "lka2d", "", L.Lka2dPtrs, L.LKA2D_FIELDS, _lka2d_params, _planar_extents, -4, True)
-_TOKENS = Block("lka3d_attention_tokens", "lka3d_tokens", "_v", L.Lka3dPtrs, L.LKA3D_FIELDS, lambda x, params: [_fp32_param(t) for t in params],
+_TOKENS = Block("lka3d_attention_tokens", "lka3d_tokens", "_v", L.Lka3dPtrs, L.LKA3D_FIELDS,
+                lambda x, params: _fp32_params("the token-layout D-LKA block", L.LKA3D_FIELDS, x, params),
                 lambda x, dims: (int(x.shape[0]), int(x.shape[2]), *(int(v) for v in dims)), -8, True)
 
 

@@ -8,23 +8,17 @@ from typing import Sequence
 import torch
 
 from .. import _lib as L
-from ._call import WS, Block, _pair, block_backward, block_forward, call_ws
+from ._call import WS, Block, _pair, block_backward, block_forward, call_ws, require_fp32_params
+from ._call import lka2d_width_ok as supported   # noqa: F401  (widths the fused block covers, in float32 and with bfloat16 activations alike)
 
 ACTIVATION_DTYPES = (torch.float32, torch.bfloat16)
 
 
-def supported(C: int) -> bool:
-    """Widths the fused block covers, in float32 and with bfloat16 activations alike: C / 32 in {1, 2, 3, 4, 6, 8, 12}."""
-    return C % 32 == 0 and C // 32 in (1, 2, 3, 4, 6, 8, 12)
-
-
 def _fp32_params(what, x, **named):
-    """bfloat16 is an ACTIVATION dtype here: the library reads every parameter as float32 whatever x is.  Anything else is refused before a launch."""
+    """float32 or bfloat16 activations next to float32 parameters; anything else is refused before a launch."""
     if x.dtype not in ACTIVATION_DTYPES:
         raise RuntimeError(f"{what}: float32 or bfloat16 activations, got {x.dtype}")
-    for name, t in named.items():
-        if t is not None and t.dtype != torch.float32:
-            raise RuntimeError(f"{what}: `{name}` must be float32 (bfloat16 is the storage of the activations only), got {t.dtype} next to {x.dtype} activations")
+    require_fp32_params(what, x, **named)
 
 
 def _block_params(x, params):

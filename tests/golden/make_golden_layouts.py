@@ -4,7 +4,8 @@
 
 The table is the contract of the blocks' `saved` / `workspace` layouts: DLKABlockStack's flat buffers and tests/pw_chain.py compute positions from these
 values, and memory use is behaviour.  tests/test_layouts_emu.py asserts that the tree reproduces every value exactly.  Regenerate only when a layout is
-changed on purpose.
+changed on purpose.  (The plain 2-D block's and dlka_dwconv2d_cl_workspace's rows were recorded from the commit before csrc/capi_lka2d_frame.h existed;
+the rows already recorded did not move.)
 
 File format: {"grid": GRID, "values": {export name: [numbers]}}.  An export's numbers are what its calls returned (return value, then its output values), in
 the order collect() makes the calls: that order is a function of GRID alone, which the file repeats so that a changed grid cannot be mistaken for a changed
@@ -28,12 +29,14 @@ GRID = {
     "widths2d": [96, 384, 40],
     "planes": [[56, 56], [14, 14], [11, 11], [0, 11]],
     "lka2d_general": [0, 1],                                         # dlka_lka2d_force_general, for dlka_lka2d_saved_offsets (the sizes do not depend on it)
+    "dw2d_members": [[5, 1, 2], [7, 3, 9]],                          # (k, dilation, padding) of dlka_dwconv2d_cl_workspace, forward and backward
 }
 
 
 def collect(lib):
     """lib: a ctypes library bound by deformablelka_amd._lib.bind.  Returns {export: [(arguments and switches, [values]), ...]}; leaves DLKA_DW_LDS unset and
     the 2-D path switch as it found it."""
+    from deformablelka_amd._lib import ConvGeom
     rows = {}
 
     def rec(name, args, *vals):
@@ -81,6 +84,12 @@ def collect(lib):
                                 rc = lib.dlka_lka2d_saved_offsets(*a, o, ctypes.byref(eb))
                                 rec("dlka_lka2d_saved_offsets", a + (lds, general), rc, o[0], o[1], eb.value)
                             lib.dlka_lka2d_force_general(0)
+                            rec("dlka_lka2d_plain_saved_bytes", a + (lds,), lib.dlka_lka2d_plain_saved_bytes(*a))
+                            rec("dlka_lka2d_plain_workspace_bytes", a + (lds,), lib.dlka_lka2d_plain_workspace_bytes(*a))
+                            for (k, dil, pad) in GRID["dw2d_members"]:
+                                g = ConvGeom(B, C, 1, H, W, C, 1, k, k, 1, 1, 1, 0, pad, pad, 1, dil, dil, C, 1, 64)
+                                for backward in (0, 1):
+                                    rec("dlka_dwconv2d_cl_workspace", a + (k, backward, lds), lib.dlka_dwconv2d_cl_workspace(ctypes.byref(g), dt, backward))
     finally:
         os.environ.pop("DLKA_DW_LDS", None)
         lib.dlka_env_refresh()

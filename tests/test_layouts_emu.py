@@ -189,3 +189,20 @@ def test_lka2d_block_in_buffers_of_exactly_the_queried_size(guarded, monkeypatch
         assert bool(torch.isfinite(t).all())
     refused(guarded, monkeypatch, "lka2d", lambda: ops.lka2d_attention_forward(x, params), lambda short: ops.lka2d_attention_backward(x, params, gy, short),
             saved.numel())
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+def test_lka2d_plain_block_in_buffers_of_exactly_the_queried_size(guarded, monkeypatch, dtype):
+    from deformablelka_amd.ops import lka2d_plain
+    from tests.lka2d_plain_cases import _attention_state
+    gen = torch.Generator().manual_seed(0)
+    params = list(_attention_state(32, 0).values())
+    x, gy = (torch.randn(1, 32, 7, 6, generator=gen).to(dtype) for _ in range(2))
+    what = f"lka2d_plain {dtype}"
+    y, saved = lka2d_plain.attention_forward(x, params)
+    gx, grads = lka2d_plain.attention_backward(x, params, gy, saved)
+    assert guarded.verify(what) == 3
+    for t in [y, gx, *grads]:
+        assert bool(torch.isfinite(t.float()).all())
+    refused(guarded, monkeypatch, what, lambda: lka2d_plain.attention_forward(x, params),
+            lambda short: lka2d_plain.attention_backward(x, params, gy, short), saved.numel())
