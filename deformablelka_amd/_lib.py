@@ -38,6 +38,7 @@ DLKA_PREP_C_MAX, DLKA_PREP_REC = 32, 8                                  # includ
 DLKA_PREP_CT, DLKA_PREP_CT2, DLKA_PREP_NONCT = 0, 1, 2
 DLKA_ZOOM2D_I16, DLKA_ZOOM2D_K_MAX, DLKA_ZOOM2D_OUTSIDE = 3, 255, -2 ** 31   # include/dlka.h: dlka_zoom2d_*
 DLKA_OPTIM_TENSORS_PER_LAUNCH, DLKA_OPTIM_CHUNK = 120, 4096               # include/dlka.h: dlka_optim_*
+DLKA_OPTIM_ADAM_TENSORS_PER_LAUNCH, DLKA_OPTIM_ADAM_TICK_PER_LAUNCH = 80, 448
 DLKA_LOAD_B_MAX, DLKA_LOAD_K_MAX = 32, 32                                  # include/dlka.h: dlka_load_*
 DLKA_LOAD_CONSTANT, DLKA_LOAD_EDGE = 0, 1
 DLKA_LOAD_F32, DLKA_LOAD_I32 = 0, 1
@@ -134,6 +135,13 @@ class OptimDesc(ctypes.Structure):
     """``dlka_optim_desc`` (include/dlka.h)."""
     _fields_ = [("n_tensors", c_int32), ("dtype", c_int32), ("nesterov", c_int32), ("has_momentum", c_int32), ("clip", c_int32),
                 ("momentum", ctypes.c_float), ("weight_decay", ctypes.c_float), ("max_norm", ctypes.c_float), ("lr_index", c_int32)]
+
+
+class OptimAdamDesc(ctypes.Structure):
+    """``dlka_optim_adam_desc`` (include/dlka.h)."""
+    _fields_ = [("n_tensors", c_int32), ("dtype", c_int32), ("decoupled", c_int32), ("amsgrad", c_int32), ("clip", c_int32),
+                ("beta1", ctypes.c_double), ("beta2", ctypes.c_double), ("eps", ctypes.c_double), ("weight_decay", ctypes.c_double),
+                ("max_norm", ctypes.c_float), ("lr_index", c_int32)]
 
 
 class LoadSample(ctypes.Structure):
@@ -350,6 +358,9 @@ SIGNATURES = {
     "dlka_optim_grad_norm": (c_int, [_PTRS, _I64S, c_int64, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
     "dlka_optim_scale": (c_int, [_PTRS, _I64S, c_int64, c_int, c_void_p, ctypes.c_float, c_void_p]),
     "dlka_optim_sgd_step": (c_int, [_PTRS, _PTRS, _PTRS, _I64S, _OPD, c_void_p, c_void_p, c_void_p]),
+    "dlka_optim_adam_workspace_bytes": (c_size_t, [c_int64]),
+    "dlka_optim_adam_step": (c_int, [_PTRS, _PTRS, _PTRS, _PTRS, _PTRS, _PTRS, _I64S, POINTER(OptimAdamDesc), c_void_p, c_void_p, c_void_p, c_size_t,
+                                     c_void_p]),
     "dlka_optim_launch_count": (ctypes.c_long, []),
     "dlka_load_crop_batch": (c_int, [POINTER(LoadCropDesc), c_void_p, c_void_p, c_void_p]),
     "dlka_load_counts_workspace_bytes": (c_size_t, [POINTER(LoadClassesDesc)]),

@@ -42,17 +42,34 @@ def set_wgrad_overlap(net: nn.Module, on: bool) -> int:
     return n
 
 
-def initialize_optimizer(net: nn.Module, initial_lr: float = 1e-2, weight_decay: float = 3e-5, fused=None):
-    """:200-205: SGD, momentum 0.99, Nesterov; the reference drives the learning rate with nnU-Net's poly schedule.
+def initialize_optimizer(net: nn.Module, initial_lr: float = None, weight_decay: float = None, fused=None, *, algorithm: str = "sgd"):
+    """:200-205: SGD, momentum 0.99, Nesterov (``initial_lr`` 1e-2, ``weight_decay`` 3e-5); the reference drives the learning rate with nnU-Net's
+    poly schedule.
     ``fused`` (default: on when every parameter is a floating-point GPU tensor) selects torch.optim.SGD's single-pass implementation — the same update,
     weight decay, momentum, Nesterov step and parameter write in one kernel per tensor list instead of the four ``_foreach`` passes over the 42 M parameters
     (0.9 ms of a 30 ms iteration).  ``fused="hip"`` returns ``optim.SGD`` instead: the clip and the step on the library's own multi-tensor kernels, the
-    learning rate in device memory (``run_iteration`` and ``GraphedIteration`` recognise it)."""
+    learning rate in device memory (``run_iteration`` and ``GraphedIteration`` recognise it).
+    ``algorithm`` (with ``fused="hip"`` only) selects the other trainers' rows on the same kernels: ``"adam"``, the 3-D base trainers'
+    ``optim.Adam(3e-4, weight_decay=3e-5, amsgrad=True)`` (Trainer_synapse.py:270-273, Trainer_acdc.py:269-272; they run it under
+    ``ReduceLROnPlateau``, which writes ``param_groups`` as any torch scheduler does); ``"adamw"``, the 2-D plain-LKA trainer's
+    ``optim.AdamW(0.05, weight_decay=1e-4)`` (2D/trainer_MaxViT_LKA.py:114; base_lr: the 2-D train scripts' default).  ``initial_lr`` and
+    ``weight_decay`` left at ``None`` take the selected row's values."""
+    rows = {"sgd": (1e-2, 3e-5), "adam": (3e-4, 3e-5), "adamw": (0.05, 1e-4)}
+    if algorithm not in rows:
+        raise ValueError(f"initialize_optimizer: algorithm must be 'sgd', 'adam' or 'adamw', got {algorithm!r}")
+    if algorithm != "sgd" and fused != "hip":
+        raise ValueError(f"initialize_optimizer: algorithm={algorithm!r} is built on the library's kernels only, pass fused='hip'")
+    initial_lr = rows[algorithm][0] if initial_lr is None else initial_lr
+    weight_decay = rows[algorithm][1] if weight_decay is None else weight_decay
     params = list(net.parameters())
     if isinstance(fused, str):
         if fused != "hip":
             raise ValueError(f"initialize_optimizer: fused must be None, a bool or 'hip', got {fused!r}")
         from . import optim
+        if algorithm == "adam":
+            return optim.Adam(params, initial_lr, weight_decay=weight_decay, amsgrad=True)
+        if algorithm == "adamw":
+            return optim.AdamW(params, initial_lr, weight_decay=weight_decay)
         return optim.SGD(params, initial_lr, momentum=0.99, nesterov=True, weight_decay=weight_decay)
     if fused is None:
         fused = bool(params) and all(p.is_cuda and p.is_floating_point() for p in params)

@@ -1032,7 +1032,7 @@ int dlka_zoom2d_argmax(const void *logits, uint8_t *labels, const dlka_zoom2d_de
 long dlka_zoom2d_launch_count(void);
 
 /* =======================================================================================
- * The trainers' optimizer step: gradient clipping + SGD, learning rate in device memory — csrc/cl_optim.hip
+ * The trainers' optimizer step: gradient clipping + SGD / Adam / AdamW, learning rate in device memory — csrc/cl_optim.hip
  * =======================================================================================
  * Every reference trainer ends its iteration with SGD: the 3-D trainer with momentum 0.99, Nesterov, weight decay 3e-5
  * (3D/d_lka_former/training/network_training/d_lka_former_trainer_synapse.py:197-205) after clip_grad_norm_(parameters, 12) (:291-309), its
@@ -1073,6 +1073,40 @@ int dlka_optim_grad_norm(const void *const *grads, const int64_t *counts, int64_
 int dlka_optim_scale(void *const *grads, const int64_t *counts, int64_t n, int dtype, const float *norm_dev, float max_norm, void *stream);
 int dlka_optim_sgd_step(void *const *params, const void *const *grads, void *const *bufs, const int64_t *counts, const dlka_optim_desc *d,
                         const float *lr_dev, const float *norm_dev, void *stream);
+/* Adam and AdamW on the same tables and partition — what the other reference trainers step with: the 2-D plain-LKA trainer with
+ * optim.AdamW(lr, weight_decay=1e-4) and a poly rate written after every iteration (2D/trainer_MaxViT_LKA.py:114, :145-147), the 3-D base
+ * trainers with Adam(3e-4, weight_decay=3e-5, amsgrad=True) (3D/d_lka_former/training/network_training/Trainer_synapse.py:270-273,
+ * Trainer_acdc.py:269-272).
+ *
+ * dlka_optim_adam_step  two kinds of launch.  (1) The tick, one workgroup per DLKA_OPTIM_ADAM_TICK_PER_LAUNCH tensors: steps[i][0] += 1 (one
+ *                       float32 count per tensor in device memory, torch's `capturable` convention, exact to 2^24 steps) and, with the new
+ *                       t, workspace[2 i] = 1 - beta1^t, workspace[2 i + 1] = sqrt(1 - beta2^t), formed in float64 and stored as float32.
+ *                       (2) The update, up to DLKA_OPTIM_ADAM_TENSORS_PER_LAUNCH tensors a launch, per element in torch.optim.Adam's order:
+ *                         g_c = clip ? g * coef : g                                 (coef as in dlka_optim_scale from norm_dev[0], max_norm)
+ *                         decoupled (AdamW): p = p * (1 - lr * weight_decay);  else (weight_decay != 0): g_c = g_c + weight_decay * p
+ *                         m = m + (g_c - m) * (1 - beta1);   v = beta2 * v + (1 - beta2) * (g_c * g_c)
+ *                         amsgrad: vmax = max(vmax, v) (a NaN stays), w = vmax;  else w = v (max_exp_avg_sq may be NULL)
+ *                         p = p - ((lr / workspace[2 i]) * m) / (sqrt(w) / workspace[2 i + 1] + eps),   lr = lr_dev[lr_index]
+ *                       every product, quotient and sum rounded to float32 on its own; 1 - beta1 and 1 - beta2 are formed in float64.  No
+ *                       workgroup of the update writes a count or reads the host; the gradient is NOT written back.  A captured call
+ *                       advances the counts at every replay.  exp_avg, exp_avg_sq, max_exp_avg_sq start as zeros, the counts as 0.
+ *                       `workspace`: dlka_optim_adam_workspace_bytes(n_tensors) bytes, 4-byte aligned, the caller's until the stream has
+ *                       run the call.  Every listed tensor needs a count address, a zero-element one too (torch counts its steps).
+ * Return codes as above: DLKA_ERR_NULL (a table, the descriptor, lr_dev, norm_dev with clip, max_exp_avg_sq with amsgrad), DLKA_ERR_SHAPE
+ * (n_tensors < 0, a negative count or lr_index, a beta outside [0, 1), eps or weight_decay below 0), DLKA_ERR_DTYPE, DLKA_ERR_UNSUPPORTED,
+ * DLKA_ERR_NULL (a NULL address of a tensor with elements, a NULL count address), DLKA_ERR_WORKSPACE.  n_tensors == 0: DLKA_OK, no launch. */
+#define DLKA_OPTIM_ADAM_TENSORS_PER_LAUNCH 80
+#define DLKA_OPTIM_ADAM_TICK_PER_LAUNCH 448
+typedef struct dlka_optim_adam_desc {
+    int32_t n_tensors, dtype, decoupled, amsgrad, clip;
+    double beta1, beta2, eps, weight_decay;   /* torch holds them as doubles; 1 - beta is formed before the rounding to float32 */
+    float max_norm;
+    int32_t lr_index;
+} dlka_optim_adam_desc;
+size_t dlka_optim_adam_workspace_bytes(int64_t n_tensors);
+int dlka_optim_adam_step(void *const *params, const void *const *grads, void *const *exp_avg, void *const *exp_avg_sq, void *const *max_exp_avg_sq,
+                         void *const *steps, const int64_t *counts, const dlka_optim_adam_desc *d, const float *lr_dev, const float *norm_dev,
+                         void *workspace, size_t workspace_bytes, void *stream);
 /* Diagnostics: kernel launches so far (this process) of the entries above. */
 long dlka_optim_launch_count(void);
 
