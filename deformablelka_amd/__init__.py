@@ -34,6 +34,11 @@ _ALIAS_DEFAULT = ("D3D", "functions.deform_conv_func", "modules.deform_conv")
 # and the modules those files import DeformConvFunction from (synapse/deform_conv.py:13, pancreas deform_conv.py)
 NET_ALIASES = ("d_lka_former.network_architecture.synapse.deform_conv", "d_lka_former.network_architecture.synapse.deform_conv_func",
                "networks.d_lka_former.deform_conv", "networks.d_lka_former.deform_conv_func")
+# the modules the reference's run_training.py looks its ``--trans_block`` class up in (3D/d_lka_former/run/run_training.py:124-128), Synapse then ACDC,
+# and the pancreas net's.  They stay the reference's own files (its nets import a dozen ablation blocks from them): install_reference_blocks() imports
+# them and rebinds only the block classes this package has
+BLOCK_ALIASES = ("d_lka_former.network_architecture.synapse.transformerblock", "d_lka_former.network_architecture.acdc.transformerblock",
+                 "networks.d_lka_former.transformerblock")
 
 
 def install_reference_aliases(names=_ALIAS_DEFAULT, torchvision_ops=False):
@@ -85,3 +90,27 @@ def install_reference_aliases(names=_ALIAS_DEFAULT, torchvision_ops=False):
             torchvision.ops = tvo
             sys.modules["torchvision"], sys.modules["torchvision.ops"] = torchvision, tvo
         tvo.DeformConv2d, tvo.deform_conv2d = tv_ops.DeformConv2d, tv_ops.deform_conv2d
+
+
+BLOCK_NAMES = ("EPA", "TransformerBlock", "TransformerBlock_3D_single_deform_LKA")
+
+
+def install_reference_blocks(names=BLOCK_ALIASES):
+    """Import the reference's OWN ``transformerblock`` modules (``BLOCK_ALIASES``; the reference tree must be on ``sys.path`` and the deformable-conv leaves
+    registered: ``install_reference_aliases(names=("D3D",) + NET_ALIASES, torchvision_ops=True)`` first) and rebind ``BLOCK_NAMES`` on them to this package's
+    classes — ``deformablelka_amd.acdc``'s for the ACDC module, ``deformablelka_amd.transformerblock``'s for the others.  Everything else in those modules (the
+    ablation blocks the reference's ``model_components.py`` imports by name) stays the reference's.  Call it BEFORE importing the reference's net files:
+    ``from ...transformerblock import TransformerBlock`` and ``run_training.py``'s ``getattr(module, args.trans_block)`` then both yield the HIP-backed class.
+    Returns the modules."""
+    import importlib
+    from . import acdc, transformerblock
+    out = []
+    for n in names:
+        if n not in BLOCK_ALIASES:
+            raise KeyError(f"install_reference_blocks: unknown import path {n!r}")
+        m = importlib.import_module(n)
+        src = acdc if ".acdc." in n else transformerblock
+        for name in BLOCK_NAMES:
+            setattr(m, name, getattr(src, name))
+        out.append(m)
+    return out

@@ -378,6 +378,11 @@ SIGNATURES = {
     "dlka_dstats_select": (c_int, [c_void_p, c_int64, _I64S, c_int32, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
     "dlka_dstats_unique_labels": (c_int, [c_void_p, _DSD, c_void_p, c_void_p]),
     "dlka_dstats_launch_count": (ctypes.c_long, []),
+    "dlka_epa_supported": (c_int, [c_int] * 4),
+    "dlka_epa_saved_bytes": (c_size_t, [c_int] * 3),
+    "dlka_epa_workspace_bytes": (c_size_t, [c_int] * 6),
+    "dlka_epa_attention_forward": (c_int, [c_void_p] * 7 + [ctypes.c_float] + [c_void_p] * 4 + [c_size_t] + [c_int] * 6 + [c_void_p]),
+    "dlka_epa_attention_backward": (c_int, [c_void_p] * 7 + [ctypes.c_float] + [c_void_p] * 9 + [c_size_t] + [c_int] * 6 + [c_void_p]),
     "dlka_trace_start": (c_int, [c_int, c_void_p]),
     "dlka_trace_mark": (c_int, [c_void_p]),
     "dlka_trace_stop": (c_int, []),

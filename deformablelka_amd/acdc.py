@@ -33,3 +33,14 @@ class LKA_Attention3d_deform(_tb.LKA_Attention3d_deform):
 class TransformerBlock_3D_single_deform_LKA(_tb.TransformerBlock_3D_single_deform_LKA):
     """acdc/transformerblock.py:140-206."""
     EPA_BLOCK = LKA_Attention3d_deform
+
+
+class EPA(_tb.EPA):
+    """acdc/transformerblock.py:70-137: ``E`` and ``F`` are two layers."""
+    SHARED_PROJECTION = False
+
+
+class TransformerBlock(_tb.TransformerBlock):
+    """acdc/transformerblock.py:6-67: a second ``UnetResBlock`` (``conv52``) behind ``conv51``."""
+    EPA_BLOCK = EPA
+    EXTRA_RES_BLOCK = True

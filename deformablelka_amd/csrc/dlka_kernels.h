@@ -145,4 +145,23 @@ int launch_cl_bn_bwd(const float *g, const float *gmask, const float *x, const f
                      const float *gres_add, float *gw, float *gb, long M, long N, int C, float slope, int training, hipStream_t st, bool zeroed = false);
 int launch_cl_channel_scale(const float *x, const float *mask, float *y, int B, long N, int C, hipStream_t st);
 
+// ---- cl_epa.hip: the UNETR++ efficient paired attention on the qkvv tensor [B][N][4][heads][D] ----
+int epa_gram_chunks(int N);
+int epa_token_tiles(int N);
+size_t epa_gram_part_floats(int B, int N, int heads, int D);
+size_t epa_token_part_floats(int B, int N, int heads, int D, int P);
+int launch_cl_epa_gram(const float *X, long xb, int xs, int xo, const float *Y, long yb, int ys, int yo, float *part, int B, int N, int heads, int D, bool sumsq,
+                       hipStream_t st);
+int launch_cl_epa_finish(const float *part, const float *temperature, const float *temperature2, const float *m1, float *nrm, float *ghat, float *a_soft,
+                         float *a_mask, int B, int N, int C, int heads, hipStream_t st);
+int launch_cl_epa_apply(const float *qkvv, const float *kp, const float *vp, const float *a_mask, const float *nrm, const unsigned char *m2, float m2_scale,
+                        float *x_sa, float *x_ca, int B, int N, int C, int heads, int P, hipStream_t st);
+int launch_cl_epa_bwd_tokens(const float *qkvv, const float *kp, const float *vp, const float *nrm, const float *temperature2, const unsigned char *m2,
+                             float m2_scale, const float *g_xsa, float *g_qkvv, float *part, int B, int N, int C, int heads, int P, hipStream_t st);
+int launch_cl_epa_bwd_finish(const float *gpart, const float *tpart, const float *kp, const float *temperature, const float *temperature2, const float *m1,
+                             const float *a_soft, const float *ghat, const float *nrm, float *g_kp, float *g_vp, float *g_t, float *g_t2, float *dgh, float *proj,
+                             int B, int N, int C, int heads, int P, hipStream_t st);
+int launch_cl_epa_bwd_apply(const float *qkvv, const float *a_mask, const float *dgh, const float *nrm, const float *proj, const float *g_xca, float *g_qkvv, int B,
+                            int N, int C, int heads, hipStream_t st);
+
 }  // namespace dlka

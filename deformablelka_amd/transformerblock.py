@@ -349,3 +349,223 @@ class TransformerBlock_3D_single_deform_LKA(nn.Module):
         y = y.view(B, H, W, D, C).permute(0, 4, 1, 2, 3)
         keep = self.keep_channels_last if keep_channels_last is None else keep_channels_last
         return y if keep else y.contiguous()
+
+
+# ---- the UNETR++ block: EPA ("efficient paired attention") and the TransformerBlock around it ------------------------------------------------
+class _EPAAttentionFn(Function):
+    """Everything of EPA.forward between the qkvv Linear and the output projections: ``dlka_epa_attention_forward/backward`` (csrc/cl_epa.hip)."""
+
+    @staticmethod
+    def forward(ctx, qkvv, kp, vp, temperature, temperature2, m1, m2, m2_scale):
+        from .ops import epa
+        x_sa, x_ca, saved = epa.attention_forward(qkvv, kp, vp, temperature, temperature2, m1, m2, m2_scale)
+        ctx.m2_scale = m2_scale
+        ctx.save_for_backward(qkvv, kp, vp, temperature, temperature2, saved, m1, m2)
+        return x_sa, x_ca
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_sa, g_ca):
+        from .ops import epa
+        qkvv, kp, vp, temperature, temperature2, saved, m1, m2 = ctx.saved_tensors
+        B, N, C = qkvv.shape[0], qkvv.shape[1], qkvv.shape[2] // 4
+        g_sa = torch.zeros((B, N, C), dtype=qkvv.dtype, device=qkvv.device) if g_sa is None else g_sa
+        g_ca = torch.zeros((B, N, C), dtype=qkvv.dtype, device=qkvv.device) if g_ca is None else g_ca
+        return (*epa.attention_backward(qkvv, kp, vp, temperature, temperature2, g_sa, g_ca, saved, m1, m2, ctx.m2_scale), None, None, None)
+
+
+class EPA(nn.Module):
+    """synapse/transformerblock.py:68-138 — same constructor, attribute names and ``state_dict`` keys (``E`` and ``F`` are ONE shared Linear, listed
+    under both names).  float32 with hidden_size / num_heads in {8, 16, 32, 64}, proj_size in {32, 64} and ``qkv_bias=False`` runs on csrc/cl_epa.hip;
+    anything else (other widths, bf16 autocast, CPU tensors) runs the same forward operator by operator in torch.
+
+    Dropout on the two attention maps: in training mode with p > 0 the module draws the multipliers itself (``_draw_masks``) — the same
+    distribution as ``F.dropout``, not the same generator consumption."""
+
+    SHARED_PROJECTION = True   # E is F (Synapse); the ACDC variant keeps two layers
+
+    def __init__(self, input_size, hidden_size, proj_size, num_heads=4, qkv_bias=False, channel_attn_drop=0.1, spatial_attn_drop=0.1):
+        super().__init__()
+        self.num_heads = num_heads
+        self.temperature = nn.Parameter(torch.ones(num_heads, 1, 1))
+        self.temperature2 = nn.Parameter(torch.ones(num_heads, 1, 1))
+        self.qkvv = nn.Linear(hidden_size, hidden_size * 4, bias=qkv_bias)
+        if self.SHARED_PROJECTION:
+            self.E = self.F = nn.Linear(input_size, proj_size)
+        else:
+            self.E = nn.Linear(input_size, proj_size)
+            self.F = nn.Linear(input_size, proj_size)
+        self.attn_drop = nn.Dropout(channel_attn_drop)
+        self.attn_drop_2 = nn.Dropout(spatial_attn_drop)
+        self.out_proj = nn.Linear(hidden_size, int(hidden_size // 2))
+        self.out_proj2 = nn.Linear(hidden_size, int(hidden_size // 2))
+
+    def fused(self, x):
+        """Whether ``forward(x)`` takes the fused kernels."""
+        from . import _lib
+        from .ops import epa
+        if not (x.is_cuda or _lib._test_backend) or x.ndim != 3 or self.qkvv.bias is not None:
+            return False
+        if ops.autocast_activation_dtype(x) != torch.float32 or any(p.dtype != torch.float32 for p in self.parameters()):
+            return False
+        return epa.supported(x.shape[2], self.num_heads, self.E.out_features, x.dtype)
+
+    def _draw_masks(self, B, N, device):
+        """(m1, m2, m2_scale): m1 float32 [B, heads, D, D] multipliers 0 or 1 / (1 - p) or None, m2 keep bytes [B, heads, N, P] or None."""
+        h, D, P = self.num_heads, self.qkvv.in_features // self.num_heads, self.E.out_features
+        m1 = m2 = None
+        scale = 1.0
+        p1, p2 = self.attn_drop.p, self.attn_drop_2.p
+        if self.attn_drop.training and p1 > 0:
+            m1 = torch.zeros(B, h, D, D, device=device) if p1 >= 1 else torch.empty(B, h, D, D, device=device).bernoulli_(1 - p1).div_(1 - p1)
+        if self.attn_drop_2.training and p2 > 0:
+            m2 = torch.zeros(B, h, N, P, dtype=torch.uint8, device=device) if p2 >= 1 else torch.empty(B, h, N, P, dtype=torch.uint8, device=device).bernoulli_(1 - p2)
+            scale = 0.0 if p2 >= 1 else 1.0 / (1 - p2)
+        return m1, m2, scale
+
+    @staticmethod
+    def _project(lin, t):
+        """lin(t) for the transposed view t [B, C, N] of a qkvv slot: one batched GEMM that reads the view in place."""
+        return torch.baddbmm(lin.bias, t, lin.weight.t().unsqueeze(0).expand(t.shape[0], -1, -1))
+
+    def forward(self, x):
+        if not self.fused(x):
+            return self.forward_per_op(x)
+        B, N, C = x.shape
+        qkvv = nn.functional.linear(x, self.qkvv.weight)
+        kp = self._project(self.E, qkvv[:, :, C:2 * C].transpose(1, 2))
+        vp = self._project(self.F, qkvv[:, :, 3 * C:].transpose(1, 2))
+        m1, m2, scale = self._draw_masks(B, N, x.device)
+        x_sa, x_ca = _EPAAttentionFn.apply(qkvv, kp, vp, self.temperature, self.temperature2, m1, m2, scale)
+        return torch.cat((self.out_proj(x_sa), self.out_proj2(x_ca)), dim=-1)
+
+    def forward_per_op(self, x, masks=None):
+        """The reference's forward, operator by operator (masks = (m1, m2, m2_scale) replaces the two Dropout layers' own draws)."""
+        B, N, C = x.shape
+        h = self.num_heads
+        qkvv = self.qkvv(x).reshape(B, N, 4, h, C // h).permute(2, 0, 3, 1, 4)
+        q, k, v_ca, v_sa = (t.transpose(-2, -1) for t in (qkvv[0], qkvv[1], qkvv[2], qkvv[3]))
+        kp, vp = self.E(k), self.F(v_sa)
+        q = nn.functional.normalize(q, dim=-1)
+        k = nn.functional.normalize(k, dim=-1)
+        attn_ca = ((q @ k.transpose(-2, -1)) * self.temperature).softmax(dim=-1)
+        attn_sa = ((q.permute(0, 1, 3, 2) @ kp) * self.temperature2).softmax(dim=-1)
+        if masks is None:
+            attn_ca, attn_sa = self.attn_drop(attn_ca), self.attn_drop_2(attn_sa)
+        else:
+            m1, m2, scale = masks
+            attn_ca = attn_ca if m1 is None else attn_ca * m1.view_as(attn_ca)
+            attn_sa = attn_sa if m2 is None else attn_sa * (m2.view_as(attn_sa).to(attn_sa.dtype) * scale)
+        x_ca = (attn_ca @ v_ca).permute(0, 3, 1, 2).reshape(B, N, C)
+        x_sa = (attn_sa @ vp.transpose(-2, -1)).permute(0, 3, 1, 2).reshape(B, N, C)
+        return torch.cat((self.out_proj(x_sa), self.out_proj2(x_ca)), dim=-1)
+
+    @torch.jit.ignore
+    def no_weight_decay(self):
+        return {'temperature', 'temperature2'}
+
+
+class _LayerNormTokensFn(Function):
+    """(NCDHW volume, pos_embed) -> (tokens + pos_embed, LayerNorm of them): ``dlka_layernorm_tokens_forward/backward``."""
+
+    @staticmethod
+    def forward(ctx, x, pos, weight, bias, eps):
+        xt, xn, stats = ops.layernorm_tokens_forward(x, True, pos, weight, bias, eps)
+        ctx.shape, ctx.with_pos = tuple(x.shape), pos is not None
+        ctx.save_for_backward(xt, stats, weight)
+        return xt, xn
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_xt, g_xn):
+        xt, stats, weight = ctx.saved_tensors
+        g_xn = torch.zeros_like(xt) if g_xn is None else g_xn
+        gxt, gw, gb, gpos = ops.layernorm_tokens_backward(g_xn, g_xt, xt, stats, weight, ctx.with_pos)
+        B, C = ctx.shape[:2]
+        return ops.ndhwc_to_ncdhw(gxt.view(B, *ctx.shape[2:], C)), gpos, gw, gb, None
+
+
+class _ScaleResidualFn(Function):
+    """xt + gamma * e: ``dlka_scale_residual_forward/backward``."""
+
+    @staticmethod
+    def forward(ctx, xt, e, gamma):
+        ctx.save_for_backward(e, gamma)
+        return ops.scale_residual_forward(xt, e, gamma)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        e, gamma = ctx.saved_tensors
+        g = g.contiguous()
+        ge, gg = ops.scale_residual_backward(g, e, gamma)
+        return g, ge, gg
+
+
+class TransformerBlock(nn.Module):
+    """synapse/transformerblock.py:6-65 — the UNETR++ block around ``EPA``; same constructor, attribute names and ``state_dict`` keys.  Composed from
+    the package's pieces: LayerNorm and the gamma-scaled residual on the token kernels, ``UnetResBlock`` and the 1x1x1 conv on the conv kernels (float32,
+    hidden_size a multiple of 32); anything else — bf16 autocast, another width, CPU tensors — runs the same forward operator by operator in torch."""
+
+    EPA_BLOCK = EPA
+    EXTRA_RES_BLOCK = False   # the ACDC variant's conv52
+
+    def __init__(self, input_size: int, hidden_size: int, proj_size: int, num_heads: int, dropout_rate: float = 0.0, pos_embed=False) -> None:
+        super().__init__()
+        if not (0 <= dropout_rate <= 1):
+            raise ValueError("dropout_rate should be between 0 and 1.")
+        if hidden_size % num_heads != 0:
+            raise ValueError("hidden_size should be divisible by num_heads.")
+        self.norm = nn.LayerNorm(hidden_size)
+        self.gamma = nn.Parameter(1e-6 * torch.ones(hidden_size), requires_grad=True)
+        self.epa_block = self.EPA_BLOCK(input_size=input_size, hidden_size=hidden_size, proj_size=proj_size, num_heads=num_heads,
+                                        channel_attn_drop=dropout_rate, spatial_attn_drop=dropout_rate)
+        self.conv51 = UnetResBlock(3, hidden_size, hidden_size, kernel_size=3, stride=1, norm_name="batch")
+        if self.EXTRA_RES_BLOCK:
+            self.conv52 = UnetResBlock(3, hidden_size, hidden_size, kernel_size=3, stride=1, norm_name="batch")
+        self.conv8 = nn.Sequential(nn.Dropout3d(0.1, False), nn.Conv3d(hidden_size, hidden_size, 1))
+        self.pos_embed = None
+        if pos_embed:
+            self.pos_embed = nn.Parameter(torch.zeros(1, input_size, hidden_size))
+
+    def on_kernels(self, x):
+        """Whether ``forward(x)`` composes the HIP kernels: float32 (no bf16 autocast), hidden_size a multiple of 32 up to 1024, on the GPU."""
+        from . import _lib
+        C = x.shape[1]
+        return ((x.is_cuda or _lib._test_backend) and x.dtype == torch.float32 and ops.autocast_activation_dtype(x) == torch.float32
+                and C % 32 == 0 and C <= 1024 and all(p.dtype == torch.float32 for p in self.parameters()))
+
+    def forward(self, x):
+        if not self.on_kernels(x):
+            return self.forward_per_op(x)
+        B, C, H, W, D = x.shape
+        with torch.autocast(x.device.type, enabled=False):
+            xt, xn = _LayerNormTokensFn.apply(x, self.pos_embed, self.norm.weight, self.norm.bias, self.norm.eps)
+            attn = _ScaleResidualFn.apply(xt, self.epa_block(xn), self.gamma)
+            attn_skip = attn.view(B, H, W, D, C).permute(0, 4, 1, 2, 3)
+            a = self.conv51(attn_skip)
+            if self.EXTRA_RES_BLOCK:
+                a = self.conv52(a)
+            c8 = self.conv8[1]
+            return (attn_skip + nn_ops.conv3d(self.conv8[0](a), c8.weight, c8.bias)).contiguous()
+
+    @staticmethod
+    def _res_block_per_op(blk, x):
+        """UnetResBlock (stride 1, equal widths) in torch: conv, norm, LeakyReLU, conv, norm, + input, LeakyReLU."""
+        f = nn.functional
+        out = f.leaky_relu(blk.norm1(f.conv3d(x, blk.conv1.conv.weight, None, 1, 1)), 0.01)
+        out = blk.norm2(f.conv3d(out, blk.conv2.conv.weight, None, 1, 1))
+        return f.leaky_relu(out + x, 0.01)
+
+    def forward_per_op(self, x):
+        """The reference's forward, operator by operator in torch: any width, dtype, device or autocast state the kernels do not cover."""
+        B, C, H, W, D = x.shape
+        t = x.reshape(B, C, H * W * D).permute(0, 2, 1)
+        if self.pos_embed is not None:
+            t = t + self.pos_embed
+        attn = t + self.gamma * self.epa_block(self.norm(t))
+        attn_skip = attn.reshape(B, H, W, D, C).permute(0, 4, 1, 2, 3)
+        a = self._res_block_per_op(self.conv51, attn_skip)
+        if self.EXTRA_RES_BLOCK:
+            a = self._res_block_per_op(self.conv52, a)
+        return attn_skip + self.conv8(a)

@@ -1219,6 +1219,34 @@ int dlka_dstats_unique_labels(const void *seg, const dlka_dstats_desc *d, uint32
 long dlka_dstats_launch_count(void);
 
 /* =======================================================================================
+ * Efficient paired attention (UNETR++ EPA, the reference's TransformerBlock: synapse/transformerblock.py:68-138) — csrc/cl_epa.hip
+ * =======================================================================================
+ * float32; D = C / heads in {8, 16, 32, 64}, P in {32, 64}, any N.  Per sample b and head h, with Q, K, Vc, Vs the four D-wide column
+ * groups of qkvv [B][N][4][heads][D] (the Linear's own output, read in place):
+ *   rq_i = 1 / max(|Q[:, i]|, 1e-12) over the N tokens, rk_j likewise;   Qh = Q rq, Kh = K rk
+ *   A = softmax_j((Qh^T Kh)[i][j] temperature[h]);   x_ca[b][n][h D + i] = sum_j (A m1)[i][j] Vc[n][j]
+ *   S[n] = softmax_p(Qh[n] . kp[b][h D + :][p] temperature2[h]);   Y[n][i] = sum_p (S m2)[n][p] vp[b][h D + i][p], stored to
+ *   x_sa at flat offset ((b D + i) heads + h) N + n — what the reference's permute(0, 3, 1, 2).reshape(B, N, C) of [B][heads][N][D] holds.
+ * kp, vp [B][C][P]: the projections of K and Vs over the tokens (a GEMM the caller runs).  temperature, temperature2 [heads].
+ * m1: optional float multipliers [B][heads][D][D]; m2: optional keep bytes [B][heads][N][P], a set byte multiplies by m2_scale.
+ * saved: the forward call's statistics (saved_bytes), handed to the backward call unchanged.  Backward: g_x_sa in x_sa's layout, g_x_ca [B][N][C];
+ * g_qkvv [B][N][4 C] is fully overwritten with the gradient through Q, the channel branch's K and Vc (slot 3, Vs, is zero: Vs and the spatial
+ * branch's K are reached through vp / kp, whose gradients g_vp / g_kp [B][C][P] the caller carries through its GEMMs); g_temperature_bh and
+ * g_temperature2_bh [B][heads] are per sample and are summed over B by the caller.  Sums over tokens are per-workgroup partial tiles folded in
+ * workgroup order, no float atomics: identical calls give identical bits.  Return codes: DLKA_ERR_NULL, DLKA_ERR_DTYPE, DLKA_ERR_SHAPE (a size
+ * < 1), DLKA_ERR_UNSUPPORTED (a width outside the set, 2^31 elements or more in qkvv or in the N x P map), DLKA_ERR_WORKSPACE. */
+int dlka_epa_supported(int C, int heads, int P, int dtype);
+size_t dlka_epa_saved_bytes(int B, int C, int heads);
+size_t dlka_epa_workspace_bytes(int B, int N, int C, int heads, int P, int backward);
+int dlka_epa_attention_forward(const void *qkvv, const void *kp, const void *vp, const void *temperature, const void *temperature2, const void *m1,
+                               const void *m2, float m2_scale, void *x_sa, void *x_ca, void *saved, void *workspace, size_t workspace_bytes, int B, int N,
+                               int C, int heads, int P, int dtype, void *stream);
+int dlka_epa_attention_backward(const void *qkvv, const void *kp, const void *vp, const void *temperature, const void *temperature2, const void *m1,
+                                const void *m2, float m2_scale, const void *saved, const void *g_x_sa, const void *g_x_ca, void *g_qkvv, void *g_kp,
+                                void *g_vp, void *g_temperature_bh, void *g_temperature2_bh, void *workspace, size_t workspace_bytes, int B, int N, int C,
+                                int heads, int P, int dtype, void *stream);
+
+/* =======================================================================================
  * Launch trace — measurement aid (no reference counterpart; the reference has no profiling hooks)
  * =======================================================================================
  * Between dlka_trace_start and dlka_trace_stop every kernel launch of the library is followed by a HIP timing event on the
